@@ -169,15 +169,32 @@ def visible_gpu_count():
     return n
 
 
+def hip_gpu_count():
+    """GPUs the HIP runtime shows a rank started from here, counted by a short-lived child process that has exited
+    before any rank starts (the launcher parent itself still holds no KFD handle).  The KFD topology lists every GPU of
+    the node, also those a container's device cgroup or a UUID-valued *_VISIBLE_DEVICES keeps from this process, so
+    it is only an upper bound.  None when the probe fails (the ranks then report a shortage themselves)."""
+    import subprocess
+    try:
+        r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"],
+                           capture_output=True, text=True, timeout=300)
+        return int(r.stdout.split()[-1]) if r.returncode == 0 else None
+    except (OSError, ValueError, IndexError, subprocess.TimeoutExpired):
+        return None
+
+
 def self_launch(n):
     """`python bench.py --gpus N` (N > 1) without a launcher: start the N ranks as children of ONE fresh
     `python -m torch.distributed.run` (the reference starts its N workers from one command as well,
     lib/test.py:327-344) and return its exit code.  The parent counts the devices from the KFD topology in sysfs
-    (visible_gpu_count: no HIP call, no KFD handle held for the run) and never touches the GPU; no exec.  `--standalone` keeps the rendezvous on a TCPStore
+    (visible_gpu_count: no HIP call; when that allows N, hip_gpu_count in a child that exits first: no KFD handle held
+    for the run) and never touches the GPU; no exec.  `--standalone` keeps the rendezvous on a TCPStore
     the agent binds itself (port 0) and hands to the workers: no bind-close-reuse of a port."""
     import subprocess
     if os.environ.get("SHF_BENCH_ONE_GPU") != "1":
         n_dev = visible_gpu_count()
+        if n_dev is None or n_dev >= n:
+            n_dev = hip_gpu_count()
         if n_dev is not None and n_dev < n:
             raise SystemExit("bench.py --gpus %d needs %d visible MI355X, found %d (SHF_BENCH_ONE_GPU=1 --backend gloo runs "
                              "all ranks on one GPU for validation)" % (n, n, n_dev))
@@ -191,6 +208,27 @@ def self_launch(n):
     print("bench.py: starting %d ranks: %s" % (n, " ".join(cmd)), file=sys.stderr, flush=True)
     # the children inherit stdout / stderr: rank 0's JSON line and every rank's diagnostics appear as they are written
     return subprocess.call(cmd, env=env, cwd=ROOT)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, last):
+    """--dump-outputs: the detections the timed path handed back in its last step ({window image: (n, 5) array}, this
+    rank's images only) as out_dir/detections_image<i>.npy, float32 / float64 as returned.  A list is bounded by the
+    runtime's detection cap, so the whole dump is a few hundred KB; the limit below only guards that assumption."""
+    arrays = {}
+    for i, v in sorted(last.items()):
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        arrays["detections_image%d" % i] = np.array(a, copy=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of detections exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -217,6 +255,11 @@ def main():
                          "blobs to the C ABI each step; 'image' uploads the raw uint8 image and builds the pyramid on "
                          "the device (shf_make_pyramid_level)")
     ap.add_argument("--dump-dets", default=None, help="rank 0 writes the detections of window image 0 to this .npy")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, every rank writes what the timed path returned in its last step -- the "
+                         "(n, 5) [x1, y1, x2, y2, score] detections of each window image it owns -- as "
+                         "DIR/detections_image<i>.npy (float32 / float64 as returned; the inputs are seeded, so two builds "
+                         "can be compared file for file)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for "
                     "validating the N>1 code path with several ranks on ONE GPU: SHF_BENCH_ONE_GPU=1)")
     ap.add_argument("--lanes", type=int, default=5, help="execution lanes (HIP streams) per GPU in --mode streams")
@@ -246,6 +289,8 @@ def main():
     ap.add_argument("--no-files", action="store_true", help="skip the file-to-detections leg ('from_files', N=1; part of the "
                     "mixed-shape leg: the same shapes as JPEG files through test.fused_image_loop into the WIDER writer)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (it is the number of timed steps)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: start the N ranks ourselves (the reference starts its N workers from one
@@ -439,6 +484,8 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     headline_dets = np.array(last[0], copy=True) if (world == 1 and 0 in last) else None   # (later legs overwrite `last`)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     if host_trace is not None and dist_path:
         print("host time per window (ms): " + ", ".join("%s %.2f" % (k, 1e3 * v / max(1, sd.collectives)) for k, v in sd.host_seconds.items()), file=sys.stderr)
     if host_trace:

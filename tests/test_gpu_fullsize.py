@@ -281,12 +281,13 @@ def test_c4_wider_shaped_pyramid_vs_oracle():
 
 def _run_bench(tmp_path, world, extra, tag, more_env=None, bare=False):
     out = str(tmp_path / ("dets_%s.npy" % tag))
+    outs = tmp_path / ("outputs_%s" % tag)
     env = dict(os.environ, PYTHONPATH=ROOT, SHF_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0", **(more_env or {}))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     base = [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "0", "--no-cpu-baseline",
             "--no-latency", "--no-calib", "--no-reduced", "--no-mixed", "--no-forward-path", "--overlap-seconds", "0",
-            "--sustain-seconds", "0", "--dump-dets", out] + extra
+            "--sustain-seconds", "0", "--dump-dets", out, "--dump-outputs", str(outs)] + extra
     if world == 1:
         cmd = [sys.executable] + base
     elif bare:
@@ -304,7 +305,11 @@ def _run_bench(tmp_path, world, extra, tag, more_env=None, bare=False):
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (tag, r.stdout[-1500:], r.stderr[-3000:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
-    return np.load(out), json.loads(line)
+    dets = np.load(out)
+    # --dump-outputs: every window image's detections, each written by its owner rank; image 0 is --dump-dets' array
+    assert sorted(os.listdir(outs)) == sorted("detections_image%d.npy" % i for i in range(world)), (tag, os.listdir(outs))
+    np.testing.assert_array_equal(np.load(outs / "detections_image0.npy"), dets)
+    return dets, json.loads(line)
 
 
 @pytest.mark.timeout(1800)
@@ -339,18 +344,27 @@ def test_c5_two_and_four_ranks_equal_one_rank(tmp_path):
 
 
 @pytest.mark.timeout(1800)
-def test_c5_eight_ranks_like_the_scaling_run(tmp_path):
-    """The command the driver's scaling run ends with -- `python bench.py --gpus 8` -- on the one GPU there is (gloo, all
-    ranks on it): the balanced window schedule (every rank one unit of each kind per window of 8 images) and the north
-    star's strict one-scale-per-GPU form (ranks 0-4 hold 2 flips x 8 images = 16 units = exactly one grouped pass, ranks
-    5-7 only take part in the exchange) both reproduce the 1-rank detections bit for bit."""
-    d1, _ = _run_bench(tmp_path, 1, [], "c5_n1_for8")
-    d8, j8 = _run_bench(tmp_path, 8, ["--shard", "window"], "c5_n8_window", bare=True)
-    np.testing.assert_array_equal(d1, d8)
-    assert j8["n_gpus"] == 8 and j8["collective_ranks"] == 8 and j8["config"]["images_per_step"] == 8
-    d8s, j8s = _run_bench(tmp_path, 8, ["--shard", "strict"], "c5_n8_strict", bare=True)
-    np.testing.assert_array_equal(d1, d8s)
-    assert j8s["config"]["shard"] == "strict"
+def test_c5_scaling_run_command_on_four_ranks(tmp_path):
+    """The command the driver's scaling run ends with -- `python bench.py --gpus N`, started bare -- on the one GPU there
+    is (gloo, all ranks on it), with N = 4: at most six processes may hold the GPU at once, and this test process and
+    the launcher are two of them.  The balanced window schedule (every rank two or three units of each image of a window
+    of 4), the strict one-scale-per-GPU form with a surplus rank (3 levels on 4 ranks: rank 3 only takes part in the
+    exchange) and strict sharding at exactly one grouped pass per rank (8 levels on 4 ranks: 2 levels x 2 flips x 4
+    images = 16 units) all reproduce the 1-rank detections bit for bit."""
+    d1, _ = _run_bench(tmp_path, 1, [], "c5_n1_for4")
+    d4, j4 = _run_bench(tmp_path, 4, ["--shard", "window"], "c5_n4_window_bare", bare=True)
+    np.testing.assert_array_equal(d1, d4)
+    assert j4["n_gpus"] == 4 and j4["collective_ranks"] == 4 and j4["config"]["images_per_step"] == 4
+    three = ["--source", "240x320", "--scales", "100,200,300"]
+    d1t, _ = _run_bench(tmp_path, 1, three, "l3_n1")
+    d4t, j4t = _run_bench(tmp_path, 4, three + ["--shard", "strict"], "l3_n4_strict", bare=True)
+    np.testing.assert_array_equal(d1t, d4t)
+    assert j4t["config"]["shard"] == "strict" and j4t["collective_ranks"] == 4 and len(d1t) > 0
+    eight = ["--source", "240x320", "--scales", "100,150,200,250,300,350,400,450"]
+    d1e, _ = _run_bench(tmp_path, 1, eight, "l8_n1")
+    d4e, j4e = _run_bench(tmp_path, 4, eight + ["--shard", "strict"], "l8_n4_strict", bare=True)
+    np.testing.assert_array_equal(d1e, d4e)
+    assert j4e["config"]["units_per_image"] == 16 and j4e["config"]["shard"] == "strict" and len(d1e) > 0
 
 
 @pytest.mark.timeout(1800)

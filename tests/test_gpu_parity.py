@@ -375,9 +375,8 @@ def test_every_blob_is_readable_after_forward(dd, conv_mode):
 def test_hostile_layer_parameters_are_refused_by_name(bad, msg, conv_mode):
     """BaseConvolutionLayer::LayerSetUp's CHECKs (base_conv_layer.cpp:21-120) abort Caffe; here a prototxt with a zero stride,
     a zero / absurd kernel, no or 10^11 outputs ... is refused at caffe.Net() with the layer's name -- no division by zero, no
-    2^31-channel allocation, the process lives on (tests/test_parser_robustness.py covers the SYNTAX of hostile files)."""
-    if conv_mode != "fp32":
-        pytest.skip("graph construction only")
+    2^31-channel allocation, the process lives on (tests/test_parser_robustness.py covers the SYNTAX of hostile files).
+    Graph construction takes the conv mode from SHF_CONV_MODE, so both modes' construction paths refuse them."""
     from smallhardface_amd import caffe
     key = bad.split(":")[0]
     base = {"num_output": "num_output: 8", "kernel_size": "kernel_size: 3", "pad": "pad: 1", "stride": "", "dilation": "", "group": ""}
@@ -649,9 +648,8 @@ np.savez(sys.argv[1], *got)
 ])
 def test_device_preprocessing_bit_exact(shape, scales, flip, conv_mode):
     """shf_make_pyramid_level == _get_image_blob + flip + pad of the host mirror, bit for bit
-    (mean subtraction and interpolation in float64, the blob narrowed to fp32 last)."""
-    if conv_mode != "fp32":
-        pytest.skip("no convolution in this test")
+    (mean subtraction and interpolation in float64, the blob narrowed to fp32 last); the conv mode of the net whose
+    stream builds the levels changes nothing."""
     import torch
     from smallhardface_amd import test as T
     cfg.TEST.FLIP = flip
@@ -675,9 +673,7 @@ def test_device_preprocessing_bit_exact(shape, scales, flip, conv_mode):
                                           ((33, 250), [0.0625, 1.0 / 3.0, 1.28])])
 def test_get_image_blob_on_the_device_equals_the_host_mirror(shape, scales, conv_mode):
     """detect()'s pre-processing step with host blobs out (C ABI shf_image_blobs; the reference calls cv2.resize here) ==
-    the numpy mirror _get_image_blob, bit for bit, unpadded and unflipped like the reference's blobs."""
-    if conv_mode != "fp32":
-        pytest.skip("no convolution in this test")
+    the numpy mirror _get_image_blob, bit for bit, unpadded and unflipped like the reference's blobs, in either conv mode."""
     from smallhardface_amd import test_utils as TU
     im = np.random.default_rng(shape[1]).integers(0, 256, shape + (3,)).astype(np.uint8)
     want = TU._get_image_blob(im, scales)
@@ -738,9 +734,7 @@ def test_kernel_selection_knobs_do_not_change_results(tmp_path, conv_mode):
     alone, so no grouping may change a bit); kernels with another accumulation scheme (8-wave two-accumulator, conv1_1
     on the vector ALUs) agree to fp32-class tolerance on the PRE-MERGE rows (a borderline IoU >= 0.4 decision of the
     greedy vote cascades through a whole pile of overlapping boxes, so voted rows are compared only between builds of
-    the same arithmetic)."""
-    if conv_mode != "f16x3":
-        pytest.skip("split-fp16 knobs")
+    the same arithmetic).  In fp32 mode the same knobs must leave the exact path's results as they are."""
     import os
     import subprocess
     import sys
@@ -760,7 +754,7 @@ for name, blobs in onet.params.items():
     if name.startswith("conv") and len(blobs) > 1:
         blobs[1][...] = rng.normal(0, 0.05, blobs[1].shape).astype(np.float32)
 H.load_params(gnet, onet.params)
-gnet.set_conv_mode("f16x3")
+gnet.set_conv_mode(sys.argv[2])
 im = np.random.default_rng(5).integers(0, 256, (150, 200, 3)).astype(np.uint8)
 units = list(T.pyramid_units(im))
 fd = T.FusedDetector(gnet, n_lanes=6, mode="group")
@@ -780,7 +774,8 @@ np.savez(sys.argv[1], voted=voted, raw=buf[:n].cpu().numpy())
                       ("pc_block_per_tile", {"SHF_F16X3_PC_PERSIST": "0"})):
         out = str(tmp_path / (name + ".npz"))
         e = dict(os.environ, PYTHONPATH=root, **env)
-        r = subprocess.run([sys.executable, str(script), out], env=e, cwd=root, capture_output=True, text=True, timeout=600)
+        r = subprocess.run([sys.executable, str(script), out, conv_mode], env=e, cwd=root, capture_output=True, text=True,
+                           timeout=600)
         assert r.returncode == 0, (name, r.stderr[-1500:])
         outs[name] = np.load(out)
     assert len(outs["default"]["voted"]) > 0 and len(outs["default"]["raw"]) > len(outs["default"]["voted"])
@@ -801,9 +796,8 @@ def test_full_bench_pyramid_properties(conv_mode):
     """BASELINE's full-size workload (1024x1024 source, scales 100..1400 x flip = 10 units, 5 TFLOP) through the
     fused path: size-independent properties instead of an oracle run -- determinism (twice, and pipelined vs one
     at a time, and from the raw uint8 image through the device pyramid), score order and range, boxes inside the
-    image, and idempotence of the merge (voting the voted boxes again changes nothing but exact duplicates)."""
-    if conv_mode != "f16x3":
-        pytest.skip("full-size run once, in the benchmarked arithmetic")
+    image, and idempotence of the merge (voting the voted boxes again changes nothing but exact duplicates), in the
+    benchmarked split-fp16 arithmetic and in exact fp32."""
     from smallhardface_amd import caffe, nms, test as T, weights
     from smallhardface_amd.config import cfg_from_file
     import os
@@ -812,7 +806,7 @@ def test_full_bench_pyramid_properties(conv_mode):
     msg = P._add_dimension_reduction(P.build_test_template(True))
     net = caffe.Net(None, prototxt_text=P.dumps(msg))
     H.load_params(net, weights.synth_params(msg, seed=1234))
-    net.set_conv_mode("f16x3")
+    net.set_conv_mode(conv_mode)
     im = np.random.default_rng(1000).integers(0, 256, (1024, 1024, 3)).astype(np.uint8)
     units = list(T.pyramid_units(im))
     assert len(units) == 10 and max(u[1] for u in units) == 1408
