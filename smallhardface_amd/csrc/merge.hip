@@ -23,7 +23,7 @@ static inline unsigned grid_for(long long n, int block = 256) {
 
 __global__ void make_keys_kernel(const float* __restrict__ dets5, int n, u64* __restrict__ keys) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    keys[i] = ((u64)__float_as_uint(dets5[i * 5 + 4]) << 32) | (u64)(0xFFFFFFFFu - (unsigned)i);
+    keys[i] = score_key(dets5[i * 5 + 4], (unsigned)i);
 }
 
 int launch_make_keys(const float* dets5, int n, u64* keys, hipStream_t s) {
@@ -111,7 +111,7 @@ int launch_iou_mask(const float* sorted5, int n, float thr, int ge_pred, u64* ma
 // ascending order, whose row covers k (a ballot per newly removed box).
 // (Round 2: one wave did both jobs, 2.4 us per block of 64 boxes = 0.26 ms for the bench image's 6 800 boxes.)
 // ---------------------------------------------------------------------------
-constexpr int SCAN_MAX_WORDS = 4096;  // 262144 boxes
+constexpr int SCAN_MAX_WORDS = kMergeMaxBoxes / 64;
 constexpr int SCAN_WAVES = 16, SCAN_PRE = 4;   // words per wave whose rows are fetched ahead of the chain
 
 __device__ __forceinline__ u64 wave_or_u64(u64 v) {
@@ -201,6 +201,7 @@ __global__ __launch_bounds__(64 * SCAN_WAVES) void greedy_scan_kernel(const u64*
 }
 
 int launch_greedy_scan(const u64* mask, int n, int* cluster, int* heads, int* counters, hipStream_t s) {
+  // (MergeCtx::run refuses such an n before it allocates or launches anything)
   if ((n + 63) / 64 > SCAN_MAX_WORDS) { set_error("merge: too many boxes for the scan bitmap"); return -1; }
   hipLaunchKernelGGL(greedy_scan_kernel, dim3(1), dim3(64 * SCAN_WAVES), 0, s, mask, n, cluster, heads, counters);
   SHF_HIP_OK(hipGetLastError());
@@ -210,8 +211,8 @@ int launch_greedy_scan(const u64* mask, int n, int* cluster, int* heads, int* co
 // ---------------------------------------------------------------------------
 // bbox_vote accumulation, one thread per cluster head (test.py:199-214).
 // numpy semantics reproduced: fp32 products, row-order (sequential) fp32 sum of the
-// weighted boxes (np.sum(axis=0) on an (m,4) view), numpy's pairwise summation for the
-// strided 1-D score sum, fp32 divide, result widened to fp64.
+// weighted boxes (np.sum(axis=0) on an (m,4) view), numpy's buffered pairwise summation
+// for the strided 1-D score sum, fp32 max, fp32 divide, result widened to fp64.
 // ---------------------------------------------------------------------------
 struct MemberIter {
   const u64* row;  // mask row of the head
@@ -268,6 +269,16 @@ __device__ float pairwise_scores(MemberIter& it, int n) {
   return a + b;
 }
 
+// np.sum of the strided (m, 1) score column: numpy's buffered reduction copies it into buffers of NPY_BUFSIZE = 8192
+// elements (numpy/core/include/numpy/ndarraytypes.h), sums each buffer pairwise and adds the buffer sums in order onto
+// the identity 0 -- past 8192 members not the same rounding as one pairwise sum over the column
+constexpr int NPY_BUFSIZE = 8192;
+__device__ float numpy_sum_scores(MemberIter& it, int n) {
+  float res = 0.f;
+  for (int i = 0; i < n; i += NPY_BUFSIZE) res += pairwise_scores(it, min(n - i, NPY_BUFSIZE));
+  return res;
+}
+
 // one cluster, one thread: the round-1/2 form, kept for clusters beyond the wave kernel's LDS list
 __device__ void vote_one_serial(const float* __restrict__ dets, const u64* __restrict__ mask, const int* __restrict__ cluster,
                                 int nw, int h, int t, int nheads, double* __restrict__ rows, int* __restrict__ emit) {
@@ -296,7 +307,7 @@ __device__ void vote_one_serial(const float* __restrict__ dets, const u64* __res
     else { sx1 += px1; sy1 += py1; sx2 += px2; sy2 += py2; mx = fmaxf(mx, sc); }
   }
   it.init(mask, cluster, dets, h, nw);
-  const float ssum = pairwise_scores(it, m);
+  const float ssum = numpy_sum_scores(it, m);
   o[0] = (double)(sx1 / ssum); o[1] = (double)(sy1 / ssum);
   o[2] = (double)(sx2 / ssum); o[3] = (double)(sy2 / ssum);
   o[4] = (double)mx;
@@ -331,6 +342,7 @@ __device__ float pairwise_array(const float* a, int n) {
 // in member order (np.sum(axis=0) of the (m, 4) products), every lane forms numpy's pairwise score sum.  Bit-for-bit
 // what the one-thread form computes (round 2: 0.21 ms for the bench image, latency-bound on dependent row loads).
 constexpr int VOTE_CAP = 1024;
+static_assert(VOTE_CAP <= NPY_BUFSIZE, "the wave form sums its scores as ONE numpy buffer");
 __global__ __launch_bounds__(64) void vote_accumulate_kernel(const float* __restrict__ dets, const u64* __restrict__ mask,
                                                              const int* __restrict__ cluster, int n,
                                                              const int* __restrict__ heads,
@@ -388,7 +400,7 @@ __global__ __launch_bounds__(64) void vote_accumulate_kernel(const float* __rest
       continue;
     }
     __syncthreads();
-    float mx = 0.f;
+    float mx = -INFINITY;   // (np.max: scores may all be negative)
     for (int i = lane; i < m; i += 64) {
       const float* d = dets + (size_t)idx[i] * 5;
       const float sc = d[4];
@@ -399,7 +411,7 @@ __global__ __launch_bounds__(64) void vote_accumulate_kernel(const float* __rest
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
     __syncthreads();
-    const float ssum = pairwise_array(scs, m);
+    const float ssum = 0.f + pairwise_array(scs, m);   // (onto numpy's identity 0, as numpy_sum_scores)
     if (lane < 4) {
       float sacc = prod[lane];
       for (int i = 1; i < m; ++i) sacc += prod[i * 4 + lane];

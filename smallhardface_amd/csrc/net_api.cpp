@@ -336,6 +336,7 @@ int shf_nms(const float* dets5, int n, float thresh, int device_id, int32_t* kee
     HIP_THROW(hipGetDevice(&cur));
     if (cur != device_id) HIP_THROW(hipSetDevice(device_id));  // _set_device, nms_kernel.cu:91-100
   }
+  CHECK_RC(MergeCtx::refuse_size(n));   // (before the input is staged)
   box_ctx_init();
   g_box_in->ensure((size_t)n * 5 * 4);
   HIP_THROW(hipMemcpyAsync(g_box_in->p, dets5, (size_t)n * 5 * 4, hipMemcpyHostToDevice, g_box_stream));
@@ -353,6 +354,7 @@ int shf_bbox_vote(const float* dets5, int n, float thresh, double* out5, int cap
     *n_out = 1;
     return 0;
   }
+  CHECK_RC(MergeCtx::refuse_size(n));   // (before the input is staged)
   box_ctx_init();
   g_box_in->ensure((size_t)n * 5 * 4);
   HIP_THROW(hipMemcpyAsync(g_box_in->p, dets5, (size_t)n * 5 * 4, hipMemcpyHostToDevice, g_box_stream));
@@ -382,6 +384,7 @@ int shf_debug_merge(const float* dets5, int n, float thresh, int ge_pred, unsign
                     int* cluster_out, int* heads_out, int* n_heads, float* sorted_out, int* perm_out) {
   API_BEGIN
   std::lock_guard<std::mutex> lk(g_box_mu);
+  CHECK_RC(MergeCtx::refuse_size(n));   // (before the input is staged)
   box_ctx_init();
   g_box_in->ensure((size_t)n * 5 * 4);
   HIP_THROW(hipMemcpyAsync(g_box_in->p, dets5, (size_t)n * 5 * 4, hipMemcpyHostToDevice, g_box_stream));

@@ -270,12 +270,21 @@ struct MergeCtx {
   std::vector<double> hout;
   std::vector<int> hidx;
 
+  // more boxes than the greedy scan holds: refused before anything is allocated or launched
+  static int refuse_size(int n) {
+    if (n <= kMergeMaxBoxes) return 0;
+    set_error("merge: " + std::to_string(n) + " boxes exceed the limit of " + std::to_string(kMergeMaxBoxes) +
+              " (the greedy scan's bitmap)");
+    return -1;
+  }
+
   // dets_dev: (n,5) fp32 on the device.  method 0 = vote (>=), 1 = nms (>).
   // vote: rows -> out5 (cap rows) ; nms: kept ORIGINAL indices -> keep
   int run(const float* dets_dev, int n, int method, float thr, double* out5, int cap, int* n_out, int32_t* keep,
           hipStream_t s) {
     *n_out = 0;
     if (n <= 0) return 0;
+    CHECK_RC(refuse_size(n));
     size_t npad = 1;
     while (npad < (size_t)n) npad <<= 1;
     const size_t nw = ((size_t)n + 63) / 64;

@@ -188,7 +188,22 @@ struct AppendUnit {
 int launch_append_dets_group(const AppendUnit* us, int n, int topN, float thresh, int pass, int per_member,
                              hipStream_t s);
 
+// ---- score sort keys -------------------------------------------------------------
+// Keys are (order bits of the score) << 32 | (0xFFFFFFFF - index), sorted descending as u64: score descending, then
+// index ascending (the oracle's canonical_order).  The raw IEEE bits do not order by value once a score is negative,
+// so -0.0 is folded onto +0.0 and then a negative value has all its bits flipped, a non-negative one its sign bit set.
+// A key is never 0 (the low word is not 0 below 2^32 - 1 rows), so 0 stays free as a "no key" sentinel.
+__device__ __forceinline__ unsigned score_order_bits(float f) {
+  unsigned u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ unsigned long long score_key(float f, unsigned idx) {
+  return ((unsigned long long)score_order_bits(f) << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
+}
+
 // ---- box merging ----------------------------------------------------------------
+constexpr int kMergeMaxBoxes = 262144;   // the greedy scan's removed bitmap: 4096 64-box words in LDS (merge.hip)
 struct MergeWork {
   float* sorted = nullptr;                // [n][5] score-descending
   unsigned long long* mask = nullptr;     // [n][ceil(n/64)]

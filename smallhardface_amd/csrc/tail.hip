@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void tail_decode_kernel(DecodeGK g) {
       const float ws = x2 - x1 + 1.f, hs = y2 - y1 + 1.f;
       valid = valid && (ws >= p.min_size_scaled) && (hs >= p.min_size_scaled);
       if (valid) {
-        key = ((unsigned long long)__float_as_uint(fg) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
+        key = score_key(fg, (unsigned)n);
         best = key > best ? key : best;
         cand = fg >= g.score_thresh;
       }
@@ -633,7 +633,7 @@ __global__ void append_dets_kernel(AppendGK g) {
     }
     float* d = p.dets5 + (size_t)pos * 5;
     d[0] = x1 / p.im_scale; d[1] = y1 / p.im_scale; d[2] = x2 / p.im_scale; d[3] = y2 / p.im_scale; d[4] = fg;
-    p.keys[pos] = ((unsigned long long)__float_as_uint(fg) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)pos);
+    p.keys[pos] = score_key(fg, (unsigned)pos);
   }
 }
 
