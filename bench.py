@@ -13,9 +13,14 @@ ranks so that each rank runs one unit of every (level, flip) kind per window; th
 detections of an image are sent to its owner rank with ONE RCCL all_to_all per window
 (smallhardface_amd/pyramid.py).
 
-Rank 0 prints ONE JSON line (contract in the task description) with two extra objects:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; rank 0's ONE JSON line
+carries the headline fields and
   roofline      dominant kernel (split-fp16 MFMA implicit-GEMM conv, or the exact fp32 MFMA one with
                 --conv-mode fp32) measured live with HIP events on the runtime's own stream over the timed region
+                (the untimed survey pass that picks it stays in a plain run: it decides which launches the timed steps bracket)
+--full adds the legs after the timed region (each can still be turned off by its own option):
+  latency_ms, roofline.matrix_pipe_sustained  (N=1) one un-pipelined image; the matrix-pipe calibration
+  overlapped_pipeline  (N=1) consecutive images' convolutions overlapped on two lane sets (never `value`)
   cpu_baseline  the numpy/OpenBLAS oracle (Caffe's im2col+SGEMM algorithm) timed on the
                 host cores on the five levels of one image (flips counted twice) + bbox_vote
   reduced_precision  (N=1) a short second run in bf16 / f16 after the timed region: value + measured drift
@@ -23,6 +28,7 @@ Rank 0 prints ONE JSON line (contract in the task description) with two extra ob
   mixed_shapes  (N=1) 32 uint8 images of 8 WIDER-like shapes through upload + device pyramid + re-plan + two images in flight
                 (test.inference_worker's loop), with the runtime's allocation counts after the first pass
   from_files    (N=1) the same shapes as JPEG FILES: decode (reader threads) -> the loop above -> WIDER detection files
+  net_forward_path  (N=1) lib/test.py's detect() with ten Net.forward() calls and host blobs
 HIP events: an untimed survey pass brackets every launch (per-class table); the timed region brackets only the dominant
 kernel's launches (an event pair costs the stream a few microseconds; --events-all restores full bracketing).
 --force-dist runs the N>1 schedule on a ONE-rank process group (with --backend nccl: a 1-rank RCCL communicator).
@@ -237,6 +243,10 @@ def main():
     # a step is ~14 ms: 50 timed steps keep the pipeline fill / drain of the two-image software pipeline below 1 %
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run the measurement legs too (N=1: sustained, overlapped_pipeline, latency, "
+                         "matrix-pipe calibration, mixed_shapes / from_files, reduced_precision, net_forward_path; "
+                         "cpu_baseline): about half a minute more; the --no-* / --*-seconds options below turn single legs off")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-events", action="store_true", help="do not record per-launch HIP events")
     ap.add_argument("--events-all", action="store_true", help="bracket EVERY launch inside the timed region (default: only the "
@@ -502,12 +512,13 @@ def main():
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
 
+    # ==== measurement legs after the timed region: --full only (a plain run goes straight to the JSON line) ====
     # ---- sustained rate (N=1, headline mode): back-to-back steps for several seconds right after the timed region --
     #      the timed region itself is a quarter of a second on a chip that is power-limited and drifts; `value` stays
     #      what --steps defines.  HIP events are off here (they bracket every launch of the timed region).
     sustained = None
     hwmon = None
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         # the card's hwmon files (sclk, socket power), found through the runtime's PCI bus id: sampled from the host side
         # under `sustained` and under the matrix-pipe calibration (smallhardface_amd/telemetry.py); no GPU call
         from smallhardface_amd import _lib, telemetry
@@ -515,7 +526,7 @@ def main():
         buf = C_.create_string_buffer(64)
         if _lib.load().shf_device_pci_bus_id(buf, 64) == 0:
             hwmon = telemetry.find_card(buf.value.decode())
-    if not dist_path and args.mode == "group" and args.sustain_seconds > 0 and not args.host_input:
+    if args.full and not dist_path and args.mode == "group" and args.sustain_seconds > 0 and not args.host_input:
         from smallhardface_amd import telemetry
         marks = []
         with telemetry.Sampler(hwmon) as tel:
@@ -540,7 +551,7 @@ def main():
     #      kernels on two lane sets and two streams (FusedDetector lane_sets=2) fill each other's partial last rounds; every
     #      kernel's duration then contains its neighbour's blocks, which is why the shipped pipeline does not do it
     overlapped = None
-    if (not dist_path and args.mode == "group" and args.overlap_seconds > 0 and not args.host_input and
+    if (args.full and not dist_path and args.mode == "group" and args.overlap_seconds > 0 and not args.host_input and
             args.conv_mode == "f16x3"):
         from smallhardface_amd.test import FusedDetector as _FD
         fdo = _FD(net, n_lanes=n_units, mode="group", lane_sets=2)
@@ -576,7 +587,7 @@ def main():
 
     # ---- single-image latency: ONE image, nothing else in flight, submit -> merged detections on the host
     latency_ms = None
-    if not dist_path and args.mode == "group" and not args.no_latency and not args.host_input:
+    if args.full and not dist_path and args.mode == "group" and not args.no_latency and not args.host_input:
         lat = []
         for _ in range(7):
             torch.cuda.synchronize()
@@ -589,7 +600,7 @@ def main():
     # random operands (the chip is power-limited under matrix load and the limit depends on operand toggling), measured
     # right after the timed region while the chip is warm; reported beside the nominal peak, never instead of it
     pipe = None
-    if world == 1 and rank == 0 and not args.no_calib and args.conv_mode != "fp32":
+    if args.full and world == 1 and rank == 0 and not args.no_calib and args.conv_mode != "fp32":
         import ctypes as C
         from smallhardface_amd import _lib
         L = _lib.load()
@@ -617,7 +628,7 @@ def main():
     #      upload, pyramid on the device, re-plan per shape, two images in flight.  Pass 1 lets every grow-only buffer
     #      reach its largest shape; pass 2 is timed and must not allocate.
     mixed = None
-    if not dist_path and args.mode == "group" and not args.no_mixed and not args.host_input and rank == 0:
+    if args.full and not dist_path and args.mode == "group" and not args.no_mixed and not args.host_input and rank == 0:
         from smallhardface_amd.test import DevicePyramid
         from smallhardface_amd.test_utils import pyramid_scales
         shapes = [(768, 1024), (683, 1024), (1024, 732), (1365, 1024), (576, 1024), (1024, 819), (1536, 1024), (1024, 1024)]
@@ -733,7 +744,8 @@ def main():
     #      and outside the timed region -- throughput of the same image pipeline in the mode, its score drift against the
     #      exact fp32 mode on one mid-size level (every anchor), and how many of the fp32 mode's boxes it reproduces
     reduced = None
-    if not dist_path and args.mode == "group" and args.conv_mode == "f16x3" and not args.no_reduced and not args.host_input:
+    if (args.full and not dist_path and args.mode == "group" and args.conv_mode == "f16x3" and not args.no_reduced and
+            not args.host_input):
         def level_scores():
             d, H_, W_, im_h, im_w, sc_, _ = units[(0, 4 if n_units > 4 else 0)]
             net.blobs['data'].reshape(1, 3, H_, W_)
@@ -787,7 +799,7 @@ def main():
     #      in and out (lib/test.py:21-106), the > 0.05 cut on the host, bbox_vote through the C ABI.  After and outside the
     #      timed region; every other leg times the device-resident loop (test.fused_image_loop / FusedDetector).
     nf_path = None
-    if not dist_path and args.mode == "group" and not args.no_forward_path and not args.host_input and rank == 0:
+    if args.full and not dist_path and args.mode == "group" and not args.no_forward_path and not args.host_input and rank == 0:
         from smallhardface_amd import test as T
         from smallhardface_amd.test_utils import _get_image_blob, _get_image_blob_device, pyramid_scales
         im0 = np.random.default_rng(1000).integers(0, 256, (src_hw[0], src_hw[1], 3)).astype(np.uint8)   # = build_units(0)
@@ -965,7 +977,7 @@ def main():
             out["reduced_precision"] = reduced
         if nf_path is not None:
             out["net_forward_path"] = nf_path
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(msg, params)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -401,6 +401,36 @@ def test_rccl_one_rank_group_runs_the_collective_path(tmp_path):
     np.testing.assert_array_equal(d1, dt)
 
 
+@pytest.mark.timeout(900)
+def test_plain_bench_run_has_no_legs_and_full_runs_them(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` as it stands prints the headline line with the roofline of its timed steps
+    and runs none of the measurement legs after them; `--full` runs them (here the short GPU ones: latency and a brief
+    sustained leg) behind the same timed steps, which return the same detections."""
+    legs = ("sustained", "overlapped_pipeline", "latency_ms", "mixed_shapes", "from_files", "reduced_precision",
+            "net_forward_path", "cpu_baseline")
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+
+    def run(extra, tag):
+        outs = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
+                            "--dump-outputs", str(outs)] + extra, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (tag, r.stdout[-1500:], r.stderr[-3000:])
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        return line, np.load(outs / "detections_image0.npy")
+
+    plain, d_plain = run([], "plain")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in plain, k
+    assert [k for k in legs if k in plain] == [] and "matrix_pipe_sustained" not in plain["roofline"]
+    full, d_full = run(["--full", "--sustain-seconds", "0.5", "--overlap-seconds", "0", "--no-calib", "--no-mixed",
+                        "--no-reduced", "--no-forward-path", "--no-cpu-baseline"], "full")
+    assert full["latency_ms"] > 0 and full["sustained"]["steps"] > 0
+    assert full["metric"] == plain["metric"] and full["dtype"] == plain["dtype"]
+    np.testing.assert_array_equal(d_plain, d_full)
+
+
 # ------------------------------------------------------------------------------------------------------------
 # the other datasets' test pyramids (configs/smallhardface-{afw,fddb,pascal}.toml, SURVEY.md 8f-4)
 # ------------------------------------------------------------------------------------------------------------
