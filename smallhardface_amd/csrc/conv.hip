@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_f32_kernel(ConvK p) {
       areg[j] = (a_goff[j] >= 0) ? *(const float4*)(inc_ + a_goff[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
   {
-    const float* wn_ = wbase + (size_t)((p.relu & 2) ? 0 : (0)) * wstep + (size_t)brow * KC + bq * 4;
+    const float* wn_ = wbase + (size_t)(0) * wstep + (size_t)brow * KC + bq * 4;
     bq0 = *(const float4*)(wn_);
     bq1 = *(const float4*)(wn_ + 32 * KC);
     if constexpr (BLD == 4) {
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_f32_kernel(ConvK p) {
     }
   }
   if (S > 1) {
-    const float* wn_ = wbase + (size_t)((p.relu & 2) ? 0 : (1)) * wstep + (size_t)brow * KC + bq * 4;
+    const float* wn_ = wbase + (size_t)(1) * wstep + (size_t)brow * KC + bq * 4;
     bq0 = *(const float4*)(wn_);
     bq1 = *(const float4*)(wn_ + 32 * KC);
     if constexpr (BLD == 4) {
@@ -166,8 +166,8 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_f32_kernel(ConvK p) {
       *(float4*)(Bn_ + 96 * LDK) = bq3;
     }
   }
-    if (s + 2 < S && !(p.relu & 4)) {
-    const float* wn_ = wbase + (size_t)((p.relu & 2) ? 0 : (s + 2)) * wstep + (size_t)brow * KC + bq * 4;
+    if (s + 2 < S) {
+    const float* wn_ = wbase + (size_t)(s + 2) * wstep + (size_t)brow * KC + bq * 4;
     bq0 = *(const float4*)(wn_);
     bq1 = *(const float4*)(wn_ + 32 * KC);
     if constexpr (BLD == 4) {
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_f32_kernel(ConvK p) {
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm) {
       const f32x16 a = acc[tm][tn];
-      conv_store_tile([&](int r) { return a[r]; }, bv, p.relu, ty0 + wm * 4 + tm * 2, tx0, kh, H, W, b, cout, gout,
+      conv_store_tile([&](int r) { return a[r]; }, bv, p.flags, ty0 + wm * 4 + tm * 2, tx0, kh, H, W, b, cout, gout,
                       p.out_stride, mem.pool, p.pool_stride, track ? &amax : nullptr);
     }
   }
@@ -383,114 +383,135 @@ static size_t mfma_lds_bytes(int k, int dil, int BN, int TH, int TW) {
   return ((size_t)(TH + 2 * pad) * (TW + 2 * pad) * LDK + 2 * (size_t)BN * LDK) * sizeof(float);
 }
 
-template <int KS, int DIL, int BN, int TH, int TW>
-static int launch_mfma_t(const ConvArgs* as, int n, hipStream_t s) {
+// Every instantiation of conv_mfma_f32_kernel, in the order of its profiler classes (PC_CONV_MFMA + index): 3x3 at dilation
+// 1, 2, 4, then 1x1, each as BN 128 (8-row tiles) and BN 64 (16-row tiles)
+#define SHF_F32(I, KS, DIL, BN, TH) {(const void*)conv_mfma_f32_kernel<KS, DIL, BN, TH, 16>, PC_CONV_MFMA + I}
+static const ConvKernel kF32Kernels[8] = {SHF_F32(0, 3, 1, 128, 8), SHF_F32(1, 3, 2, 128, 8), SHF_F32(2, 3, 4, 128, 8),
+                                          SHF_F32(3, 3, 1, 64, 16), SHF_F32(4, 3, 2, 64, 16), SHF_F32(5, 3, 4, 64, 16),
+                                          SHF_F32(6, 1, 0, 128, 8), SHF_F32(7, 1, 0, 64, 16)};
+#undef SHF_F32
+
+#ifdef SHF_CONV_TIMING
+static void f32_timing_report(const ConvPlan& pl, hipStream_t s) {
+  unsigned long long h[40];
+  hipStreamSynchronize(s);
+  hipMemcpy(h, pl.k.dbg, sizeof(h), hipMemcpyDeviceToHost);
+  for (int w = 0; w < 8; ++w)
+    if (h[w * 5 + 4])
+      fprintf(stderr, "[conv timing] blk%d wave%d steps %llu: per-step cycles barrier %.0f issue %.0f compute %.0f tail %.0f\n",
+              w / 4 ? 300 : 0, w % 4, h[w * 5 + 4], (double)h[w * 5] / h[w * 5 + 4], (double)h[w * 5 + 1] / h[w * 5 + 4],
+              (double)h[w * 5 + 2] / h[w * 5 + 4], (double)h[w * 5 + 3] / h[w * 5 + 4]);
+}
+#endif
+
+// fp32 mode: BN 128 where Cout allows, else 64 (16-row tiles)
+static ConvPlan plan_conv_f32(const ConvArgs* as, int n) {
+  ConvPlan pl;
   const ConvArgs& a = as[0];
-  ConvK p = {};
-  p.wp = a.wpacked;
+  const bool bn128 = a.out.C % 128 == 0;
+  const int BN = bn128 ? 128 : 64, TH = bn128 ? 8 : 16, TW = 16;
+  const long long tiles = conv_fill(pl, as, n, a.out.C / BN, TH, TW);
+  if (tiles < 0) return pl;
+  if (a.k != 1 && a.dil != 1 && a.dil != 2 && a.dil != 4) {
+    pl.err = "conv: the MFMA kernel is instantiated for dilation 1, 2 and 4";
+    return pl;
+  }
+  pl.k.wp = a.wpacked;
+  const ConvKernel& kern = kF32Kernels[a.k == 1 ? 6 + !bn128 : 3 * !bn128 + a.dil / 2];
+#ifdef SHF_CONV_TIMING
+  static unsigned long long* dbg_dev = nullptr;
+  if (!dbg_dev) hipMalloc((void**)&dbg_dev, 8 * 5 * 8);
+  hipMemset(dbg_dev, 0, 8 * 5 * 8);
+  pl.k.dbg = dbg_dev;
+  pl.timing_report = f32_timing_report;
+#endif
+  pl.l[pl.nl++] = {&kern, dim3((unsigned)(tiles * pl.k.nct)), dim3(256), mfma_lds_bytes(a.k, a.dil, BN, TH, TW), 0, 0, 1.0};
+  return pl;
+}
+
+long long conv_fill(ConvPlan& pl, const ConvArgs* as, int n, int nct, int th, int tw) {
+  if (n < 1 || n > MAX_GROUP) { pl.err = "conv group: 1..16 members"; return -1; }
+  const ConvArgs& a = as[0];
+  ConvK& p = pl.k;
   p.bias = a.bias;
+  p.wscale_inv = 1.f;
   p.Cin = a.in.C; p.Cout = a.out.C;
   p.in_stride = a.in.cstride; p.out_stride = a.out.cstride;
-  p.dil = a.dil; p.relu = a.relu | (a.pool.p && !a.write_main ? 8 : 0);
+  p.dil = a.dil;
+  p.flags = (a.relu ? CONV_RELU : 0) | (a.pool.p && !a.write_main ? CONV_NO_MAIN : 0);
   p.pool_stride = a.pool.p ? a.pool.cstride : 0;
-  p.nct = p.Cout / BN;
+  p.nct = nct;
   p.nmem = n;
-  for (int i = 0; i < MAX_GROUP; ++i) p.tile_starts[i] = 0x7fffffff;
-  p.w1t = nullptr;
-  p.w1f = nullptr;
-  p.b1 = nullptr;
   p.range_flag = a.range_flag;
-  p.wph = nullptr;
-  p.wscale_inv = 1.f;
-  p.tile_base = 0;
-  p.ntile_blocks = 0;
-  p.pc_tab = 0;
+  for (int i = 0; i < MAX_GROUP; ++i) p.tile_starts[i] = 0x7fffffff;
   long long tiles = 0;
   for (int i = 0; i < n; ++i) {
     const ConvArgs& q = as[i];
-    if (q.in.C != p.Cin || q.out.C != p.Cout || q.in.cstride != p.in_stride || q.out.cstride != p.out_stride ||
-        q.dil != p.dil || q.wpacked != p.wp) {
-      set_error("conv group: members must share the layer");
+    if ((q.in.cstride % 4) || (q.in.coff % 4)) { pl.err = "conv: input view not 16-byte aligned"; return -1; }
+    if (q.in.C != p.Cin || q.out.C != p.Cout || q.in.cstride != p.in_stride || q.out.cstride != p.out_stride || q.k != a.k ||
+        q.dil != a.dil || q.wpacked != a.wpacked || q.wsplit16 != a.wsplit16 || q.wsplit16h != a.wsplit16h || !q.img != !a.img ||
+        q.in_split != a.in_split || q.out_split != a.out_split || q.pool_split != a.pool_split) {
+      pl.err = "conv group: members must share the layer";
       return -1;
     }
     ConvMember& m = p.m[i];
     m.in = q.in.p + q.in.coff;
     m.out = q.out.p + q.out.coff;
     m.pool = q.pool.p ? q.pool.p + q.pool.coff : nullptr;
-    m.img = nullptr;
+    m.img = q.img;
     m.in_amax = q.in_amax; m.out_amax = q.out_amax; m.pool_amax = q.pool.p ? q.pool_amax : nullptr;
     m.B = q.in.B; m.H = q.in.H; m.W = q.in.W;
-    m.tiles_x = (m.W + TW - 1) / TW;
-    m.tiles_per_img = m.tiles_x * ((m.H + TH - 1) / TH);
-    m.inv_tiles_x = conv_inv32(m.tiles_x);
-    m.inv_tiles_per_img = conv_inv32(m.tiles_per_img);
     m.tile_start = (int)tiles;
     p.tile_starts[i] = (int)tiles;
+    if (th == 0) {   // flat tiles over the member's pixel list
+      const long long npix = (long long)m.B * m.H * m.W;
+      if (npix >= (1ll << 31)) { pl.err = "conv: 2^31 pixels or more in one member"; return -1; }
+      m.tiles_x = 1;
+      m.tiles_per_img = (int)((npix + tw - 1) / tw);
+      tiles += m.tiles_per_img;
+      continue;
+    }
+    m.tiles_x = (m.W + tw - 1) / tw;
+    m.tiles_per_img = m.tiles_x * ((m.H + th - 1) / th);
+    m.inv_tiles_x = conv_inv32(m.tiles_x);
+    m.inv_tiles_per_img = conv_inv32(m.tiles_per_img);
     tiles += (long long)m.tiles_per_img * m.B;
     // conv_split_tile's multiply-high quotients are exact while tile index x divisor < 2^32
     if ((unsigned long long)m.tiles_per_img * m.B * (unsigned long long)m.tiles_per_img >= (1ull << 32)) {
-      set_error("conv: more than 2^32 / tiles-per-image pixel tiles in one member (shrink the batch or the map)");
+      pl.err = "conv: more than 2^32 / tiles-per-image pixel tiles in one member (shrink the batch or the map)";
       return -1;
     }
   }
-  if (tiles * p.nct >= (1ll << 31)) { set_error("conv: grid too large"); return -1; }
-  p.dbg = nullptr;
-#ifdef SHF_CONV_TIMING
-  static unsigned long long* dbg_dev = nullptr;
-  if (!dbg_dev) hipMalloc((void**)&dbg_dev, 8 * 5 * 8);
-  hipMemset(dbg_dev, 0, 8 * 5 * 8);
-  p.dbg = dbg_dev;
-#endif
-  size_t lds = mfma_lds_bytes(KS, DIL, BN, TH, TW);
-  const long long blocks = tiles * p.nct;
-  hipLaunchKernelGGL((conv_mfma_f32_kernel<KS, DIL, BN, TH, TW>), dim3((unsigned)blocks), dim3(256), lds, s, p);
-  SHF_HIP_OK(hipGetLastError());
-#ifdef SHF_CONV_TIMING
-  {
-    unsigned long long h[40];
-    hipStreamSynchronize(s);
-    hipMemcpy(h, dbg_dev, sizeof(h), hipMemcpyDeviceToHost);
-    for (int w = 0; w < 8; ++w)
-      if (h[w * 5 + 4])
-        fprintf(stderr, "[conv timing] blk%d wave%d steps %llu: per-step cycles barrier %.0f issue %.0f compute %.0f tail %.0f\n",
-                w / 4 ? 300 : 0, w % 4, h[w * 5 + 4], (double)h[w * 5] / h[w * 5 + 4], (double)h[w * 5 + 1] / h[w * 5 + 4],
-                (double)h[w * 5 + 2] / h[w * 5 + 4], (double)h[w * 5 + 3] / h[w * 5 + 4]);
-  }
-#endif
-  return 0;
+  if (tiles * nct >= (1ll << 31)) { pl.err = "conv: grid too large"; return -1; }
+  return tiles;
 }
 
-template <int KS, int DIL, int BN, int TH, int TW>
-static int set_attr_t() {
-  SHF_HIP_OK(hipFuncSetAttribute((const void*)conv_mfma_f32_kernel<KS, DIL, BN, TH, TW>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+int conv_set_lds_attributes(const ConvKernel* t, int n) {
+  for (int i = 0; i < n; ++i)
+    SHF_HIP_OK(hipFuncSetAttribute(t[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   return 0;
 }
 
 int conv_init_attributes() {
-  if (set_attr_t<3, 1, 128, 8, 16>() || set_attr_t<3, 2, 128, 8, 16>() || set_attr_t<3, 4, 128, 8, 16>() ||
-      set_attr_t<3, 1, 64, 16, 16>() || set_attr_t<3, 2, 64, 16, 16>() || set_attr_t<3, 4, 64, 16, 16>() ||
-      set_attr_t<1, 0, 128, 8, 16>() || set_attr_t<1, 0, 64, 16, 16>())
-    return -1;
+  if (conv_set_lds_attributes(kF32Kernels, 8)) return -1;
+  return conv_f16x3_init_attributes();
+}
+
+ConvPlan plan_conv(const ConvArgs* as, int n) {
+  return (n >= 1 && as[0].wsplit16) ? plan_conv_f16x3(as, n) : plan_conv_f32(as, n);
+}
+
+int launch_conv_plan(const ConvPlan& pl, int i, hipStream_t s) {
+  const ConvLaunch& L = pl.l[i];
+  ConvK k = pl.k;
+  k.tile_base = L.tile_base;
+  k.ntile_blocks = L.ntile_blocks;
+  void* args[] = {&k};
+  (void)hipLaunchKernel(L.kern->fn, L.grid, L.block, args, L.lds, s);
+  SHF_HIP_OK(hipGetLastError());
+  if (pl.timing_report && i == pl.nl - 1) pl.timing_report(pl, s);
   return 0;
 }
-
-int launch_conv_mfma_group(const ConvArgs* as, int n, hipStream_t s) {
-  if (n < 1 || n > MAX_GROUP) { set_error("conv group: 1..16 members"); return -1; }
-  for (int i = 0; i < n; ++i)
-    if ((as[i].in.cstride % 4) || (as[i].in.coff % 4)) { set_error("conv: input view not 16-byte aligned"); return -1; }
-  const ConvArgs& a = as[0];
-  const bool bn128 = (a.out.C % 128 == 0);
-  if (a.k == 1) return bn128 ? launch_mfma_t<1, 0, 128, 8, 16>(as, n, s) : launch_mfma_t<1, 0, 64, 16, 16>(as, n, s);
-  switch (a.dil) {
-    case 1: return bn128 ? launch_mfma_t<3, 1, 128, 8, 16>(as, n, s) : launch_mfma_t<3, 1, 64, 16, 16>(as, n, s);
-    case 2: return bn128 ? launch_mfma_t<3, 2, 128, 8, 16>(as, n, s) : launch_mfma_t<3, 2, 64, 16, 16>(as, n, s);
-    case 4: return bn128 ? launch_mfma_t<3, 4, 128, 8, 16>(as, n, s) : launch_mfma_t<3, 4, 64, 16, 16>(as, n, s);
-    default: set_error("conv: the MFMA kernel is instantiated for dilation 1, 2 and 4"); return -1;
-  }
-}
-
-int launch_conv_mfma(const ConvArgs& a, hipStream_t s) { return launch_conv_mfma_group(&a, 1, s); }
 
 int launch_conv_first(const float* in_nchw, const ConvArgs& a, hipStream_t s) {
   const int Cin = a.in.C, Cout = a.out.C;

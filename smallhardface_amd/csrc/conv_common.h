@@ -32,6 +32,13 @@ struct ConvMember {
   unsigned* out3_amax;
 };
 
+// ConvK::flags
+constexpr int CONV_RELU = 1;         // ReLU in the epilogue
+constexpr int CONV_NO_MAIN = 8;      // do not write the un-pooled output (its only reader is the fused pool)
+constexpr int CONV_VEC_EPI = 16;     // 16-byte aligned views: LDS-transposed float4 epilogue
+constexpr int CONV_MAIN_SPLIT = 32;  // write the main output in the split-fp16 activation format (ConvArgs::out_split)
+constexpr int CONV_POOL_SPLIT = 64;  // ... the pooled output (ConvArgs::pool_split)
+
 struct ConvK {
   const float* wp;   // packed weights
   const void* wph;   // dual-tile 4-wave kernel: its own split-fp16 pack (16-channel chunks, unscaled low parts)
@@ -39,9 +46,7 @@ struct ConvK {
   const float* bias;
   int Cin, Cout;
   int in_stride, out_stride;
-  int dil, relu;     // relu bit 0: ReLU; bit 3 (8): do NOT write the un-pooled output; bit 4 (16): views are
-                     // 16-byte aligned -> LDS-transposed float4 epilogue; bit 5 (32) / bit 6 (64): write the
-                     // main / the pooled output in the split-fp16 activation format (ConvArgs::out_split)
+  int dil, flags;    // CONV_* bits below
   int pool_stride;   // floats per pixel of the pool buffer
   int nct, nmem;
   int ntile_blocks;  // persistent / dual-tile kernels: (pixel tiles of the group this launch ends at) x cout tiles
@@ -91,11 +96,11 @@ __device__ __forceinline__ void row_to_pixel(int i, int& dy, int& px) {
 // the (dy,dx) = (s>>1, s&1) corners of ONE pooling window, so the pool is a max over four registers
 // of the same lane -- no cross-lane traffic.  Windows on a ragged edge are clipped like Caffe's.
 template <typename GetV>
-__device__ __forceinline__ void conv_store_tile(GetV getv, float bv, int relu_flags, int gy0, int gx0, int kh,
+__device__ __forceinline__ void conv_store_tile(GetV getv, float bv, int flags, int gy0, int gx0, int kh,
                                                 int H, int W, int b, int cout, float* __restrict__ gout,
                                                 int out_stride, float* __restrict__ gpool, int pool_stride,
                                                 float* amax = nullptr) {
-  const bool write_main = !(relu_flags & 8);
+  const bool write_main = !(flags & CONV_NO_MAIN);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int gx = gx0 + 2 * (2 * q + kh);
@@ -104,7 +109,7 @@ __device__ __forceinline__ void conv_store_tile(GetV getv, float bv, int relu_fl
     for (int s = 0; s < 4; ++s) {
       const int y = gy0 + (s >> 1), x = gx + (s & 1);
       float v = getv(4 * q + s) + bv;
-      if (relu_flags & 1) v = fmaxf(v, 0.f);
+      if (flags & CONV_RELU) v = fmaxf(v, 0.f);
       if (y < H && x < W) {
         // (only what is stored counts: the unit's max must not depend on how the launch tiles the map)
         if (amax) *amax = fmaxf(*amax, v != v ? __builtin_inff() : fabsf(v));
@@ -130,7 +135,7 @@ constexpr int CS_PAD = 16;  // 2 x (BN + CS_PAD) words = 32 (mod 64 banks): the 
 
 // stage the 2x16-pixel x 32-cout MFMA tile of one lane: local rows ly0, ly0+1; `cl` = local cout
 template <int BN, typename GetV>
-__device__ __forceinline__ void conv_stage_tile(float* __restrict__ Cs, GetV getv, float bv, int relu_flags, int ly0,
+__device__ __forceinline__ void conv_stage_tile(float* __restrict__ Cs, GetV getv, float bv, int flags, int ly0,
                                                 int kh, int cl) {
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -138,7 +143,7 @@ __device__ __forceinline__ void conv_stage_tile(float* __restrict__ Cs, GetV get
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       float v = getv(4 * q + s) + bv;
-      if (relu_flags & 1) v = fmaxf(v, 0.f);
+      if (flags & CONV_RELU) v = fmaxf(v, 0.f);
       Cs[((ly0 + (s >> 1)) * 16 + lx + (s & 1)) * (BN + CS_PAD) + cl] = v;
     }
   }
@@ -720,5 +725,41 @@ __device__ __forceinline__ void conv_epilogue_regs1(const cs_f32x16 acc, float s
   }
   conv_epilogue_regs_tail<RELU>(v, bias16, valid, interior, pix_main, cout16, main_split, pix_pool, pool_writer, pool_split, amax);
 }
+
+// ---- launch plans: which kernel runs a convolution, decided once (plan_conv, conv.hip / conv_f16x3.hip) and launched by
+//      run_conv_plan (net_forward.cpp), which books every launch under its kernel's profiler class
+struct ConvKernel {   // one compiled instantiation: an entry of the kernel tables in conv.hip / conv_f16x3.hip
+  const void* fn;
+  int prof;           // ProfClass its launches are booked under
+};
+struct ConvLaunch {
+  const ConvKernel* kern;
+  dim3 grid, block;
+  size_t lds;
+  int tile_base, ntile_blocks;  // -> ConvK::tile_base / ntile_blocks
+  double share;                 // its fraction of the layer's flops / bytes
+};
+struct ConvPlan {
+  ConvK k{};
+  int nl = 0;                   // launches (the dual-tile family may cover a layer with two)
+  ConvLaunch l[2];
+  std::string err;              // a failed plan: why (nl == 0)
+  void (*timing_report)(const ConvPlan&, hipStream_t) = nullptr;   // SHF_CONV_TIMING builds: after the last launch
+  int rows = 0;                                                    // ... the dual-tile family's tile rows
+};
+// grouped launch over 1..16 members that share the layer; the mode follows the arguments (wsplit16: split-fp16, else fp32)
+ConvPlan plan_conv(const ConvArgs* as, int n);
+// the three shared-weight dilated heads (dilation 1 / 2 / 4) as one launch; nl == 0 with no error: the triple does not
+// qualify and the heads run one by one
+ConvPlan plan_conv_heads3(const ConvArgs* a1, const ConvArgs* a2, const ConvArgs* a4, int n);
+int launch_conv_plan(const ConvPlan& pl, int i, hipStream_t s);
+// the ConvK header and member table every kernel kind shares, with the group-consistency and size-limit checks: th x tw pixel
+// tiles (th == 0: flat tiles of tw pixels over each member's pixel list), nct cout tiles.  The group's pixel tiles, or -1
+// with pl.err set.
+long long conv_fill(ConvPlan& pl, const ConvArgs* as, int n, int nct, int th, int tw);
+// the kernel tables' LDS opt-in (160 KiB)
+int conv_set_lds_attributes(const ConvKernel* t, int n);
+ConvPlan plan_conv_f16x3(const ConvArgs* as, int n);   // (conv_f16x3.hip: the split-fp16 modes)
+int conv_f16x3_init_attributes();
 
 }  // namespace shf

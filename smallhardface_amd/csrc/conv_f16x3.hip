@@ -13,7 +13,7 @@
 // epilogue (ConvArgs::in_split / out_split) -- and weights are split once at load time.  Every MFMA convolution
 // of the detector runs here in the split-fp16 modes: 3x3 at dilation 1, 2, 4 and the 1x1s.
 //
-// Kernels, one header each (this file is the host side: weight packs, knobs, launchers):
+// Kernels, one header each (this file is the host side: weight packs, knobs, the kernel table and the planner):
 //   conv_f16x3_w4d.h   conv_mfma_f16x3_w4d_kernel -- the dual-tile 4-wave family: Cin >= 64, Cout % 128 == 0 (80 % of the time)
 //   conv_f16x3_pc.h    conv_mfma_f16x3_pc_kernel  -- the fused first pair conv1_1 -> conv1_2, producer / consumer waves
 //   conv_f16x3_k1.h    conv_mfma_f16x3_k1_kernel  -- the 1x1 layers with Cout % 256 == 0 as a plain GEMM over flat pixels
@@ -138,24 +138,10 @@ float pack_conv_weights_split16h(const float* w, int Cout, int Cin, int k, void*
 }
 
 
-// Environment knobs (experiments; the defaults are the measured best), read ONCE: none of them is consulted per launch.
-namespace {
-struct Knobs {
-  int w4_mode;         // SHF_F16X3_W4: -1 auto (Cin >= 64), 0 never, 1 always -- which layers take the 4-wave dual-tile family
-  int w4_mt;           // SHF_F16X3_W4_MT: 0 auto, 2 / 4 force 8- / 16-row tiles
-  int w4d_ntile;       // SHF_F16X3_W4D_NTILE: 0 auto (hybrid launches), 1 / 2 force single- / two-tile blocks
-  int pc_tab;          // SHF_F16X3_PC_TAB: 0 = the persistent first pair decodes its tiles one by one (the path launches with more than
-                       // 300 tiles per block take anyway); bit-identical
-  int heads3;          // SHF_F16X3_HEADS3: 1 (default) = the three shared-weight dilated heads as ONE launch (conv_f16x3_h3.h), 0 = one
-                       // launch per head; bit-identical
-  bool pc;             // SHF_F16X3_PC (default on): the fused first pair on the producer / consumer kernel
-  bool pc_persist;     // SHF_F16X3_PC_PERSIST (default on): the fused first pair as one block per CU walking the tiles
-  int cus;
-};
-int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
-const Knobs& knobs() {
-  static const Knobs k = [] {
-    Knobs q;
+const ConvKnobs& conv_knobs() {
+  static const ConvKnobs k = [] {
+    auto env_int = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+    ConvKnobs q;
     q.w4_mode = env_int("SHF_F16X3_W4", -1);
     q.w4_mt = env_int("SHF_F16X3_W4_MT", 0);
     q.w4d_ntile = env_int("SHF_F16X3_W4D_NTILE", 0);
@@ -163,6 +149,7 @@ const Knobs& knobs() {
     q.pc_tab = env_int("SHF_F16X3_PC_TAB", 1);
     q.pc = env_int("SHF_F16X3_PC", 1) != 0;
     q.pc_persist = env_int("SHF_F16X3_PC_PERSIST", 1) != 0;
+    q.split_act = env_int("SHF_F16X3_SPLIT_ACT", 1) != 0;
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 4)
       cus = 256;
@@ -171,6 +158,8 @@ const Knobs& knobs() {
   }();
   return k;
 }
+
+namespace {
 // 16-byte aligned channel views: what the vector epilogues (LDS-transposed and register) need
 bool views_aligned(const ConvArgs* as, int n) {
   for (int i = 0; i < n; ++i) {
@@ -180,43 +169,15 @@ bool views_aligned(const ConvArgs* as, int n) {
   }
   return true;
 }
+// the dual-tile family addresses its input with 32-bit BYTE offsets from the member's base
+bool inputs_under_4gib(const ConvArgs* as, int n) {
+  for (int i = 0; i < n; ++i)
+    if ((unsigned long long)as[i].in.B * as[i].in.H * as[i].in.W * as[i].in.cstride * 4ull >= (1ull << 32)) return false;
+  return true;
+}
+// (Cin 64 -- conv2_1 -- joined in round 3: as two single-tile 8-row blocks per CU it beats the 8-wave kernel, 0.67 vs 0.81 ms)
+bool uses_w4(int Cin) { return conv_knobs().w4_mode < 0 ? Cin >= 64 : conv_knobs().w4_mode != 0; }
 }  // namespace
-
-// (net_forward.cpp / net_detect.cpp: will launch_conv_f16x3_group(as, n) take the dual-tile family?  Then the sub-launch hook does the profiling.)
-// The family addresses its input with 32-bit BYTE offsets from the member's base: inputs of 4 GiB and more, and
-// unaligned views (scalar epilogue), take the 8-wave kernel.
-bool conv_f16x3_group_is_dual(const ConvArgs* as, int n) {
-  if (!as[0].wsplit16h || as[0].img || as[0].k != 3 || as[0].dil != 1 || as[0].out.C % 128) return false;
-  if (!conv_f16x3_uses_w4(as[0].in.C) || !views_aligned(as, n)) return false;
-  for (int i = 0; i < n; ++i)
-    if ((unsigned long long)as[i].in.B * as[i].in.H * as[i].in.W * as[i].in.cstride * 4ull >= (1ull << 32)) return false;
-  return true;
-}
-
-// the dilated shared-weight heads (dilation 2 / 4) on the family's DIL form: the same conditions but for the dilation
-// (what they exclude -- Cin < 64, Cout % 128, unaligned views -- takes the 8-wave kernel's DIL form)
-bool conv_f16x3_group_is_dilated_w4(const ConvArgs* as, int n) {
-  if (!as[0].wsplit16h || as[0].img || as[0].k != 3 || (as[0].dil != 2 && as[0].dil != 4) || as[0].out.C % 128)
-    return false;
-  if (!conv_f16x3_uses_w4(as[0].in.C) || !views_aligned(as, n)) return false;
-  for (int i = 0; i < n; ++i)
-    if ((unsigned long long)as[i].in.B * as[i].in.H * as[i].in.W * as[i].in.cstride * 4ull >= (1ull << 32)) return false;
-  return true;
-}
-
-// 1x1 layers on the GEMM kernel (conv_f16x3_k1.h): all 256 couts of a pixel in one block, the family's weight pack with
-// k = 1, activations in the split format (net_graph.cpp counts such a layer as a split-format reader) or fp32
-bool conv_f16x3_k1_gemm_shape(int Cin, int Cout) {
-  return conv_f16x3_uses_w4(Cin) && Cin % 32 == 0 && Cout % 256 == 0;
-}
-bool conv_f16x3_group_is_k1_gemm(const ConvArgs* as, int n) {
-  if (!as[0].wsplit16h || as[0].img || as[0].k != 1 || as[0].bf16 || as[0].pool.p || !conv_f16x3_k1_gemm_shape(as[0].in.C, as[0].out.C))
-    return false;
-  if (!views_aligned(as, n)) return false;
-  for (int i = 0; i < n; ++i)
-    if ((unsigned long long)as[i].in.B * as[i].in.H * as[i].in.W * as[i].in.cstride * 4ull >= (1ull << 32)) return false;
-  return true;
-}
 
 void pack_first_conv_frags(const float* w, void* dst_, bool bf) {
   _Float16* dst = (_Float16*)dst_;
@@ -233,16 +194,17 @@ void pack_first_conv_frags(const float* w, void* dst_, bool bf) {
         }
 }
 
-bool conv_f16x3_uses_pc() { return knobs().pc; }
-bool conv_f16x3_pc_persistent() { return knobs().pc_persist; }
-
-// (Cin 64 -- conv2_1 -- joined in round 3: as two single-tile 8-row blocks per CU it beats the 8-wave kernel, 0.67 vs 0.81 ms)
-bool conv_f16x3_uses_w4(int Cin) { return knobs().w4_mode < 0 ? Cin >= 64 : knobs().w4_mode != 0; }
-
 bool conv_f16x3_eligible(int Cin, int Cout, int k, int pad, int dil) {
   const bool dil_ok = dil == 1 || dil == 2 || dil == 4;
   if (k == 1) return pad == 0 && Cin % 32 == 0 && Cout % 64 == 0;
   return k == 3 && dil_ok && pad == dil && Cin % 32 == 0 && Cout % 64 == 0;
+}
+
+// 3x3: Cout % 128 == 0 and the Cin the knob gives the family; 1x1 (the GEMM kernel: all 256 couts of a pixel in one
+// block): Cout % 256 == 0, no fused pool.  What the family writes must be 16-byte aligned (register epilogues).
+bool conv_f16x3_family_shape(int Cin, int Cout, int k, int pad, int dil, bool pool, bool aligned) {
+  if (!aligned || !uses_w4(Cin) || !conv_f16x3_eligible(Cin, Cout, k, pad, dil)) return false;
+  return k == 1 ? !pool && Cout % 256 == 0 : Cout % 128 == 0;
 }
 
 // 4-wave family: 16-row tiles (MT 4) or 8-row tiles (MT 2)?  A launch runs in ceil(blocks / CUs) rounds of one block
@@ -257,9 +219,9 @@ bool conv_f16x3_eligible(int Cin, int Cout, int k, int pad, int dil) {
 static bool w4_short_k(const ConvArgs* as) { return as[0].in.C <= 128; }
 
 static int w4_pick_mt(const ConvArgs* as, int n, int nct) {
-  if (knobs().w4_mt == 2 || knobs().w4_mt == 4) return knobs().w4_mt;
+  if (conv_knobs().w4_mt == 2 || conv_knobs().w4_mt == 4) return conv_knobs().w4_mt;
   if (w4_short_k(as)) return 2;
-  const int cus = knobs().cus;
+  const int cus = conv_knobs().cus;
   long long t4 = 0, t2 = 0;
   for (int i = 0; i < n; ++i) {
     const long long tx = (as[i].in.W + f16x3::TW - 1) / f16x3::TW, B = as[i].in.B;
@@ -270,139 +232,172 @@ static int w4_pick_mt(const ConvArgs* as, int n, int nct) {
   return c2 < c4 ? 2 : 4;
 }
 
-int conv_f16x3_w4_mt(const ConvArgs* as, int n) { return w4_pick_mt(as, n, as[0].out.C / 128); }
+// Every kernel instantiation of the split-fp16 modes, each with the profiler class its launches are booked under.  Columns:
+// NP = 3, 2, 1 fp16 products, then bf16 (one product on bf16 operands); [IN_SPLIT x NP] = the fp32-input forms, the split-input
+// forms, then bf16 (fp32 activations: no split input).
+#define SHF_K(PC, ...) {(const void*)__VA_ARGS__, PC}
+#define SHF_8W(PC, BN, DIL, KS)                                                                                            \
+  {SHF_K(PC, conv_mfma_f16x3_kernel<BN, false, DIL, KS, 3>), SHF_K(PC, conv_mfma_f16x3_kernel<BN, false, DIL, KS, 2>),       \
+   SHF_K(PC, conv_mfma_f16x3_kernel<BN, false, DIL, KS, 1>), SHF_K(PC, conv_mfma_f16x3_kernel<BN, false, DIL, KS, 1, true>)}
+#define SHF_PC(PC, PERSIST)                                                                                                \
+  {SHF_K(PC, conv_mfma_f16x3_pc_kernel<3, false, PERSIST>), SHF_K(PC, conv_mfma_f16x3_pc_kernel<2, false, PERSIST>),         \
+   SHF_K(PC, conv_mfma_f16x3_pc_kernel<1, false, PERSIST>), SHF_K(PC, conv_mfma_f16x3_pc_kernel<1, true, PERSIST>)}
+#define SHF_W4D(PC0, PC1, MT, NT, DIL)                                                                                     \
+  {SHF_K(PC0, conv_mfma_f16x3_w4d_kernel<false, MT, NT, 3, false, DIL>), SHF_K(PC0, conv_mfma_f16x3_w4d_kernel<false, MT, NT, 2, false, DIL>), \
+   SHF_K(PC0, conv_mfma_f16x3_w4d_kernel<false, MT, NT, 1, false, DIL>), SHF_K(PC1, conv_mfma_f16x3_w4d_kernel<true, MT, NT, 3, false, DIL>),  \
+   SHF_K(PC1, conv_mfma_f16x3_w4d_kernel<true, MT, NT, 2, false, DIL>), SHF_K(PC1, conv_mfma_f16x3_w4d_kernel<true, MT, NT, 1, false, DIL>),   \
+   SHF_K(PC0, conv_mfma_f16x3_w4d_kernel<false, MT, NT, 1, true, DIL>)}
+#define SHF_2NP3(PC, K)                                                                                                    \
+  {SHF_K(PC, K<false, 3>), SHF_K(PC, K<false, 2>), SHF_K(PC, K<false, 1>), SHF_K(PC, K<true, 3>), SHF_K(PC, K<true, 2>),     \
+   SHF_K(PC, K<true, 1>)}
+struct F16x3Kernels {
+  ConvKernel w8[2][4][4];    // conv_mfma_f16x3_kernel: [BN 128, 64][DIL 1, 2, 4 (3x3), then 1x1][NP]; the BN 128 dilated rows
+                             // are never selected (those heads take the family's DIL form)
+  ConvKernel w8_fuse1;       // ... conv1_1 computed in the halo staging
+  ConvKernel pc[2][4];       // conv_mfma_f16x3_pc_kernel: [PERSIST][NP]
+  ConvKernel w4d[2][2][7];   // conv_mfma_f16x3_w4d_kernel, DIL 1: [MT 4, 2][NTILE 2, 1][IN_SPLIT x NP]
+  ConvKernel w4d_dil[2][7];  // ... single 16-row tiles at DIL 2, 4: [DIL][IN_SPLIT x NP]
+  ConvKernel k1[6];          // conv_mfma_f16x3_k1_kernel: [IN_SPLIT x NP]
+  ConvKernel h3[6];          // conv_mfma_f16x3_heads3_kernel: [IN_SPLIT x NP]
+};
+#define SHF_W4D_PC(SPLIT, MT, NT) (PC_CONV_F16X3_W4D_0 + 4 * SPLIT + (MT == 2 ? 2 : 0) + (NT == 1 ? 1 : 0))
+static const F16x3Kernels kK = {
+    {{SHF_8W(PC_CONV_F16X3_128, 128, 1, 3), SHF_8W(PC_CONV_F16X3_64_D2, 128, 2, 3), SHF_8W(PC_CONV_F16X3_64_D4, 128, 4, 3),
+      SHF_8W(PC_CONV_F16X3_128_K1, 128, 1, 1)},
+     {SHF_8W(PC_CONV_F16X3_64, 64, 1, 3), SHF_8W(PC_CONV_F16X3_64_D2, 64, 2, 3), SHF_8W(PC_CONV_F16X3_64_D4, 64, 4, 3),
+      SHF_8W(PC_CONV_F16X3_64_K1, 64, 1, 1)}},
+    SHF_K(PC_CONV_F16X3_64_FUSE1, conv_mfma_f16x3_kernel<64, true, 1, 3, 3>),
+    {SHF_PC(PC_CONV_F16X3_PC, false), SHF_PC(PC_CONV_F16X3_PCP, true)},
+    {{SHF_W4D(SHF_W4D_PC(0, 4, 2), SHF_W4D_PC(1, 4, 2), 4, 2, 1), SHF_W4D(SHF_W4D_PC(0, 4, 1), SHF_W4D_PC(1, 4, 1), 4, 1, 1)},
+     {SHF_W4D(SHF_W4D_PC(0, 2, 2), SHF_W4D_PC(1, 2, 2), 2, 2, 1), SHF_W4D(SHF_W4D_PC(0, 2, 1), SHF_W4D_PC(1, 2, 1), 2, 1, 1)}},
+    {SHF_W4D(PC_CONV_F16X3_W4D_D2, PC_CONV_F16X3_W4D_D2, 4, 1, 2), SHF_W4D(PC_CONV_F16X3_W4D_D4, PC_CONV_F16X3_W4D_D4, 4, 1, 4)},
+    SHF_2NP3(PC_CONV_F16X3_K1G, conv_mfma_f16x3_k1_kernel),
+    SHF_2NP3(PC_CONV_F16X3_H3, conv_mfma_f16x3_heads3_kernel)};
+#undef SHF_W4D_PC
+#undef SHF_2NP3
+#undef SHF_W4D
+#undef SHF_PC
+#undef SHF_8W
+#undef SHF_K
+static_assert(sizeof(F16x3Kernels) % sizeof(ConvKernel) == 0, "the attribute set-up walks the table as one array");
 
-template <int BN, bool FUSE1, int DIL = 1, int KS = 3>
-static int launch_f16x3_t(const ConvArgs* as, int n, hipStream_t s) {
-  using namespace f16x3;
-  constexpr int PADH = KS == 3 ? DIL : 0;
-  constexpr int HP = (TH + 2 * PADH) * (TW + 2 * PADH);
-  const ConvArgs& a = as[0];
-  ConvK p = {};
-  p.wp = (const float*)a.wsplit16;
-  p.wph = nullptr;
-  p.wscale_inv = 1.f;
-  p.tile_base = 0;
-  p.ntile_blocks = 0;
-  p.pc_tab = 0;
-  p.bias = a.bias;
-  p.Cin = a.in.C; p.Cout = a.out.C;
-  p.in_stride = a.in.cstride; p.out_stride = a.out.cstride;
-  p.dil = DIL; p.relu = a.relu | (a.pool.p && !a.write_main ? 8 : 0);
-  p.pool_stride = a.pool.p ? a.pool.cstride : 0;
-  p.nct = p.Cout / BN;
-  p.nmem = n;
-  for (int i = 0; i < MAX_GROUP; ++i) p.tile_starts[i] = 0x7fffffff;
-  p.dbg = nullptr;
-  p.range_flag = a.range_flag;
-  p.w1t = a.w1t;
-  p.w1f = a.w1f;
-  p.b1 = a.b1;
-  long long tiles = 0;
-  const bool vec_ok = views_aligned(as, n);   // (unaligned channel views: the 8-wave kernel's scalar stores)
-  // the dual-tile 4-wave family (16- or 8-row tiles, w4_pick_mt) or this template's 8-wave kernel
-  const bool dual = BN == 128 && !FUSE1 && DIL == 1 && KS == 3 && conv_f16x3_group_is_dual(as, n);
-  const int mt = dual ? w4_pick_mt(as, n, p.nct) : 4;
-  const int th = 4 * mt;
-  for (int i = 0; i < n; ++i) {
-    const ConvArgs& q = as[i];
-    if (FUSE1 && !q.img) { set_error("conv f16x3: fused first layer needs the image pointer"); return -1; }
-    if (q.in.C != p.Cin || q.out.C != p.Cout || q.in.cstride != p.in_stride || q.out.cstride != p.out_stride ||
-        q.wsplit16 != a.wsplit16 || q.in_split != a.in_split || q.out_split != a.out_split ||
-        q.pool_split != a.pool_split) {
-      set_error("conv group: members must share the layer");
-      return -1;
-    }
-    ConvMember& m = p.m[i];
-    m.in = q.in.p + q.in.coff;
-    m.out = q.out.p + q.out.coff;
-    m.pool = q.pool.p ? q.pool.p + q.pool.coff : nullptr;
-    m.img = q.img;
-    m.in_amax = q.in_amax; m.out_amax = q.out_amax; m.pool_amax = q.pool.p ? q.pool_amax : nullptr;
-    m.B = q.in.B; m.H = q.in.H; m.W = q.in.W;
-    m.tiles_x = (m.W + TW - 1) / TW;
-    m.tiles_per_img = m.tiles_x * ((m.H + th - 1) / th);
-    m.inv_tiles_x = conv_inv32(m.tiles_x);
-    m.inv_tiles_per_img = conv_inv32(m.tiles_per_img);
-    m.tile_start = (int)tiles;
-    p.tile_starts[i] = (int)tiles;
-    tiles += (long long)m.tiles_per_img * m.B;
-    // conv_split_tile's multiply-high quotients are exact while tile index x divisor < 2^32
-    if ((unsigned long long)m.tiles_per_img * m.B * (unsigned long long)m.tiles_per_img >= (1ull << 32)) {
-      set_error("conv f16x3: more than 2^32 / tiles-per-image pixel tiles in one member (shrink the batch or the map)");
-      return -1;
-    }
-  }
-  if (tiles * p.nct >= (1ll << 31)) { set_error("conv f16x3: grid too large"); return -1; }
-  if (vec_ok) p.relu |= 16;
-  if (a.out_split || a.pool_split) {
-    if (!vec_ok) { set_error("conv f16x3: split-format output needs the aligned epilogue"); return -1; }
-    p.relu |= (a.out_split ? 32 : 0) | (a.pool_split ? 64 : 0);
-  }
-  // (the transposed epilogue needs 256 x (BN + 4) floats: the 1x1 variant's K-loop buffers are smaller than that)
-  const size_t lds = std::max((size_t)HP * ROWB + 2 * KS * (size_t)BN * ROWB, (size_t)256 * (BN + CS_PAD) * sizeof(float)) +
-                     (FUSE1 ? (3 * (TH + 4) * (TW + 4) + 27 * 64 + 64) * sizeof(float) : 0);
+int conv_f16x3_init_attributes() {
+  (void)conv_knobs();
+  return conv_set_lds_attributes((const ConvKernel*)&kK, (int)(sizeof(kK) / sizeof(ConvKernel)));
+}
+
+static int np_col(const ConvArgs& a) { return a.bf16 ? 3 : a.nprod >= 3 ? 0 : a.nprod == 2 ? 1 : 2; }   // [NP]
+static int split_col(const ConvArgs& a) { return a.bf16 ? 6 : 3 * (a.in_split ? 1 : 0) + np_col(a); }  // [IN_SPLIT x NP]
+
 #ifdef SHF_CONV_TIMING
+static unsigned long long* timing_buffer() {
   static unsigned long long* dbg_dev = nullptr;
   if (!dbg_dev) hipMalloc((void**)&dbg_dev, 16 * 5 * 8);
   hipMemset(dbg_dev, 0, 16 * 5 * 8);
-  p.dbg = dbg_dev;
+  return dbg_dev;
+}
+// the family's per-block phase sums (conv_f16x3_w4d.h): wave 0 of every block of the layer's launch(es)
+static void w4d_timing_report(const ConvPlan& pl, hipStream_t s) {
+  unsigned long long h[4];
+  hipStreamSynchronize(s);
+  hipMemcpy(h, pl.k.dbg, sizeof(h), hipMemcpyDeviceToHost);
+  const ConvK& p = pl.k;
+  if (h[3])
+    fprintf(stderr, "[w4d timing] Cin %d Cout %d rows %d: %llu blocks, per block cycles: prologue %.0f, K loop %.0f (%d stages: %.0f each), epilogue %.0f\n",
+            p.Cin, p.Cout, pl.rows, h[3], (double)h[0] / h[3], (double)h[1] / h[3], p.Cin / 16 * 3, (double)h[1] / h[3] / (p.Cin / 16 * 3),
+            (double)h[2] / h[3]);
+}
+static void f16x3_timing_report(const ConvPlan& pl, hipStream_t s) {
+  unsigned long long h[80];
+  hipStreamSynchronize(s);
+  hipMemcpy(h, pl.k.dbg, sizeof(h), hipMemcpyDeviceToHost);
+  for (int w = 0; w < 16; w += 3)
+    if (h[w * 5 + 4])
+      fprintf(stderr, "[f16x3 timing] blk%d wave%d stages %llu: per-stage cycles barrier %.0f issue %.0f compute %.0f tail %.0f\n",
+              w / 8 ? 100 : 0, w % 8, h[w * 5 + 4], (double)h[w * 5] / h[w * 5 + 4], (double)h[w * 5 + 1] / h[w * 5 + 4],
+              (double)h[w * 5 + 2] / h[w * 5 + 4], (double)h[w * 5 + 3] / h[w * 5 + 4]);
+}
 #endif
-  if (FUSE1 && BN == 64 && conv_f16x3_uses_pc() && vec_ok && p.Cin == 64 && p.Cout == 64 && p.w1f && a.wsplit16r) {
+
+// The split-fp16 modes: the fused first pair (producer / consumer kernel, or the 8-wave kernel's FUSE1 form), the dual-tile
+// family (1x1: the GEMM kernel; dilated heads: single 16-row tiles; dilation 1: two-tile / single-tile blocks, 16 or 8 rows),
+// and the 8-wave kernel for what the others cannot take (Cout 64, other 1x1s, unaligned views, inputs of 4 GiB or more).
+ConvPlan plan_conv_f16x3(const ConvArgs* as, int n) {
+  using namespace f16x3;
+  const ConvKnobs& kn = conv_knobs();
+  const ConvArgs& a = as[0];
+  ConvPlan pl;
+  if (a.img && (a.in.C != 64 || !a.w1t)) { pl.err = "conv f16x3: fused first layer needs 64 channels + transposed weights"; return pl; }
+  const bool vec_ok = views_aligned(as, n);   // (unaligned channel views: the 8-wave kernel's scalar stores)
+  const bool family = a.wsplit16h && !a.img && !(a.k == 1 && a.bf16) && inputs_under_4gib(as, n) &&
+                      conv_f16x3_family_shape(a.in.C, a.out.C, a.k, a.pad, a.dil, a.pool.p != nullptr, vec_ok);
+  const bool dual = family && a.k == 3 && a.dil == 1;
+  const int BN = family ? (a.k == 1 ? 256 : 128) : (a.img || a.out.C % 128 || (a.k == 3 && a.dil != 1)) ? 64 : 128;
+  const int nct = a.out.C / BN;
+  const int mt = dual ? w4_pick_mt(as, n, nct) : 4;
+  const long long tiles = conv_fill(pl, as, n, nct, family && a.k == 1 ? 0 : 4 * mt, family && a.k == 1 ? 256 : TW);
+  if (tiles < 0) return pl;
+  ConvK& p = pl.k;
+  p.wp = (const float*)a.wsplit16;
+  if (family) {
+    p.wph = a.wsplit16h;
+    p.wscale_inv = a.wscale_inv;
+  }
+  p.w1t = a.w1t; p.w1f = a.w1f; p.b1 = a.b1;
+  if (a.k == 1) p.dil = 1;
+  if (vec_ok) p.flags |= CONV_VEC_EPI;
+  if (a.out_split || a.pool_split) {
+    if (!vec_ok) { pl.err = "conv f16x3: split-format output needs the aligned epilogue"; return pl; }
+    p.flags |= (a.out_split ? CONV_MAIN_SPLIT : 0) | (a.pool_split ? CONV_POOL_SPLIT : 0);
+  }
+  auto add = [&](const ConvKernel& kern, long long grid, int block, size_t lds, long long tile_base, long long ntile_blocks, double share) {
+    pl.l[pl.nl++] = {&kern, dim3((unsigned)grid), dim3(block), lds, (int)tile_base, (int)ntile_blocks, share};
+  };
+#ifdef SHF_CONV_TIMING
+  if (!(family && a.k == 1)) {
+    p.dbg = timing_buffer();
+    pl.timing_report = dual ? w4d_timing_report : f16x3_timing_report;
+    pl.rows = 4 * mt;
+  }
+#endif
+  if (family && a.k == 1) {   // blocks of 256 pixels of each member's flat pixel list x 256 couts
+    add(kK.k1[split_col(a)], tiles * nct, 256, 3 * 256 * 128 + 2 * 2 * 256 * 64, 0, 0, 1.0);   // (all 160 KiB: three activation
+    return pl;                                                                                  // chunks + two weight chunks)
+  }
+  if (a.img && kn.pc && vec_ok && a.out.C == 64 && a.w1f && a.wsplit16r) {
     p.wp = (const float*)a.wsplit16r;   // its own pack: 128-byte rotated rows (pack_conv_weights_split16r)
     // two halo tiles (both channel chunks of conv1_1's output; rows of 18 pixels x 144 B + 96 B) + the weight double buffer
-    // (128-byte rows) + the image patch
+    // (128-byte rows) + the image patch (+ conv1_1's weight fragments 8 KiB, its 64 biases, the row-tile counter)
     constexpr size_t HPP = (HP + 31) / 32 * 32;
-    // (+ conv1_1's weight fragments 8 KiB, its 64 biases, the row-tile counter)
-    const size_t lds_pc = 2 * (size_t)(TH + 2) * ((TW + 2) * ROWB + 96) + 2 * 3 * (size_t)BN * 128 + (3 * (TH + 4) * (TW + 4) + 8) * sizeof(float) + HPP +
-                          BN * sizeof(float) + 8192 + 64 * sizeof(float) + 16 + 64 + 300 * 4;
-if (lds_pc > 160 * 1024) { set_error("conv f16x3: the fused first pair does not fit the LDS"); return -1; }
-    if (knobs().pc_persist) {
-      // one block per CU walks the tiles (tile = block, block + grid, ...)
-      p.ntile_blocks = (int)tiles;
-      const dim3 gp((unsigned)std::min<long long>(tiles, knobs().cus));
-      {   // the per-block tile table: fits (300 tiles per block) and packs (image < 256, tile row / column < 1024)?
-        bool ok = knobs().pc_tab != 0 && (tiles + gp.x - 1) / gp.x <= 300;
-        for (int i = 0; i < n; ++i)
-          ok = ok && as[i].in.B <= 255 && p.m[i].tiles_x <= 1023 && p.m[i].tiles_per_img / std::max(1, p.m[i].tiles_x) <= 1023;
-        p.pc_tab = ok ? 1 : 0;
-      }
-      if (a.bf16) hipLaunchKernelGGL((conv_mfma_f16x3_pc_kernel<1, true, true>), gp, dim3(512), lds_pc, s, p);
-      else if (a.nprod >= 3) hipLaunchKernelGGL((conv_mfma_f16x3_pc_kernel<3, false, true>), gp, dim3(512), lds_pc, s, p);
-      else if (a.nprod == 2) hipLaunchKernelGGL((conv_mfma_f16x3_pc_kernel<2, false, true>), gp, dim3(512), lds_pc, s, p);
-      else hipLaunchKernelGGL((conv_mfma_f16x3_pc_kernel<1, false, true>), gp, dim3(512), lds_pc, s, p);
-    } else if (a.bf16) hipLaunchKernelGGL((conv_mfma_f16x3_pc_kernel<1, true>), dim3((unsigned)tiles), dim3(512), lds_pc, s, p);
-    else if (a.nprod >= 3) hipLaunchKernelGGL(conv_mfma_f16x3_pc_kernel<3>, dim3((unsigned)tiles), dim3(512), lds_pc, s, p);
-    else if (a.nprod == 2) hipLaunchKernelGGL(conv_mfma_f16x3_pc_kernel<2>, dim3((unsigned)tiles), dim3(512), lds_pc, s, p);
-    else hipLaunchKernelGGL(conv_mfma_f16x3_pc_kernel<1>, dim3((unsigned)tiles), dim3(512), lds_pc, s, p);
-  } else if (BN == 128 && !FUSE1 && KS == 3 && DIL > 1 && conv_f16x3_group_is_dilated_w4(as, n)) {
-    // the dilated heads on the family's DIL form: single 16-row tiles (halo tiles of (16 + 2 DIL)^2 pixels, two buffer sets)
-    if constexpr (BN == 128 && !FUSE1 && KS == 3 && (DIL == 2 || DIL == 4)) {
-      p.wph = a.wsplit16h;
-      p.wscale_inv = a.wscale_inv;
-      p.tile_base = 0;
-      p.ntile_blocks = (int)(tiles * p.nct);
-      const size_t as_b = 4 * ((size_t)(16 + 2 * DIL) * 24 * 16 + 32);
-      const size_t ldsd = 2 * as_b + 2 * 3 * (size_t)BN * 64 + BN * sizeof(float);
-      const dim3 gd((unsigned)(tiles * p.nct));
-#define SHF_W4D_DIL(SPLIT)                                                                                                    \
-      {                                                                                                                      \
-        if (a.bf16) hipLaunchKernelGGL((conv_mfma_f16x3_w4d_kernel<false, 4, 1, 1, true, DIL>), gd, dim3(256), ldsd, s, p);     \
-        else if (a.nprod >= 3) hipLaunchKernelGGL((conv_mfma_f16x3_w4d_kernel<SPLIT, 4, 1, 3, false, DIL>), gd, dim3(256), ldsd, s, p); \
-        else if (a.nprod == 2) hipLaunchKernelGGL((conv_mfma_f16x3_w4d_kernel<SPLIT, 4, 1, 2, false, DIL>), gd, dim3(256), ldsd, s, p); \
-        else hipLaunchKernelGGL((conv_mfma_f16x3_w4d_kernel<SPLIT, 4, 1, 1, false, DIL>), gd, dim3(256), ldsd, s, p);            \
-      }
-      if (a.in_split) SHF_W4D_DIL(true)
-      else SHF_W4D_DIL(false)
-#undef SHF_W4D_DIL
+    const size_t lds_pc = 2 * (size_t)(TH + 2) * ((TW + 2) * ROWB + 96) + 2 * 3 * (size_t)64 * 128 + (3 * (TH + 4) * (TW + 4) + 8) * sizeof(float) + HPP +
+                          64 * sizeof(float) + 8192 + 64 * sizeof(float) + 16 + 64 + 300 * 4;
+    if (lds_pc > 160 * 1024) { pl.err = "conv f16x3: the fused first pair does not fit the LDS"; return pl; }
+    if (!kn.pc_persist) {
+      add(kK.pc[0][np_col(a)], tiles, 512, lds_pc, 0, 0, 1.0);
+      return pl;
     }
-  } else if (dual) {
+    // one block per CU walks the tiles (tile = block, block + grid, ...)
+    const long long grid = std::min<long long>(tiles, kn.cus);
+    // the per-block tile table: fits (300 tiles per block) and packs (image < 256, tile row / column < 1024)?
+    bool ok = kn.pc_tab != 0 && (tiles + grid - 1) / grid <= 300;
+    for (int i = 0; i < n; ++i)
+      ok = ok && as[i].in.B <= 255 && p.m[i].tiles_x <= 1023 && p.m[i].tiles_per_img / std::max(1, p.m[i].tiles_x) <= 1023;
+    p.pc_tab = ok ? 1 : 0;
+    add(kK.pc[1][np_col(a)], grid, 512, lds_pc, 0, tiles, 1.0);
+    return pl;
+  }
+  if (family && a.dil > 1) {
+    // the dilated heads on the family's DIL form: single 16-row tiles (halo tiles of (16 + 2 DIL)^2 pixels, two buffer sets)
+    const size_t as_b = 4 * ((size_t)(16 + 2 * a.dil) * 24 * 16 + 32);
+    add(kK.w4d_dil[a.dil == 4][split_col(a)], tiles * nct, 256, 2 * as_b + 2 * 3 * (size_t)BN * 64 + BN * sizeof(float), 0,
+        tiles * nct, 1.0);
+    return pl;
+  }
+  if (dual) {
     // dual-tile family (conv_mfma_f16x3_w4d_kernel<.., MT, NTILE, ..>): every variant forms an output with the same
     // operations in the same order, so the choice below -- two tiles per block where that fills whole rounds of one
     // block per CU, single tiles for the rest -- never changes a result.
-    p.wph = a.wsplit16h;
-    p.wscale_inv = a.wscale_inv;
-    const long long per_round = knobs().cus / p.nct > 0 ? knobs().cus / p.nct : 1;   // pixel tiles (single) or pairs (dual) per round
+    const long long per_round = kn.cus / nct > 0 ? kn.cus / nct : 1;   // pixel tiles (single) or pairs (dual) per round
     const long long pairs = (tiles + 1) / 2;
     const double c1 = mt == 4 ? 1.0 : 0.56, c2 = mt == 4 ? 1.82 : 1.02;   // block cost: one / two tiles (w4_pick_mt's unit)
     const long long full2 = pairs / per_round;                  // whole rounds of dual blocks
@@ -413,147 +408,38 @@ if (lds_pc > 160 * 1024) { set_error("conv f16x3: the fused first pair does not 
     long long n2 = 0;                                           // pixel tiles covered by the dual launch
     if (cost_all2 <= cost_all1 && cost_all2 <= cost_hyb) n2 = tiles;
     else if (cost_hyb < cost_all1) n2 = 2 * full2 * per_round;
-    if (w4_short_k(as) && knobs().w4_mt == 0) n2 = 0;          // two single-tile blocks per CU (w4_pick_mt)
-    if (knobs().w4d_ntile == 1) n2 = 0;
-    if (knobs().w4d_ntile == 2) n2 = tiles;
-    // two buffer sets of halo tiles (4 planes of (th + 2) rows x 24 pixels x 16 B, + 32 B), the weight double buffer, biases
-    const size_t as_b = 4 * ((size_t)(th + 2) * 24 * 16 + 32);
+    if (w4_short_k(as) && kn.w4_mt == 0) n2 = 0;               // two single-tile blocks per CU (w4_pick_mt)
+    if (kn.w4d_ntile == 1) n2 = 0;
+    if (kn.w4d_ntile == 2) n2 = tiles;
+    // two buffer sets of halo tiles (4 planes of (rows + 2) x 24 pixels x 16 B, + 32 B), the weight double buffer, biases
+    const size_t as_b = 4 * ((size_t)(4 * mt + 2) * 24 * 16 + 32);
     const size_t lds1 = 2 * as_b + 2 * 3 * (size_t)BN * 64 + BN * sizeof(float), lds2 = lds1 + 2 * as_b;
-#define SHF_W4D_LAUNCH(SPLIT, MTV, NTV, GRID, LDS)                                                                        \
-    {                                                                                                                    \
-      if (a.bf16) hipLaunchKernelGGL((conv_mfma_f16x3_w4d_kernel<false, MTV, NTV, 1, true>), GRID, dim3(256), LDS, s, p);  \
-      else if (a.nprod >= 3) hipLaunchKernelGGL((conv_mfma_f16x3_w4d_kernel<SPLIT, MTV, NTV, 3>), GRID, dim3(256), LDS, s, p);    \
-      else if (a.nprod == 2) hipLaunchKernelGGL((conv_mfma_f16x3_w4d_kernel<SPLIT, MTV, NTV, 2>), GRID, dim3(256), LDS, s, p); \
-      else hipLaunchKernelGGL((conv_mfma_f16x3_w4d_kernel<SPLIT, MTV, NTV, 1>), GRID, dim3(256), LDS, s, p);                 \
-    }
-#define SHF_W4D_PICK(NTV, GRID, LDS)                                       \
-    {                                                                     \
-      if (mt == 4 && a.in_split) SHF_W4D_LAUNCH(true, 4, NTV, GRID, LDS)  \
-      else if (mt == 4) SHF_W4D_LAUNCH(false, 4, NTV, GRID, LDS)          \
-      else if (a.in_split) SHF_W4D_LAUNCH(true, 2, NTV, GRID, LDS)        \
-      else SHF_W4D_LAUNCH(false, 2, NTV, GRID, LDS)                       \
-    }
-    const int vbase = (a.in_split ? 4 : 0) + (mt == 2 ? 2 : 0);
-    if (n2 > 0) {
-      p.tile_base = 0;
-      p.ntile_blocks = (int)(n2 * p.nct);
-      const dim3 g2((unsigned)(((n2 + 1) / 2) * p.nct));
-      if (a.sub_hook) a.sub_hook(a.sub_ctx, 0, vbase, (double)n2 / (double)tiles);
-      SHF_W4D_PICK(2, g2, lds2)
-      if (a.sub_hook) a.sub_hook(a.sub_ctx, 1, vbase, (double)n2 / (double)tiles);
-    }
-    if (n2 < tiles) {
-      p.tile_base = (int)n2;
-      p.ntile_blocks = (int)(tiles * p.nct);
-      const dim3 g1((unsigned)((tiles - n2) * p.nct));
-      if (a.sub_hook) a.sub_hook(a.sub_ctx, 0, vbase + 1, (double)(tiles - n2) / (double)tiles);
-      SHF_W4D_PICK(1, g1, lds1)
-      if (a.sub_hook) a.sub_hook(a.sub_ctx, 1, vbase + 1, (double)(tiles - n2) / (double)tiles);
-    }
-#undef SHF_W4D_PICK
-#undef SHF_W4D_LAUNCH
-  } else if (a.in_split) {
-    set_error("conv f16x3: split-format input reached a kernel other than the 4-wave family (unaligned views, or an input of 4 GiB or more)");
-    return -1;
-  } else {
-    const dim3 g8((unsigned)(tiles * p.nct));
-    if (a.bf16 && FUSE1) { set_error("conv f16x3: bf16 mode runs the first pair on the producer/consumer kernel only"); return -1; }
-    if (a.bf16) hipLaunchKernelGGL((conv_mfma_f16x3_kernel<BN, false, DIL, KS, 1, true>), g8, dim3(512), lds, s, p);
-    else if (FUSE1 || a.nprod >= 3) hipLaunchKernelGGL((conv_mfma_f16x3_kernel<BN, FUSE1, DIL, KS, 3>), g8, dim3(512), lds, s, p);
-    else if (a.nprod == 2) hipLaunchKernelGGL((conv_mfma_f16x3_kernel<BN, false, DIL, KS, 2>), g8, dim3(512), lds, s, p);
-    else hipLaunchKernelGGL((conv_mfma_f16x3_kernel<BN, false, DIL, KS, 1>), g8, dim3(512), lds, s, p);
+    const auto& fam = kK.w4d[mt == 2];
+    if (n2 > 0) add(fam[0][split_col(a)], ((n2 + 1) / 2) * nct, 256, lds2, 0, n2 * nct, (double)n2 / (double)tiles);
+    if (n2 < tiles) add(fam[1][split_col(a)], (tiles - n2) * nct, 256, lds1, n2, tiles * nct, (double)(tiles - n2) / (double)tiles);
+    return pl;
   }
-  SHF_HIP_OK(hipGetLastError());
-#ifdef SHF_CONV_TIMING
-  if (dual) {   // the family's per-block phase sums (conv_f16x3_w4d.h): wave 0 of every block of the layer's launch(es)
-    unsigned long long h[4];
-    hipStreamSynchronize(s);
-    hipMemcpy(h, dbg_dev, sizeof(h), hipMemcpyDeviceToHost);
-    if (h[3])
-      fprintf(stderr, "[w4d timing] Cin %d Cout %d rows %d: %llu blocks, per block cycles: prologue %.0f, K loop %.0f (%d stages: %.0f each), epilogue %.0f\n",
-              p.Cin, p.Cout, 4 * mt, h[3], (double)h[0] / h[3], (double)h[1] / h[3], p.Cin / 16 * 3, (double)h[1] / h[3] / (p.Cin / 16 * 3),
-              (double)h[2] / h[3]);
-  } else {
-    unsigned long long h[80];
-    hipStreamSynchronize(s);
-    hipMemcpy(h, dbg_dev, sizeof(h), hipMemcpyDeviceToHost);
-    for (int w = 0; w < 16; w += 3)
-      if (h[w * 5 + 4])
-        fprintf(stderr, "[f16x3 timing] blk%d wave%d stages %llu: per-stage cycles barrier %.0f issue %.0f compute %.0f tail %.0f\n",
-                w / 8 ? 100 : 0, w % 8, h[w * 5 + 4], (double)h[w * 5] / h[w * 5 + 4], (double)h[w * 5 + 1] / h[w * 5 + 4],
-                (double)h[w * 5 + 2] / h[w * 5 + 4], (double)h[w * 5 + 3] / h[w * 5 + 4]);
+  if (a.in_split) {
+    pl.err = "conv f16x3: split-format input reached a kernel other than the 4-wave family (unaligned views, or an input of 4 GiB or more)";
+    return pl;
   }
-#endif
-  return 0;
-}
-
-// 1x1 GEMM kernel: blocks of 256 pixels of each member's flat pixel list x 256 couts
-static int launch_f16x3_k1(const ConvArgs* as, int n, hipStream_t s) {
-  const ConvArgs& a = as[0];
-  ConvK p = {};
-  p.wp = (const float*)a.wsplit16;
-  p.wph = a.wsplit16h;
-  p.wscale_inv = a.wscale_inv;
-  p.tile_base = 0;
-  p.ntile_blocks = 0;
-  p.pc_tab = 0;
-  p.bias = a.bias;
-  p.Cin = a.in.C; p.Cout = a.out.C;
-  p.in_stride = a.in.cstride; p.out_stride = a.out.cstride;
-  p.dil = 1; p.relu = a.relu | 16 | (a.out_split ? 32 : 0);
-  p.pool_stride = 0;
-  p.nct = p.Cout / 256;
-  p.nmem = n;
-  for (int i = 0; i < MAX_GROUP; ++i) p.tile_starts[i] = 0x7fffffff;
-  p.dbg = nullptr;
-  p.range_flag = a.range_flag;
-  p.w1t = nullptr; p.w1f = nullptr; p.b1 = nullptr;
-  long long tiles = 0;
-  for (int i = 0; i < n; ++i) {
-    const ConvArgs& q = as[i];
-    if (q.in.C != p.Cin || q.out.C != p.Cout || q.in.cstride != p.in_stride || q.out.cstride != p.out_stride ||
-        q.wsplit16h != a.wsplit16h || q.in_split != a.in_split || q.out_split != a.out_split || q.k != 1) {
-      set_error("conv group: members must share the layer");
-      return -1;
-    }
-    ConvMember& m = p.m[i];
-    m.in = q.in.p + q.in.coff;
-    m.out = q.out.p + q.out.coff;
-    m.pool = nullptr;
-    m.img = nullptr;
-    m.in_amax = q.in_amax; m.out_amax = q.out_amax; m.pool_amax = nullptr;
-    m.B = q.in.B; m.H = q.in.H; m.W = q.in.W;
-    const long long npix = (long long)m.B * m.H * m.W;
-    if (npix >= (1ll << 31)) { set_error("conv f16x3: 2^31 pixels or more in one member"); return -1; }
-    m.tiles_x = 1;
-    m.tiles_per_img = (int)((npix + 255) / 256);
-    m.inv_tiles_x = 0; m.inv_tiles_per_img = 0;
-    m.tile_start = (int)tiles;
-    p.tile_starts[i] = (int)tiles;
-    tiles += m.tiles_per_img;
-  }
-  if (tiles * p.nct >= (1ll << 31)) { set_error("conv f16x3: grid too large"); return -1; }
-  const size_t lds = 3 * 256 * 128 + 2 * 2 * 256 * 64;   // three activation chunks + two weight chunks: all 160 KiB
-  const dim3 g((unsigned)(tiles * p.nct));
-#define SHF_K1_LAUNCH(SPLIT)                                                                                         \
-  {                                                                                                                 \
-    if (a.nprod >= 3) hipLaunchKernelGGL((conv_mfma_f16x3_k1_kernel<SPLIT, 3>), g, dim3(256), lds, s, p);            \
-    else if (a.nprod == 2) hipLaunchKernelGGL((conv_mfma_f16x3_k1_kernel<SPLIT, 2>), g, dim3(256), lds, s, p);       \
-    else hipLaunchKernelGGL((conv_mfma_f16x3_k1_kernel<SPLIT, 1>), g, dim3(256), lds, s, p);                         \
-  }
-  if (a.in_split) SHF_K1_LAUNCH(true)
-  else SHF_K1_LAUNCH(false)
-#undef SHF_K1_LAUNCH
-  SHF_HIP_OK(hipGetLastError());
-  return 0;
+  if (a.bf16 && a.img) { pl.err = "conv f16x3: bf16 mode runs the first pair on the producer/consumer kernel only"; return pl; }
+  // 8-wave kernel; (the transposed epilogue needs 256 x (BN + 4) floats: the 1x1 variant's K-loop buffers are smaller than that)
+  const int KS = a.k == 1 ? 1 : 3, padh = a.k == 1 ? 0 : a.dil;
+  const size_t hp = (size_t)(TH + 2 * padh) * (TW + 2 * padh);
+  const size_t lds = std::max(hp * ROWB + 2 * KS * (size_t)BN * ROWB, (size_t)256 * (BN + CS_PAD) * sizeof(float)) +
+                     (a.img ? (3 * (TH + 4) * (TW + 4) + 27 * 64 + 64) * sizeof(float) : 0);
+  const int dcol = a.k == 1 ? 3 : a.dil / 2;   // [DIL 1, 2, 4, then 1x1]
+  add(a.img ? kK.w8_fuse1 : kK.w8[BN == 64][dcol][np_col(a)], tiles * nct, 512, lds, 0, 0, 1.0);
+  return pl;
 }
 
 // The three shared-weight dilated heads as ONE launch (conv_f16x3_h3.h): a1 / a2 / a4 = the dilation-1 / 2 / 4 layers'
 // arguments, member by member.  They must read the same input with the same weights and differ in dilation and output only.
-bool conv_f16x3_group_is_heads3(const ConvArgs* a1, const ConvArgs* a2, const ConvArgs* a4, int n) {
-  if (!knobs().heads3 || n < 1 || n > MAX_GROUP) return false;
+static bool heads3_qualifies(const ConvArgs* a1, const ConvArgs* a2, const ConvArgs* a4, int n) {
+  if (!conv_knobs().heads3 || n < 1 || n > MAX_GROUP) return false;
   const ConvArgs& a = a1[0];
-  if (!a.wsplit16h || a.bf16 || a.img || a.k != 3 || a.dil != 1 || a.out.C != 128 || a.in.C % 16 || !conv_f16x3_uses_w4(a.in.C)) return false;
+  if (!a.wsplit16h || a.bf16 || a.img || a.k != 3 || a.dil != 1 || a.out.C != 128 || a.in.C % 16 || !uses_w4(a.in.C)) return false;
   for (int i = 0; i < n; ++i) {
     const ConvArgs* q[3] = {&a1[i], &a2[i], &a4[i]};
     if (q[1]->dil != 2 || q[2]->dil != 4) return false;
@@ -565,125 +451,33 @@ bool conv_f16x3_group_is_heads3(const ConvArgs* a1, const ConvArgs* a2, const Co
           b.in.B != q[0]->in.B || b.in.H != q[0]->in.H || b.in.W != q[0]->in.W || b.range_flag != a.range_flag)
         return false;
     }
-    if (!views_aligned(q[0], 1) || !views_aligned(q[1], 1) || !views_aligned(q[2], 1)) return false;
-    if ((unsigned long long)a1[i].in.B * a1[i].in.H * a1[i].in.W * a1[i].in.cstride * 4ull >= (1ull << 32)) return false;
+    if (!views_aligned(q[0], 1) || !views_aligned(q[1], 1) || !views_aligned(q[2], 1) || !inputs_under_4gib(q[0], 1)) return false;
   }
   return true;
 }
 
-int launch_conv_f16x3_heads3(const ConvArgs* a1, const ConvArgs* a2, const ConvArgs* a4, int n, hipStream_t s) {
-  if (!conv_f16x3_group_is_heads3(a1, a2, a4, n)) { set_error("conv f16x3: not a shared-weight dilation-1/2/4 triple"); return -1; }
+ConvPlan plan_conv_heads3(const ConvArgs* a1, const ConvArgs* a2, const ConvArgs* a4, int n) {
+  ConvPlan pl;
+  if (!heads3_qualifies(a1, a2, a4, n)) return pl;
+  const long long tiles = conv_fill(pl, a1, n, 1, 8, 16);
+  if (tiles < 0) return pl;
   const ConvArgs& a = a1[0];
-  ConvK p = {};
+  ConvK& p = pl.k;
   p.wp = (const float*)a.wsplit16;
   p.wph = a.wsplit16h;
   p.wscale_inv = a.wscale_inv;
-  p.bias = a.bias;
-  p.Cin = a.in.C; p.Cout = a.out.C;
-  p.in_stride = a.in.cstride; p.out_stride = a.out.cstride;
-  p.dil = 1; p.relu = a.relu | 16 | (a.out_split ? 32 : 0);
-  p.nct = 1;
-  p.nmem = n;
-  for (int i = 0; i < MAX_GROUP; ++i) p.tile_starts[i] = 0x7fffffff;
-  p.range_flag = a.range_flag;
-  long long tiles = 0;
+  p.flags |= CONV_VEC_EPI | (a.out_split ? CONV_MAIN_SPLIT : 0);
   for (int i = 0; i < n; ++i) {
     ConvMember& m = p.m[i];
-    m.in = a1[i].in.p + a1[i].in.coff;
-    m.out = a1[i].out.p + a1[i].out.coff;
     m.out2 = a2[i].out.p + a2[i].out.coff;
     m.out3 = a4[i].out.p + a4[i].out.coff;
-    m.in_amax = a1[i].in_amax;
-    m.out_amax = a1[i].out_amax; m.out2_amax = a2[i].out_amax; m.out3_amax = a4[i].out_amax;
-    m.B = a1[i].in.B; m.H = a1[i].in.H; m.W = a1[i].in.W;
-    m.tiles_x = (m.W + 15) / 16;
-    m.tiles_per_img = m.tiles_x * ((m.H + 7) / 8);
-    m.inv_tiles_x = conv_inv32(m.tiles_x);
-    m.inv_tiles_per_img = conv_inv32(m.tiles_per_img);
-    m.tile_start = (int)tiles;
-    p.tile_starts[i] = (int)tiles;
-    tiles += (long long)m.tiles_per_img * m.B;
-    if ((unsigned long long)m.tiles_per_img * m.B * (unsigned long long)m.tiles_per_img >= (1ull << 32)) {
-      set_error("conv f16x3: more than 2^32 / tiles-per-image pixel tiles in one member");
-      return -1;
-    }
+    m.out2_amax = a2[i].out_amax;
+    m.out3_amax = a4[i].out_amax;
   }
-  if (tiles >= (1ll << 31)) { set_error("conv f16x3: grid too large"); return -1; }
-  p.ntile_blocks = (int)tiles;
   const size_t as_b = 4 * ((size_t)16 * 24 * 16 + 32);
-  const size_t lds = 2 * as_b + 2 * 3 * (size_t)128 * 64 + 128 * sizeof(float);
-  const dim3 g((unsigned)tiles);
-#define SHF_H3_LAUNCH(SPLIT)                                                                                        \
-  {                                                                                                                \
-    if (a.nprod >= 3) hipLaunchKernelGGL((conv_mfma_f16x3_heads3_kernel<SPLIT, 3>), g, dim3(256), lds, s, p);       \
-    else if (a.nprod == 2) hipLaunchKernelGGL((conv_mfma_f16x3_heads3_kernel<SPLIT, 2>), g, dim3(256), lds, s, p);  \
-    else hipLaunchKernelGGL((conv_mfma_f16x3_heads3_kernel<SPLIT, 1>), g, dim3(256), lds, s, p);                    \
-  }
-  if (a.in_split) SHF_H3_LAUNCH(true)
-  else SHF_H3_LAUNCH(false)
-#undef SHF_H3_LAUNCH
-  SHF_HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int conv_f16x3_init_attributes() {
-  (void)knobs();
-#define SHF_LDS_ATTR(K) SHF_HIP_OK(hipFuncSetAttribute((const void*)(K), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#define SHF_8W_ATTR(BNV, DILV, KSV)                                       \
-  SHF_LDS_ATTR((conv_mfma_f16x3_kernel<BNV, false, DILV, KSV, 3>))         \
-  SHF_LDS_ATTR((conv_mfma_f16x3_kernel<BNV, false, DILV, KSV, 2>))         \
-  SHF_LDS_ATTR((conv_mfma_f16x3_kernel<BNV, false, DILV, KSV, 1>))         \
-  SHF_LDS_ATTR((conv_mfma_f16x3_kernel<BNV, false, DILV, KSV, 1, true>))
-  SHF_8W_ATTR(128, 1, 3) SHF_8W_ATTR(128, 1, 1) SHF_8W_ATTR(64, 1, 1) SHF_8W_ATTR(64, 2, 3) SHF_8W_ATTR(64, 4, 3) SHF_8W_ATTR(64, 1, 3)
-#undef SHF_8W_ATTR
-  SHF_LDS_ATTR((conv_mfma_f16x3_kernel<64, true, 1, 3, 3>))
-  SHF_LDS_ATTR(conv_mfma_f16x3_pc_kernel<3>)
-  SHF_LDS_ATTR(conv_mfma_f16x3_pc_kernel<2>)
-  SHF_LDS_ATTR(conv_mfma_f16x3_pc_kernel<1>)
-  SHF_LDS_ATTR((conv_mfma_f16x3_pc_kernel<1, true>))
-  SHF_LDS_ATTR((conv_mfma_f16x3_pc_kernel<3, false, true>))
-  SHF_LDS_ATTR((conv_mfma_f16x3_pc_kernel<2, false, true>))
-  SHF_LDS_ATTR((conv_mfma_f16x3_pc_kernel<1, false, true>))
-  SHF_LDS_ATTR((conv_mfma_f16x3_pc_kernel<1, true, true>))
-#define SHF_W4D_ATTR(SPLIT, MTV, NTV)                                      \
-  SHF_LDS_ATTR((conv_mfma_f16x3_w4d_kernel<SPLIT, MTV, NTV, 3>))           \
-  SHF_LDS_ATTR((conv_mfma_f16x3_w4d_kernel<SPLIT, MTV, NTV, 2>))           \
-  SHF_LDS_ATTR((conv_mfma_f16x3_w4d_kernel<SPLIT, MTV, NTV, 1>))
-  SHF_W4D_ATTR(false, 4, 2) SHF_W4D_ATTR(true, 4, 2) SHF_W4D_ATTR(false, 4, 1) SHF_W4D_ATTR(true, 4, 1)
-  SHF_W4D_ATTR(false, 2, 2) SHF_W4D_ATTR(true, 2, 2) SHF_W4D_ATTR(false, 2, 1) SHF_W4D_ATTR(true, 2, 1)
-#undef SHF_W4D_ATTR
-#define SHF_W4D_DIL_ATTR(DILV)                                                                                                  \
-  SHF_LDS_ATTR((conv_mfma_f16x3_w4d_kernel<false, 4, 1, 3, false, DILV>)) SHF_LDS_ATTR((conv_mfma_f16x3_w4d_kernel<true, 4, 1, 3, false, DILV>)) \
-  SHF_LDS_ATTR((conv_mfma_f16x3_w4d_kernel<false, 4, 1, 2, false, DILV>)) SHF_LDS_ATTR((conv_mfma_f16x3_w4d_kernel<true, 4, 1, 2, false, DILV>)) \
-  SHF_LDS_ATTR((conv_mfma_f16x3_w4d_kernel<false, 4, 1, 1, false, DILV>)) SHF_LDS_ATTR((conv_mfma_f16x3_w4d_kernel<true, 4, 1, 1, false, DILV>)) \
-  SHF_LDS_ATTR((conv_mfma_f16x3_w4d_kernel<false, 4, 1, 1, true, DILV>))
-  SHF_W4D_DIL_ATTR(2) SHF_W4D_DIL_ATTR(4)
-#undef SHF_W4D_DIL_ATTR
-  SHF_LDS_ATTR((conv_mfma_f16x3_w4d_kernel<false, 4, 2, 1, true>)) SHF_LDS_ATTR((conv_mfma_f16x3_w4d_kernel<false, 4, 1, 1, true>))
-  SHF_LDS_ATTR((conv_mfma_f16x3_w4d_kernel<false, 2, 2, 1, true>)) SHF_LDS_ATTR((conv_mfma_f16x3_w4d_kernel<false, 2, 1, 1, true>))
-  SHF_LDS_ATTR((conv_mfma_f16x3_k1_kernel<true, 3>)) SHF_LDS_ATTR((conv_mfma_f16x3_k1_kernel<true, 2>)) SHF_LDS_ATTR((conv_mfma_f16x3_k1_kernel<true, 1>))
-  SHF_LDS_ATTR((conv_mfma_f16x3_heads3_kernel<true, 3>)) SHF_LDS_ATTR((conv_mfma_f16x3_heads3_kernel<true, 2>)) SHF_LDS_ATTR((conv_mfma_f16x3_heads3_kernel<true, 1>))
-  SHF_LDS_ATTR((conv_mfma_f16x3_heads3_kernel<false, 3>)) SHF_LDS_ATTR((conv_mfma_f16x3_heads3_kernel<false, 2>)) SHF_LDS_ATTR((conv_mfma_f16x3_heads3_kernel<false, 1>))
-  SHF_LDS_ATTR((conv_mfma_f16x3_k1_kernel<false, 3>)) SHF_LDS_ATTR((conv_mfma_f16x3_k1_kernel<false, 2>)) SHF_LDS_ATTR((conv_mfma_f16x3_k1_kernel<false, 1>))
-#undef SHF_LDS_ATTR
-  return 0;
-}
-
-int launch_conv_f16x3_group(const ConvArgs* as, int n, hipStream_t s) {
-  if (n < 1 || n > MAX_GROUP) { set_error("conv group: 1..16 members"); return -1; }
-  for (int i = 0; i < n; ++i)
-    if ((as[i].in.cstride % 4) || (as[i].in.coff % 4)) { set_error("conv: input view not 16-byte aligned"); return -1; }
-  if (!as[0].wsplit16) { set_error("conv f16x3: split weights not packed"); return -1; }
-  if (as[0].img) {
-    if (as[0].in.C != 64 || !as[0].w1t) { set_error("conv f16x3: fused first layer needs 64 channels + transposed weights"); return -1; }
-    return launch_f16x3_t<64, true>(as, n, s);  // conv1_1 computed in place (BN=64 tile: Cout 64 or any multiple of 64)
-  }
-  if (as[0].k == 1 && conv_f16x3_group_is_k1_gemm(as, n)) return launch_f16x3_k1(as, n, s);
-  if (as[0].k == 1)
-    return (as[0].out.C % 128 == 0) ? launch_f16x3_t<128, false, 1, 1>(as, n, s) : launch_f16x3_t<64, false, 1, 1>(as, n, s);
-  if (as[0].dil == 2) return conv_f16x3_group_is_dilated_w4(as, n) ? launch_f16x3_t<128, false, 2>(as, n, s) : launch_f16x3_t<64, false, 2>(as, n, s);
-  if (as[0].dil == 4) return conv_f16x3_group_is_dilated_w4(as, n) ? launch_f16x3_t<128, false, 4>(as, n, s) : launch_f16x3_t<64, false, 4>(as, n, s);
-  return (as[0].out.C % 128 == 0) ? launch_f16x3_t<128, false>(as, n, s) : launch_f16x3_t<64, false>(as, n, s);
+  pl.l[pl.nl++] = {&kK.h3[split_col(a)], dim3((unsigned)tiles), dim3(256), 2 * as_b + 2 * 3 * (size_t)128 * 64 + 128 * sizeof(float), 0,
+                   (int)tiles, 1.0};
+  return pl;
 }
 
 }  // namespace shf

@@ -339,7 +339,7 @@ __global__ __launch_bounds__(512) void conv_mfma_f16x3_kernel(ConvK p) {
 
   // epilogue: C row = (r&3) + 8*(r>>2) + 4*(lane>>5), C col = lane&31
   float amax = 0.f;  // fp16 range guard: largest |output| of this lane
-  if (p.relu & 16) {
+  if (p.flags & CONV_VEC_EPI) {
     __syncthreads();  // the K loop's LDS buffers are dead: the output tile is transposed through them
     float* Cs = (float*)smem;
 #pragma unroll
@@ -348,7 +348,7 @@ __global__ __launch_bounds__(512) void conv_mfma_f16x3_kernel(ConvK p) {
       const float bv = p.bias ? p.bias[ct * BN + cl] : 0.f;
 #pragma unroll
       for (int tm = 0; tm < MT; ++tm) {
-        if (p.relu & 1)
+        if (p.flags & CONV_RELU)
           conv_stage_tile_pk<BN, true>(Cs, accm[tm][tn], accc[tm][tn], LO_INV, bv, wm * 2 * MT + tm * 2, kh, cl, amax, H - ty0, W - tx0);
         else
           conv_stage_tile_pk<BN, false>(Cs, accm[tm][tn], accc[tm][tn], LO_INV, bv, wm * 2 * MT + tm * 2, kh, cl, amax, H - ty0, W - tx0);
@@ -356,7 +356,7 @@ __global__ __launch_bounds__(512) void conv_mfma_f16x3_kernel(ConvK p) {
     }
     __syncthreads();
     conv_flush_tile<BN, 512>(Cs, tid, ty0, tx0, H, W, b, ct * BN, gout, p.out_stride, mem.pool, p.pool_stride,
-                             !(p.relu & 8), (p.relu & 32) != 0, (p.relu & 64) != 0);
+                             !(p.flags & CONV_NO_MAIN), (p.flags & CONV_MAIN_SPLIT) != 0, (p.flags & CONV_POOL_SPLIT) != 0);
     conv_raise_range_flag(p.range_flag, amax);
     conv_publish_amax(mem.out_amax, mem.pool ? mem.pool_amax : nullptr, amax);
 #ifdef SHF_CONV_TIMING
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(512) void conv_mfma_f16x3_kernel(ConvK p) {
 #pragma unroll
     for (int tm = 0; tm < MT; ++tm) {
       const f32x16 am = accm[tm][tn], ac = accc[tm][tn];
-      conv_store_tile([&](int r) { return am[r] + ac[r] * LO_INV; }, bv, p.relu, ty0 + wm * 2 * MT + tm * 2, tx0, kh,
+      conv_store_tile([&](int r) { return am[r] + ac[r] * LO_INV; }, bv, p.flags, ty0 + wm * 2 * MT + tm * 2, tx0, kh,
                       H, W, b, cout, gout, p.out_stride, mem.pool, p.pool_stride, &amax);
     }
   }

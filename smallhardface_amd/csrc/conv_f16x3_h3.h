@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256) void conv_mfma_f16x3_heads3_kernel(ConvK p) {
   // register epilogue, one dilation after the other (the family's conv_epilogue_regs1)
   float amax1 = 0.f, amax2 = 0.f, amax4 = 0.f;
   {
-    const bool relu = (p.relu & 1) != 0, main_split = (p.relu & 32) != 0;
+    const bool relu = (p.flags & CONV_RELU) != 0, main_split = (p.flags & CONV_MAIN_SPLIT) != 0;
     int lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     asm volatile("" : "+v"(lane_e));
     const int i_e = lane_e & 31, kh_e = lane_e >> 5;

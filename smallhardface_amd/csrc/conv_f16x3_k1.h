@@ -245,7 +245,7 @@ __global__ __launch_bounds__(256) void conv_mfma_f16x3_k1_kernel(ConvK p) {
 #endif
 
   {
-    const bool relu = (p.relu & 1) != 0, main_split = (p.relu & 32) != 0;
+    const bool relu = (p.flags & CONV_RELU) != 0, main_split = (p.flags & CONV_MAIN_SPLIT) != 0;
     const float out_scale = p.wscale_inv * __builtin_bit_cast(float, (unsigned)(127 - e_act) << 23);   // 2^-e, exact
     float amax = 0.f;
     if (main_split) {

@@ -597,8 +597,8 @@ __global__ __launch_bounds__(512) void conv_mfma_f16x3_pc_kernel(ConvK p) {
   // consecutive couts per lane, fused 2x2 max-pool as a DPP quad max) -- no LDS round trip, no barrier
   float amax = 0.f;  // this layer's stored outputs: fp16 range guard (with conv1_1's, amax1) + activation exponent
   if (consumer) {
-    const bool relu = (p.relu & 1) != 0, write_main = !(p.relu & 8), main_split = (p.relu & 32) != 0,
-               pool_split = (p.relu & 64) != 0;
+    const bool relu = (p.flags & CONV_RELU) != 0, write_main = !(p.flags & CONV_NO_MAIN), main_split = (p.flags & CONV_MAIN_SPLIT) != 0,
+               pool_split = (p.flags & CONV_POOL_SPLIT) != 0;
     // (the lane's coordinates are formed AGAIN here, from the lane id the hardware hands out: kept alive across the K loop
     // they are spilled, and a scratch reload between the stores waits for every store issued so far)
     int lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));

@@ -461,8 +461,8 @@ __global__ __launch_bounds__(256) void conv_mfma_f16x3_w4d_kernel(ConvK p) {
   // register epilogue, one tile after the other (each with its unit's scale and its unit's max |output| slot)
   float amax0 = 0.f, amax1 = 0.f;
   {
-    const bool relu = (p.relu & 1) != 0, write_main = !(p.relu & 8), main_split = (p.relu & 32) != 0,
-               pool_split = (p.relu & 64) != 0;
+    const bool relu = (p.flags & CONV_RELU) != 0, write_main = !(p.flags & CONV_NO_MAIN), main_split = (p.flags & CONV_MAIN_SPLIT) != 0,
+               pool_split = (p.flags & CONV_POOL_SPLIT) != 0;
     // the lane's coordinates are formed AGAIN here, from the lane id the hardware hands out (mbcnt) and the wave number
     // in its scalar register: kept alive across the K loop they were spilled, and every scratch reload in an epilogue
     // is followed by a vmcnt(0) that waits for all the stores issued so far

@@ -199,28 +199,14 @@ int shf_detect_add_levels(shf_net* net, int n, shf_net** members, const float* c
                        mb->blobs[mb->layers[li].tops[0]].shape);
       by += 4.0 * (mb->blobs[mb->layers[li].bottoms[0]].count() + mb->blobs[mb->layers[li].tops[0]].count());
     }
-    if (group[0].wsplit16) {
-      if (group[0].img && L.first_src >= 0) {  // conv1_1's work rides in this launch
-        for (int m = 0; m < n; ++m) {
-          shf_net* mb = members[m];
-          const Layer& F = mb->layers[L.first_src];
-          fl += conv_flops(F, mb->blobs[F.bottoms[0]].shape, mb->blobs[F.tops[0]].shape);
-        }
+    if (group[0].wsplit16 && group[0].img && L.first_src >= 0) {  // conv1_1's work rides in this launch
+      for (int m = 0; m < n; ++m) {
+        shf_net* mb = members[m];
+        const Layer& F = mb->layers[L.first_src];
+        fl += conv_flops(F, mb->blobs[F.bottoms[0]].shape, mb->blobs[F.tops[0]].shape);
       }
-      if (conv_f16x3_group_is_dual(group.data(), n)) {
-        SubProf sp{&net->prof, st, fl, by, {}};
-        group[0].sub_hook = &SubProf::hook;
-        group[0].sub_ctx = &sp;
-        CHECK_RC_LAYER(launch_conv_f16x3_group(group.data(), n, st), L.name);
-      } else {
-        ProfScope ps(net->prof, st, f16x3_prof_class(group[0], L.nout, group.data(), n), fl, by);
-        CHECK_RC_LAYER(launch_conv_f16x3_group(group.data(), n, st), L.name);
-      }
-    } else {
-      const int pc = conv_prof_class(L.k, L.dil, L.nout);
-      ProfScope ps(net->prof, st, pc, fl, by);
-      CHECK_RC(launch_conv_mfma_group(group.data(), n, st));
     }
+    CHECK_RC_LAYER(run_conv_plan(plan_conv(group.data(), n), st, net->prof, fl, by), L.name);
   };
   // the three shared-weight dilated heads of every unit as ONE launch (conv_f16x3_h3.h); false: not that shape / mode
   int heads3_done = -1;
@@ -236,9 +222,9 @@ int shf_detect_add_levels(shf_net* net, int n, shf_net** members, const float* c
       fl += 3.0 * conv_flops(mb->layers[li], mb->blobs[mb->layers[li].bottoms[0]].shape, mb->blobs[mb->layers[li].tops[0]].shape);
       by += 4.0 * (mb->blobs[mb->layers[li].bottoms[0]].count() + 3.0 * mb->blobs[mb->layers[li].tops[0]].count());
     }
-    if (!group[0].wsplit16h || !conv_f16x3_group_is_heads3(group.data(), g2.data(), g4.data(), n)) return false;
-    ProfScope ps(net->prof, st, PC_CONV_F16X3_H3, fl, by);
-    CHECK_RC(launch_conv_f16x3_heads3(group.data(), g2.data(), g4.data(), n, st));
+    const ConvPlan pl = plan_conv_heads3(group.data(), g2.data(), g4.data(), n);
+    if (pl.nl == 0 && pl.err.empty()) return false;
+    CHECK_RC_LAYER(run_conv_plan(pl, st, net->prof, fl, by), L.name);
     return true;
   };
   for (size_t li = 0; li < net->layers.size(); ++li) {

@@ -8,8 +8,7 @@ const char* const kProfNames[PC_COUNT] = {"conv_mfma_f32_kernel<3, 1, 128, 8, 16
                                            "conv_mfma_f32_kernel<3, 4, 128, 8, 16>", "conv_mfma_f32_kernel<3, 1, 64, 16, 16>",
                                            "conv_mfma_f32_kernel<3, 2, 64, 16, 16>", "conv_mfma_f32_kernel<3, 4, 64, 16, 16>",
                                            "conv_mfma_f32_kernel<1, 0, 128, 8, 16>", "conv_mfma_f32_kernel<1, 0, 64, 16, 16>",
-                                           "conv_mfma_f16x3_kernel<128, false, 1, 3, 3, false>", "(retired: single-tile 4-wave kernel)",
-                                           "(retired)", "(retired)", "(retired)",
+                                           "conv_mfma_f16x3_kernel<128, false, 1, 3, 3, false>",
                                            "conv_mfma_f16x3_kernel<64, false, 1, 3, 3, false>",
                                            "conv_mfma_f16x3_kernel<64, true, 1, 3, 3, false>", "conv_mfma_f16x3_kernel<64, false, 2, 3, 3, false>",
                                            "conv_mfma_f16x3_kernel<64, false, 4, 3, 3, false>", "conv_mfma_f16x3_kernel<128, false, 1, 1, 3, false>",
@@ -28,27 +27,16 @@ const char* const kProfNames[PC_COUNT] = {"conv_mfma_f32_kernel<3, 1, 128, 8, 16
                                            "conv_first_kernel", "conv_direct_kernel", "maxpool_kernel",
                                            "deconv_depthwise", "detect_tail", "box_merge", "layout", "h2d_copy", "d2h_copy"};
 
-// which split-fp16 kernel launch_conv_f16x3_group picks for these arguments -- decided by the launcher's OWN predicates on the
-// actual arguments, so that the 8-wave fallbacks (unaligned views, Cout % 256, bf16 1x1s ...) are not booked under the name of
-// the kernel the knobs would normally select
-int f16x3_prof_class(const ConvArgs& a, int nout, const ConvArgs* group, int n) {
-  const ConvArgs* as = group ? group : &a;
-  if (a.img) {
-    if (!(conv_f16x3_uses_pc() && a.in.C == 64 && nout == 64)) return PC_CONV_F16X3_64_FUSE1;
-    return conv_f16x3_pc_persistent() ? PC_CONV_F16X3_PCP : PC_CONV_F16X3_PC;
+int run_conv_plan(const ConvPlan& pl, hipStream_t s, Prof& prof, double flops, double bytes) {
+  if (!pl.err.empty()) {
+    set_error(pl.err);
+    return -1;
   }
-  if (a.k == 1) return conv_f16x3_group_is_k1_gemm(as, n) ? PC_CONV_F16X3_K1G : (nout % 128 ? PC_CONV_F16X3_64_K1 : PC_CONV_F16X3_128_K1);
-  if (a.dil == 2) return conv_f16x3_group_is_dilated_w4(as, n) ? PC_CONV_F16X3_W4D_D2 : PC_CONV_F16X3_64_D2;
-  if (a.dil == 4) return conv_f16x3_group_is_dilated_w4(as, n) ? PC_CONV_F16X3_W4D_D4 : PC_CONV_F16X3_64_D4;
-  if (nout % 128) return PC_CONV_F16X3_64;
-  return PC_CONV_F16X3_128;   // (the dual-tile family reports through SubProf, one record per kernel of the layer)
-}
-
-int conv_prof_class(int k, int dil, int nout) {
-  const int bn64 = (nout % 128 == 0) ? 0 : 1;
-  if (k == 1) return 6 + bn64;
-  const int d = dil == 1 ? 0 : dil == 2 ? 1 : 2;
-  return bn64 * 3 + d;
+  for (int i = 0; i < pl.nl; ++i) {
+    ProfScope ps(prof, s, pl.l[i].kern->prof, flops * pl.l[i].share, bytes * pl.l[i].share);
+    if (launch_conv_plan(pl, i, s)) return -1;
+  }
+  return 0;
 }
 }  // namespace shf
 
@@ -91,11 +79,11 @@ void shf_net::forward_ops(bool fused_path, float im_h, float im_w, float im_scal
     ConvArgs a2, a4;
     forward_ops(fused_path, im_h, im_w, im_scale, st_, &pf_, L1.heads3_d2, &a2);
     forward_ops(fused_path, im_h, im_w, im_scale, st_, &pf_, L1.heads3_d4, &a4);
-    if (!conv_f16x3_group_is_heads3(&a, &a2, &a4, 1)) return false;
+    const ConvPlan pl = plan_conv_heads3(&a, &a2, &a4, 1);
+    if (pl.nl == 0 && pl.err.empty()) return false;
     const double fl = 3.0 * conv_flops(L1, blobs[L1.bottoms[0]].shape, blobs[L1.tops[0]].shape);
     const double by = 4.0 * (blobs[L1.bottoms[0]].count() + 3.0 * blobs[L1.tops[0]].count() + L1.params[0]->count());
-    ProfScope ps(pf_, st_, PC_CONV_F16X3_H3, fl, by);
-    CHECK_RC(launch_conv_f16x3_heads3(&a, &a2, &a4, 1, st_));
+    CHECK_RC_LAYER(run_conv_plan(pl, st_, pf_, fl, by), L1.name);
     return true;
   };
   for (size_t li = 0; li < layers.size(); ++li) {
@@ -145,7 +133,7 @@ void shf_net::forward_ops(bool fused_path, float im_h, float im_w, float im_scal
         // FUSE1 form instead)
         auto pair_fused = [&](const Layer& F1, const Layer& F2) {
           if (!bf) return true;
-          return conv_f16x3_uses_pc() && F1.params[0]->first_frag_b.p != nullptr && F1.nout == 64 && F2.nout == 64;
+          return conv_knobs().pc && F1.params[0]->first_frag_b.p != nullptr && F1.nout == 64 && F2.nout == 64;
         };
         if (fused_path && split16 && L.first_src >= 0 && pair_fused(layers[L.first_src], L)) {
           Layer& F = layers[L.first_src];
@@ -174,20 +162,8 @@ void shf_net::forward_ops(bool fused_path, float im_h, float im_w, float im_scal
             // written by the dilation-1 sibling's launch (the three shared-weight heads in one kernel)
           } else if (L.kclass == 0 && split16 && L.heads3_d2 >= 0 && only_layer < 0 && try_heads3((int)li, a, st, pf)) {
             heads3_done = (int)li;
-          } else if (L.kclass == 0 && split16) {
-            if (conv_f16x3_group_is_dual(&a, 1)) {
-              SubProf sp{&pf, st, fl, by, {}};
-              a.sub_hook = &SubProf::hook;
-              a.sub_ctx = &sp;
-              CHECK_RC_LAYER(launch_conv_f16x3_group(&a, 1, st), L.name);
-            } else {
-              ProfScope ps(pf, st, f16x3_prof_class(a, L.nout), fl, by);
-              CHECK_RC_LAYER(launch_conv_f16x3_group(&a, 1, st), L.name);
-            }
           } else if (L.kclass == 0) {
-            const int pc = conv_prof_class(L.k, L.dil, L.nout);
-            ProfScope ps(pf, st, pc, fl, by);
-            CHECK_RC(launch_conv_mfma(a, st));
+            CHECK_RC_LAYER(run_conv_plan(plan_conv(&a, 1), st, pf, fl, by), L.name);
           } else {
             ProfScope ps(pf, st, PC_CONV_DIRECT, fl, by);
             CHECK_RC(launch_conv_direct(a, st));

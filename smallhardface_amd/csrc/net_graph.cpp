@@ -126,7 +126,6 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   root = tp.parse();
   HIP_THROW(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
   CHECK_RC(conv_init_attributes());
-  CHECK_RC(conv_f16x3_init_attributes());
 
   // ---- inputs: legacy `input:` + input_shape / input_dim (upgrade_proto.cpp:966-1000)
   auto in_names = root->all("input");
@@ -505,25 +504,21 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   // ---- blobs the fused split-fp16 path keeps in the pre-split activation format: produced by a split-fp16 conv
   //      (or by the pool fused into its epilogue) and read ONLY by convs that run on the 4-wave kernel
   {
-    static const bool split_act = !(getenv("SHF_F16X3_SPLIT_ACT") && atoi(getenv("SHF_F16X3_SPLIT_ACT")) == 0);
-    // (the static half of the launch-time predicates conv_f16x3_group_is_dual / _dilated_w4 / _k1_gemm: what a reader writes
-    // -- its top and the top of a pool fused into it -- must be a 16-byte aligned channel view, and the GEMM kernel takes no
-    // fused pool; the dynamic half -- an input of 4 GiB or more -- fails the launch with the layer's name)
+    // (plan_conv's shape-only half, conv_f16x3_family_shape: what a reader writes -- its top and the top of a pool fused into
+    // it -- must be a 16-byte aligned channel view; the launch-time half -- an input of 4 GiB or more -- fails the launch with
+    // the layer's name)
     auto aligned_view = [&](int bi_) {
       const Blob& b_ = blobs[bi_];
       const Blob& ob_ = blobs[b_.owner >= 0 ? b_.owner : bi_];
       return ob_.shape.size() == 4 && ob_.shape[1] % 4 == 0 && b_.coff % 4 == 0;
     };
     auto w4_reader = [&](const Layer& Q, int cin) {
-      const bool dil_ok = Q.dil == 1 || Q.dil == 2 || Q.dil == 4;   // (the heads: family's DIL form / the three-heads kernel)
-      if (Q.op != OP_CONV || Q.tops.empty() || !aligned_view(Q.tops[0])) return false;
-      if (Q.fuse_pool >= 0 && !aligned_view(layers[Q.fuse_pool].tops[0])) return false;
-      if (Q.op == OP_CONV && Q.kclass == 0 && Q.k == 1 && Q.pad == 0 && Q.first_src < 0)   // 1x1 layers on the GEMM kernel
-        return Q.fuse_pool < 0 && conv_f16x3_k1_gemm_shape(cin, Q.nout) && conv_f16x3_eligible(cin, Q.nout, Q.k, Q.pad, Q.dil);
-      return Q.op == OP_CONV && Q.kclass == 0 && Q.k == 3 && dil_ok && Q.pad == Q.dil && cin % 32 == 0 && Q.nout % 128 == 0 &&
-             Q.first_src < 0 && conv_f16x3_uses_w4(cin) && conv_f16x3_eligible(cin, Q.nout, Q.k, Q.pad, Q.dil);
+      if (Q.op != OP_CONV || Q.kclass != 0 || Q.first_src >= 0 || Q.tops.empty()) return false;
+      const bool pool = Q.fuse_pool >= 0;
+      const bool aligned = aligned_view(Q.tops[0]) && (!pool || aligned_view(layers[Q.fuse_pool].tops[0]));
+      return conv_f16x3_family_shape(cin, Q.nout, Q.k, Q.pad, Q.dil, pool, aligned);
     };
-    for (size_t bi = 0; bi < blobs.size() && split_act; ++bi) {
+    for (size_t bi = 0; bi < blobs.size() && conv_knobs().split_act; ++bi) {
       Blob& B = blobs[bi];
       if (B.owner >= 0 || B.kind != BK_NHWC || B.shape.size() != 4) continue;
       if (std::count(tail_feat_blobs.begin(), tail_feat_blobs.end(), (int)bi)) continue;
@@ -698,9 +693,7 @@ void shf_net::commit_params(int li) {
   if (L.params.empty()) return;
   // the dual-tile family's weight pack (16-channel slabs, unscaled low parts): its 3x3 layers, and the 1x1 GEMM kernel's
   auto wants_family_pack = [](const Layer& Q, const ParamBlob& w) {
-    if (Q.k == 1) return Q.pad == 0 && conv_f16x3_k1_gemm_shape(w.shape[1], w.shape[0]);
-    return Q.k == 3 && (Q.dil == 1 || Q.dil == 2 || Q.dil == 4) && conv_f16x3_uses_w4(w.shape[1]) &&
-           w.shape[0] % 128 == 0 && w.shape[1] % 32 == 0;
+    return conv_f16x3_family_shape(w.shape[1], w.shape[0], Q.k, Q.pad, Q.dil, false, true);
   };
   // the raw / packed tensors are shared by every lane cloned from this net: nothing may be in flight on any stream
   HIP_THROW(hipDeviceSynchronize());

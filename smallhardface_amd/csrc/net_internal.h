@@ -13,6 +13,7 @@
 #include <set>
 
 #include "../../include/shf_hip.h"
+#include "conv_common.h"
 #include "proto_text.h"
 #include "shf_internal.h"
 
@@ -168,12 +169,10 @@ struct Layer {
   int first_dst = -1;      // first-layer conv: index of the conv that absorbs it
   // the three shared-weight dilated heads (prototxt :480-552): on the dilation-1 layer, the indices of its dilation-2 / -4
   // siblings (same bottom, same parameter blobs); on those, the index of the dilation-1 layer.  One launch covers the three
-  // when the shapes and the mode allow (conv_f16x3_group_is_heads3).
+  // when the shapes and the mode allow (plan_conv_heads3).
   int heads3_d2 = -1, heads3_d4 = -1, heads3_lead = -1;
 };
 
-// the first 8 classes are the instantiations of conv_mfma_f32_kernel, named like rocprofv3 prints them
-enum ProfClass { PC_CONV_MFMA, PC_CONV_MFMA_1 = 1, PC_CONV_MFMA_7 = 7, PC_CONV_F16X3_128, PC_CONV_F16X3_W4, PC_CONV_F16X3_W4_SPLIT, PC_CONV_F16X3_W4_MT2, PC_CONV_F16X3_W4_SPLIT_MT2, PC_CONV_F16X3_64, PC_CONV_F16X3_64_FUSE1, PC_CONV_F16X3_64_D2, PC_CONV_F16X3_64_D4, PC_CONV_F16X3_128_K1, PC_CONV_F16X3_64_K1, PC_CONV_F16X3_PC, PC_CONV_F16X3_W4D_0, PC_CONV_F16X3_W4D_7 = PC_CONV_F16X3_W4D_0 + 7, PC_CONV_F16X3_PCP, PC_CONV_F16X3_K1G, PC_CONV_F16X3_W4D_D2, PC_CONV_F16X3_W4D_D4, PC_CONV_F16X3_H3, PC_CONV_FIRST, PC_CONV_DIRECT, PC_POOL, PC_DECONV, PC_TAIL, PC_MERGE, PC_LAYOUT, PC_H2D, PC_D2H, PC_COUNT };
 extern const char* const kProfNames[PC_COUNT];   // net_forward.cpp
 
 struct Prof {
@@ -215,12 +214,6 @@ struct Prof {
   }
 };
 
-// which split-fp16 kernel launch_conv_f16x3_group picks for these arguments -- decided by the launcher's OWN predicates on the
-// actual arguments, so that the 8-wave fallbacks (unaligned views, Cout % 256, bf16 1x1s ...) are not booked under the name of
-// the kernel the knobs would normally select
-int f16x3_prof_class(const ConvArgs& a, int nout, const ConvArgs* group = nullptr, int n = 1);   // net_forward.cpp
-int conv_prof_class(int k, int dil, int nout);
-
 struct ProfScope {
   Prof& p;
   hipStream_t s;
@@ -239,28 +232,8 @@ struct ProfScope {
   }
 };
 
-// dual-tile conv family: one profiler record per kernel of a (possibly two-launch) layer, through ConvArgs::sub_hook
-struct SubProf {
-  Prof* p;
-  hipStream_t s;
-  double flops, bytes;
-  Prof::Rec r;
-  static void hook(void* ctx, int after, int variant, double share) {
-    SubProf* sp = (SubProf*)ctx;
-    if (!sp->p->wants(PC_CONV_F16X3_W4D_0 + variant)) return;
-    if (!after) {
-      sp->r.cls = PC_CONV_F16X3_W4D_0 + variant;
-      sp->r.flops = sp->flops * share;
-      sp->r.bytes = sp->bytes * share;
-      sp->r.a = sp->p->get();
-      sp->r.b = sp->p->get();
-      (void)hipEventRecord(sp->r.a, sp->s);
-    } else {
-      (void)hipEventRecord(sp->r.b, sp->s);
-      sp->p->pending.push_back(sp->r);
-    }
-  }
-};
+// a conv's launches, each bracketed by a ProfScope of its kernel's class and its share of the layer's flops / bytes
+int run_conv_plan(const ConvPlan& pl, hipStream_t s, Prof& prof, double flops, double bytes);
 
 // ---------------------------------------------------------------------------
 // box merging context (also used stand-alone by shf_nms / shf_bbox_vote)

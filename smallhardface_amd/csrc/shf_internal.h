@@ -24,6 +24,17 @@ struct View {
   int coff = 0;     // first channel of this view inside a pixel
 };
 
+// ---- profiler classes: the conv classes are named after a kernel instantiation, like rocprofv3 prints them (kProfNames,
+//      net_forward.cpp); the reduced arithmetic modes book their instantiations under the headline mode's name
+enum ProfClass {
+  PC_CONV_MFMA, PC_CONV_MFMA_7 = 7,   // the eight conv_mfma_f32_kernel instantiations (conv.hip)
+  PC_CONV_F16X3_128, PC_CONV_F16X3_64, PC_CONV_F16X3_64_FUSE1, PC_CONV_F16X3_64_D2, PC_CONV_F16X3_64_D4, PC_CONV_F16X3_128_K1,
+  PC_CONV_F16X3_64_K1, PC_CONV_F16X3_PC,
+  PC_CONV_F16X3_W4D_0, PC_CONV_F16X3_W4D_7 = PC_CONV_F16X3_W4D_0 + 7,   // dual-tile family: + in_split * 4 + (rows == 8) * 2 + (tiles == 1)
+  PC_CONV_F16X3_PCP, PC_CONV_F16X3_K1G, PC_CONV_F16X3_W4D_D2, PC_CONV_F16X3_W4D_D4, PC_CONV_F16X3_H3,
+  PC_CONV_FIRST, PC_CONV_DIRECT, PC_POOL, PC_DECONV, PC_TAIL, PC_MERGE, PC_LAYOUT, PC_H2D, PC_D2H, PC_COUNT
+};
+
 // ---- convolution (stride 1, "same" geometry: pad == dil*(k-1)/2) ------------
 struct ConvArgs {
   View in, out;
@@ -57,41 +68,39 @@ struct ConvArgs {
   const unsigned* in_amax = nullptr;
   unsigned* out_amax = nullptr;
   unsigned* pool_amax = nullptr;
-  // dual-tile family: a layer may take two launches (two tiles per block, then single tiles); the profiler wants one
-  // record per KERNEL: hook(ctx, 0, variant, share) before and hook(ctx, 1, ..) after each, variant = in_split * 4 +
-  // (rows == 8) * 2 + (tiles per block == 1), share = its fraction of the launch's pixel tiles
-  void (*sub_hook)(void* ctx, int after, int variant, double share) = nullptr;
-  void* sub_ctx = nullptr;
 };
 // which kernel class a conv will use: 0 = mfma implicit GEMM, 1 = first-layer direct (NCHW in), 2 = generic direct
 int conv_kernel_class(int Cin, int Cout, int k, int pad, int dil, bool in_nchw);
-int launch_conv_mfma(const ConvArgs& a, hipStream_t s);
-// one grid over up to 16 problems that share the layer (weights/channels) but not H x W
-int launch_conv_mfma_group(const ConvArgs* as, int n, hipStream_t s);
 // first layer: input is the NCHW 'data' blob (B,Cin,H,W), Cin <= 8, Cout % 16 == 0
 int launch_conv_first(const float* in_nchw, const ConvArgs& a, hipStream_t s);
 int launch_conv_direct(const ConvArgs& a, hipStream_t s);
 int conv_init_attributes();
-// split-fp16 (3 x fp16 MFMA, fp32-class accuracy) variant for 3x3 / dilation 1 layers
+// Environment knobs of the split-fp16 kernels (experiments; the defaults are the measured best), read once
+struct ConvKnobs {
+  int w4_mode;      // SHF_F16X3_W4: -1 auto (Cin >= 64), 0 never, 1 always -- which layers take the 4-wave dual-tile family
+  int w4_mt;        // SHF_F16X3_W4_MT: 0 auto, 2 / 4 force 8- / 16-row tiles
+  int w4d_ntile;    // SHF_F16X3_W4D_NTILE: 0 auto (hybrid launches), 1 / 2 force single- / two-tile blocks
+  int pc_tab;       // SHF_F16X3_PC_TAB: 0 = the persistent first pair decodes its tiles one by one (the path launches with more
+                    // than 300 tiles per block take anyway); bit-identical
+  int heads3;       // SHF_F16X3_HEADS3: 1 (default) = the three shared-weight dilated heads as ONE launch (conv_f16x3_h3.h),
+                    // 0 = one launch per head; bit-identical
+  bool pc;          // SHF_F16X3_PC (default on): the fused first pair on the producer / consumer kernel
+  bool pc_persist;  // SHF_F16X3_PC_PERSIST (default on): the fused first pair as one block per CU walking the tiles
+  bool split_act;   // SHF_F16X3_SPLIT_ACT (default on): blobs read only by the dual-tile family are stored split (net_graph.cpp)
+  int cus;
+};
+const ConvKnobs& conv_knobs();
 bool conv_f16x3_eligible(int Cin, int Cout, int k, int pad, int dil);
-bool conv_f16x3_uses_pc();         // fused first pair: producer/consumer kernel (SHF_F16X3_PC=0 disables)
-bool conv_f16x3_pc_persistent();   // ... as one block per CU walking the tiles (SHF_F16X3_PC_PERSIST)
-bool conv_f16x3_uses_w4(int Cin);  // Cout % 128 == 0, 3x3 / dilation 1 layers: the 4-wave dual-tile family (Cin >= 128) or the 8-wave kernel
-int conv_f16x3_w4_mt(const ConvArgs* as, int n);  // 4-wave family: 16-row (4) or 8-row (2) tiles for this launch
-int conv_f16x3_init_attributes();
-int launch_conv_f16x3_group(const ConvArgs* as, int n, hipStream_t s);
+// the shape-only half of plan_conv's choice in the split-fp16 modes: a layer of this shape runs on the dual-tile family
+// (3x3: its DIL 1 / 2 / 4 forms; 1x1: the GEMM kernel), which takes the family's weight pack and reads the split activation
+// format.  `pool`: a pool is fused into the layer; `aligned`: its output views are 16-byte aligned.  What the launch adds:
+// an input under 4 GiB, no fused first layer, a 1x1 not in bf16 mode.
+bool conv_f16x3_family_shape(int Cin, int Cout, int k, int pad, int dil, bool pool, bool aligned);
 size_t split16_conv_weight_halfs(int Cout, int Cin, int k);
 size_t split16h_conv_weight_halfs(int Cout, int Cin, int k);
 size_t split16r_conv_weight_halfs(int Cout, int Cin, int k);
 void pack_conv_weights_split16r(const float* w, int Cout, int Cin, int k, void* dst, bool bf = false);
 float pack_conv_weights_split16h(const float* w, int Cout, int Cin, int k, void* dst, bool bf = false);  // returns 1 / scale
-bool conv_f16x3_group_is_dual(const ConvArgs* as, int n);
-bool conv_f16x3_group_is_dilated_w4(const ConvArgs* as, int n);
-bool conv_f16x3_k1_gemm_shape(int Cin, int Cout);   // a 1x1 layer of this shape runs on the GEMM kernel: the family's pack, split-format input
-bool conv_f16x3_group_is_k1_gemm(const ConvArgs* as, int n);
-// the three shared-weight dilated heads (dilation 1 / 2 / 4, same input, same weights) as ONE launch (conv_f16x3_h3.h; SHF_F16X3_HEADS3)
-bool conv_f16x3_group_is_heads3(const ConvArgs* a1, const ConvArgs* a2, const ConvArgs* a4, int n);
-int launch_conv_f16x3_heads3(const ConvArgs* a1, const ConvArgs* a2, const ConvArgs* a4, int n, hipStream_t s);
 void pack_conv_weights_split16(const float* w, int Cout, int Cin, int k, void* dst, bool bf = false);
 // first layer (64, 27) as the B operand of v_mfma_f32_32x32x16_f16: [n 2][kk 2][hi/lo 2][lane 64][8 halfs], K padded 27 -> 32
 constexpr size_t kFirstConvFragHalfs = 2 * 2 * 2 * 64 * 8;
