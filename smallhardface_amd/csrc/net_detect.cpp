@@ -43,7 +43,8 @@ void shf_net::prepare_unit(const float* data, int data_on_device, int H, int W, 
     d.dev.ensure(d.count() * 4);
     HIP_THROW(hipMemcpyAsync(d.dev.p, data, d.count() * 4, hipMemcpyHostToDevice, st));
   }
-  // (the activation-exponent slots are zero here: zeroed at build, by Net.forward(), and by every pass's tail reset)
+  // (the activation-exponent slots are zero here: zeroed at build, and every pass leaves them zeroed -- a pass with a tail
+  // by the tail's reset kernel, ensure_plain's tail-less one by a reset of its own)
 }
 
 void shf_net::ensure_img_cap(int units_after) {
@@ -138,7 +139,8 @@ int shf_detect_add_level(shf_net* net, const float* data, int data_on_device, in
                          float im_scale, int flip, float thresh) {
   API_BEGIN
   net->prepare_unit(data, data_on_device, H, W, net->stream);
-  net->forward_ops(true, (float)im_h, (float)im_w, im_scale);
+  const float im_info[3] = {(float)im_h, (float)im_w, im_scale};
+  net->run_unit(true, im_info, TAIL_LANE);
   net->blobs[net->data_blob].ext_dev = nullptr;
   append_units(net, &net, 1, &im_w, &im_scale, &flip, thresh, false);
   return 0;
@@ -159,7 +161,7 @@ int shf_detect_add_levels(shf_net* net, int n, shf_net** members, const float* c
   // The member lanes' activations are free as soon as the previous pass over them has run its logits
   // kernels (the rest of a tail works on its own buffers), so with a predecessor head set this pass's
   // convolutions overlap the predecessor's sorts / gathers / appends; the full hand-over is only
-  // awaited before this pass's own tail (below).
+  // awaited before this pass's own tail (run_pass, TAIL_HANDOVER).
   // (With a predecessor head the start only awaits its last convolution; the logits events are awaited
   // right before the first layer that writes a feature map the tails read: every blob owns its buffer.)
   int first_feat_writer = (int)net->layers.size();
@@ -183,149 +185,15 @@ int shf_detect_add_levels(shf_net* net, int n, shf_net** members, const float* c
   // longer unit list comes as several passes into the same list and a later one must not clear an earlier one's flag)
   if (shared && !per_member_lists && net->img_units == 0) HIP_THROW(hipMemsetAsync(net->range_flag.p, 0, 4, cs));
   if (per_member_lists) HIP_THROW(hipMemsetAsync(net->range_flag.p, 0, 4, cs));  // no detect_begin on this path
-  struct FlagScope {  // one range flag per pass: the head's
-    shf_net** mb; int n;
-    FlagScope(shf_net** m, int n_, int* f) : mb(m), n(n_) { for (int i = 0; i < n; ++i) mb[i]->flag_ptr = f; }
-    ~FlagScope() { for (int i = 0; i < n; ++i) mb[i]->flag_ptr = nullptr; }
-  } flag_scope(members, n, (int*)net->range_flag.p);
-  std::vector<ConvArgs> group(n);
-  auto launch_group_conv = [&](size_t li, hipStream_t st) {
-    Layer& L = net->layers[li];
-    double fl = 0, by = 4.0 * L.params[0]->count();
-    for (int m = 0; m < n; ++m) {
-      shf_net* mb = members[m];
-      mb->forward_ops(true, (float)im_h[m], (float)im_w[m], im_scale[m], st, &net->prof, (int)li, &group[m]);
-      fl += conv_flops(mb->layers[li], mb->blobs[mb->layers[li].bottoms[0]].shape,
-                       mb->blobs[mb->layers[li].tops[0]].shape);
-      by += 4.0 * (mb->blobs[mb->layers[li].bottoms[0]].count() + mb->blobs[mb->layers[li].tops[0]].count());
-    }
-    if (group[0].wsplit16 && group[0].img && L.first_src >= 0) {  // conv1_1's work rides in this launch
-      for (int m = 0; m < n; ++m) {
-        shf_net* mb = members[m];
-        const Layer& F = mb->layers[L.first_src];
-        fl += conv_flops(F, mb->blobs[F.bottoms[0]].shape, mb->blobs[F.tops[0]].shape);
-      }
-    }
-    CHECK_RC_LAYER(run_conv_plan(plan_conv(group.data(), n), st, net->prof, fl, by), L.name);
-  };
-  // the three shared-weight dilated heads of every unit as ONE launch (conv_f16x3_h3.h); false: not that shape / mode
-  int heads3_done = -1;
-  std::vector<ConvArgs> g2(n), g4(n);
-  auto launch_group_heads3 = [&](size_t li, hipStream_t st) {
-    Layer& L = net->layers[li];
-    double fl = 0, by = 4.0 * L.params[0]->count();
-    for (int m = 0; m < n; ++m) {
-      shf_net* mb = members[m];
-      mb->forward_ops(true, (float)im_h[m], (float)im_w[m], im_scale[m], st, &net->prof, (int)li, &group[m]);
-      mb->forward_ops(true, (float)im_h[m], (float)im_w[m], im_scale[m], st, &net->prof, L.heads3_d2, &g2[m]);
-      mb->forward_ops(true, (float)im_h[m], (float)im_w[m], im_scale[m], st, &net->prof, L.heads3_d4, &g4[m]);
-      fl += 3.0 * conv_flops(mb->layers[li], mb->blobs[mb->layers[li].bottoms[0]].shape, mb->blobs[mb->layers[li].tops[0]].shape);
-      by += 4.0 * (mb->blobs[mb->layers[li].bottoms[0]].count() + 3.0 * mb->blobs[mb->layers[li].tops[0]].count());
-    }
-    const ConvPlan pl = plan_conv_heads3(group.data(), g2.data(), g4.data(), n);
-    if (pl.nl == 0 && pl.err.empty()) return false;
-    CHECK_RC_LAYER(run_conv_plan(pl, st, net->prof, fl, by), L.name);
-    return true;
-  };
-  for (size_t li = 0; li < net->layers.size(); ++li) {
-    Layer& L = net->layers[li];
-    if (early_start && (int)li == first_feat_writer)
-      for (int m = 0; m < n; ++m)
-        if (members[m]->logits_done) HIP_THROW(hipStreamWaitEvent(net->stream, members[m]->logits_done, 0));
-    if (L.op == OP_SKIP) continue;
-    if (L.op == OP_CONV && L.kclass == 0 && L.heads3_lead >= 0 && heads3_done == L.heads3_lead) {
-      continue;   // written by the dilation-1 sibling's launch
-    } else if (L.op == OP_CONV && L.kclass == 0 && L.heads3_d2 >= 0 && launch_group_heads3(li, cs)) {
-      heads3_done = (int)li;
-    } else if (L.op == OP_CONV && L.kclass == 0) {
-      launch_group_conv(li, cs);
-    } else if (L.op == OP_DECONV && n > 1) {
-      // the units' depthwise up-samplings as one launch (ten serial 5..60-us launches otherwise)
-      View dins[kMaxGroup], douts[kMaxGroup];
-      unsigned* dslots[kMaxGroup];
-      double fl = 0, by = 0;
-      bool ok = true;
-      for (int m = 0; m < n; ++m) {
-        shf_net* mb = members[m];
-        dins[m] = mb->view_of(L.bottoms[0]);
-        douts[m] = mb->view_of(L.tops[0]);
-        dslots[m] = mb->amax_slot(L.tops[0]);
-        ok = ok && dins[m].B == 1;
-        fl += 2.0 * mb->blobs[L.tops[0]].count() * 4;
-        by += 4.0 * (mb->blobs[L.bottoms[0]].count() + mb->blobs[L.tops[0]].count());
-      }
-      if (ok) {
-        ProfScope ps(net->prof, cs, PC_DECONV, fl, by);
-        CHECK_RC(launch_deconv_depthwise_group(dins, douts, n, (const float*)L.params[0]->raw.p,
-                                               L.params.size() > 1 ? (const float*)L.params[1]->raw.p : nullptr, L.k,
-                                               L.stride, L.pad, cs,
-                                               net->conv_mode >= 1 && net->conv_mode != 4 ? (int*)net->range_flag.p : nullptr, dslots));
-      } else {
-        for (int m = 0; m < n; ++m)
-          members[m]->forward_ops(true, (float)im_h[m], (float)im_w[m], im_scale[m], cs, &net->prof, (int)li, nullptr);
-      }
-    } else if (L.op == OP_TAIL) {
-      // The detection tails of all units as ONE launch per stage (counters reset, logits, decode, sort stages,
-      // gather): ~15 launches per image instead of ~100.  Phase 1 (reset + logits) is what reads the head feature
-      // maps; phase 2 works on the members' tail workspaces only.
-      TailArgs targs[kMaxGroup];
-      TailWork* tws[kMaxGroup];
-      float* tb[kMaxGroup];
-      float* tp[kMaxGroup];
-      double tfl = 0, tby = 0;
-      for (int m = 0; m < n; ++m) {
-        shf_net* mb = members[m];
-        if (mb->tail_w_dirty || mb->tail_gen != *mb->wgen) mb->build_tail_weights();
-        targs[m] = mb->tail_args((float)im_h[m], (float)im_w[m], im_scale[m], true);
-        tws[m] = &mb->tw;
-        tb[m] = (float*)mb->blobs[mb->boxes_blob].dev.p;
-        tp[m] = mb->probs_out();
-        const double K = (double)targs[m].h * targs[m].w;
-        tfl += 2.0 * K * mb->tail_A * 6 * mb->tail_Cf;
-        tby += 4.0 * K * (mb->tail_heads * mb->tail_Cf + mb->tail_A * 18);
-      }
-      for (int m = 1; m < n; ++m) targs[m].wcls[0] = targs[0].wcls[0], targs[m].bcls[0] = targs[0].bcls[0];  // lanes hold identical copies
-      if (!net->ev_convs) HIP_THROW(hipEventCreateWithFlags(&net->ev_convs, hipEventDisableTiming));
-      if (shared) {
-        // the members' tail workspaces were last used by the predecessor head's tails (its own stream)
-        if (net->pred && net->pred->ev_mark) HIP_THROW(hipStreamWaitEvent(cs, net->pred->ev_mark, 0));
-        {
-          ProfScope ps(net->prof, cs, PC_TAIL, tfl, tby);
-          CHECK_RC(launch_tail_group(targs, tws, tb, tp, n, cs, nullptr, 1));
-        }
-        // the feature maps are consumed: the conv stream is free for the next image
-        HIP_THROW(hipEventRecord(net->ev_convs, cs));
-        HIP_THROW(hipStreamWaitEvent(net->stream, net->ev_convs, 0));
-      } else {
-        // (every n: a one-unit pass over two heads needs the same hand-over as a ten-unit one)
-        if (net->pred && net->pred->ev_mark) HIP_THROW(hipStreamWaitEvent(net->stream, net->pred->ev_mark, 0));
-        {
-          ProfScope ps(net->prof, net->stream, PC_TAIL, tfl, tby);
-          CHECK_RC(launch_tail_group(targs, tws, tb, tp, n, net->stream, nullptr, 1));
-        }
-        // recorded AFTER phase 1: its reset kernel zeroes the member lanes' activation-exponent slots, which the
-        // successor head's first convolutions (early_start waits for this event only) publish into and read
-        HIP_THROW(hipEventRecord(net->ev_convs, net->stream));
-      }
-      for (int m = 0; m < n; ++m) {  // hand-over mark for passes issued from another head without a pipeline
-        shf_net* mb = members[m];
-        if (shared) {
-          mb->logits_done = net->ev_convs;   // recorded on the conv stream right after the logits launch above
-          continue;
-        }
-        if (!mb->ev_logits) HIP_THROW(hipEventCreateWithFlags(&mb->ev_logits, hipEventDisableTiming));
-        HIP_THROW(hipEventRecord(mb->ev_logits, net->stream));
-        mb->logits_done = mb->ev_logits;
-      }
-      {
-        ProfScope ps(net->prof, net->stream, PC_TAIL, 0, 0);
-        CHECK_RC(launch_tail_group(targs, tws, tb, tp, n, net->stream, nullptr, 2));
-      }
-    } else {
-      for (int m = 0; m < n; ++m)
-        members[m]->forward_ops(true, (float)im_h[m], (float)im_w[m], im_scale[m], cs, &net->prof, (int)li, nullptr);
-    }
-  }
+  Pass p;   // one range flag per pass: the head's
+  p.head = net;
+  p.n = n;
+  for (int m = 0; m < n; ++m) p.u[m] = {members[m], (float)im_h[m], (float)im_w[m], im_scale[m]};
+  p.fused = true;
+  p.s = cs;
+  p.tail = TAIL_HANDOVER;
+  p.wait_logits_at = early_start ? first_feat_writer : -1;
+  run_pass(p);
   for (int m = 0; m < n; ++m) members[m]->blobs[members[m]->data_blob].ext_dev = nullptr;
   // units of different images (per_member_lists): each member keeps its own list
   append_units(net, members, n, im_w, im_scale, flip, thresh, per_member_lists != 0, net->stream, &net->prof);

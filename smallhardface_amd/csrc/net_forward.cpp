@@ -1,4 +1,4 @@
-// Net runtime, part 2: the per-layer executor (forward_ops: one unit, or the arguments of one layer for a grouped launch),
+// Net runtime, part 2: the layer walk (run_pass: one lane's unit, or one grouped pass over the units of several lanes),
 // Net.forward() with its fp32 redo, Blob.data read-back, and the profiler's kernel classes.
 #include "net_internal.h"
 
@@ -40,13 +40,14 @@ int run_conv_plan(const ConvPlan& pl, hipStream_t s, Prof& prof, double flops, d
 }
 }  // namespace shf
 
-double conv_flops(const Layer& L, const std::vector<int>& in, const std::vector<int>& out) {
+static double conv_flops(const Layer& L, const std::vector<int>& in, const std::vector<int>& out) {
   return 2.0 * out[0] * out[2] * out[3] * (double)L.nout * in[1] * L.k * L.k;
 }
 
 // the proposal stage's arguments for the current shapes (also sizes the workspace: pre_nms_topN is shared with the
 // other lanes and may have grown)
-TailArgs shf_net::tail_args(float im_h, float im_w, float im_scale, bool fused_path) {
+TailArgs shf_net::tail_args(float im_h, float im_w, float im_scale, bool materialize) {
+  if (tail_w_dirty || tail_gen != *wgen) build_tail_weights();
   TailArgs t;
   t.A = tail_A; t.heads = tail_heads; t.Cf = tail_Cf;
   for (int i = 0; i < tail_heads; ++i) t.feat[i] = view_of(tail_feat_blobs[i]);
@@ -59,7 +60,7 @@ TailArgs shf_net::tail_args(float im_h, float im_w, float im_scale, bool fused_p
   t.feat_stride = feat_stride;
   t.im_h = im_h; t.im_w = im_w; t.im_scale = im_scale;
   t.min_size = min_size; t.score_thresh = score_thresh; t.pre_nms_topN = pre_nms_topN;
-  if (materialize_tail && (!fused_path || in_net_forward)) {
+  if (materialize) {
     t.cls_prob_reshape_nchw = (float*)blobs[tail_cls_blob].dev.p;
     t.bbox_pred_nchw = (float*)blobs[tail_box_blob].dev.p;
   }
@@ -67,143 +68,251 @@ TailArgs shf_net::tail_args(float im_h, float im_w, float im_scale, bool fused_p
   return t;
 }
 
-void shf_net::forward_ops(bool fused_path, float im_h, float im_w, float im_scale, hipStream_t s_override,
-                          Prof* prof_override, int only_layer, ConvArgs* collect) {
-  if (tail_w_dirty || tail_gen != *wgen) build_tail_weights();
-  hipStream_t st = s_override ? s_override : stream;
-  Prof& pf = prof_override ? *prof_override : prof;
-  int heads3_done = -1;   // index of a dilation-1 head whose launch also wrote its dilation-2 / -4 siblings
-  // the three shared-weight heads of this unit in one launch (conv_f16x3_h3.h): `a` = the dilation-1 layer's arguments
-  auto try_heads3 = [&](int li, const ConvArgs& a, hipStream_t st_, Prof& pf_) {
-    const Layer& L1 = layers[li];
-    ConvArgs a2, a4;
-    forward_ops(fused_path, im_h, im_w, im_scale, st_, &pf_, L1.heads3_d2, &a2);
-    forward_ops(fused_path, im_h, im_w, im_scale, st_, &pf_, L1.heads3_d4, &a4);
-    const ConvPlan pl = plan_conv_heads3(&a, &a2, &a4, 1);
-    if (pl.nl == 0 && pl.err.empty()) return false;
-    const double fl = 3.0 * conv_flops(L1, blobs[L1.bottoms[0]].shape, blobs[L1.tops[0]].shape);
-    const double by = 4.0 * (blobs[L1.bottoms[0]].count() + 3.0 * blobs[L1.tops[0]].count() + L1.params[0]->count());
-    CHECK_RC_LAYER(run_conv_plan(pl, st_, pf_, fl, by), L1.name);
-    return true;
+bool shf_net::split16(const Layer& L) const {
+  const ParamBlob& w = *L.params[0];
+  return conv_mode >= 1 && L.kclass == 0 && (conv_mode == 4 ? w.packed16b.p : w.packed16.p) &&
+         conv_f16x3_eligible(blobs[L.bottoms[0]].shape[1], L.nout, L.k, L.pad, L.dil);
+}
+
+// the fused first pair: conv li stages its halo from the raw image through the first-layer conv that feeds it, which then
+// runs no launch of its own
+bool shf_net::absorbs_first(int li, bool fused) const {
+  const Layer& L = layers[li];
+  if (!fused || L.first_src < 0 || !split16(L)) return false;
+  // bf16 mode has the fused first pair on the producer/consumer kernel only: without its preconditions conv1_1 runs on
+  // its own kernel and this layer as a plain bf16 convolution (the fp16 modes fall back to the 8-wave FUSE1 form instead)
+  const Layer& F = layers[L.first_src];
+  return conv_mode != 4 || (conv_knobs().pc && F.params[0]->first_frag_b.p != nullptr && F.nout == 64 && L.nout == 64);
+}
+
+ConvArgs shf_net::conv_args(int li, bool fused, int* flag) const {
+  const Layer& L = layers[li];
+  const ParamBlob& w = *L.params[0];
+  const bool bf = conv_mode == 4, s16 = split16(L);
+  ConvArgs a;
+  a.in = view_of(L.bottoms[0]);   // (the first-layer kernel takes only its shape from it: its input is the NCHW image)
+  a.out = view_of(L.tops[0]);
+  a.k = L.k; a.dil = L.dil; a.pad = L.pad; a.relu = L.relu;
+  a.bias = L.params.size() > 1 ? (const float*)L.params[1]->raw.p : nullptr;
+  a.wraw = (const float*)w.raw.p;
+  a.wpacked = (const float*)w.packed.p;
+  a.wfirst = (const float*)w.first_t.p;
+  a.wsplit16 = s16 ? (bf ? w.packed16b.p : w.packed16.p) : nullptr;
+  a.wsplit16h = s16 ? (bf ? w.packed16hb.p : w.packed16h.p) : nullptr;
+  a.wsplit16r = s16 ? (bf ? w.packed16rb.p : w.packed16r.p) : nullptr;
+  a.wscale_inv = bf ? 1.f : w.wscale_inv;
+  a.bf16 = bf && s16 ? 1 : 0;
+  // an fp16 mode: every producer of a map that a split-fp16 conv may read guards the fp16 range
+  a.range_flag = fp16_mode() ? flag : nullptr;
+  a.in_amax = amax_slot(L.bottoms[0]);
+  a.out_amax = amax_slot(L.tops[0]);
+  if (fused && L.fuse_pool >= 0) {
+    const int pt = layers[L.fuse_pool].tops[0];
+    a.pool = view_of(pt);
+    a.write_main = L.pool_only ? 0 : 1;
+    a.pool_split = s16 && !bf && blobs[pt].split_fused;
+    a.pool_amax = amax_slot(pt);
+  }
+  if (s16) {  // how many of the three fp16 products this layer forms
+    a.nprod = conv_mode == 1 ? 3 : conv_mode == 2 ? 2 : 1;   // (modes 3 "f16" and 4 "bf16": one product)
+    auto it = sh->layer_products.find(L.name);
+    if (it != sh->layer_products.end()) a.nprod = it->second;
+  }
+  if (fused && s16 && !bf) {   // (bf16 mode keeps fp32 activations in HBM)
+    a.in_split = blobs[L.bottoms[0]].split_fused;
+    a.out_split = blobs[L.tops[0]].split_fused;
+  }
+  if (absorbs_first(li, fused)) {
+    const Layer& F = layers[L.first_src];
+    a.img = nchw_input(F.bottoms[0]);
+    a.w1t = (const float*)F.params[0]->first_t.p;
+    a.w1f = bf ? F.params[0]->first_frag_b.p : F.params[0]->first_frag.p;
+    a.b1 = F.params.size() > 1 ? (const float*)F.params[1]->raw.p : nullptr;
+  }
+  return a;
+}
+
+// the profiler's flops / bytes of layer li on this lane's unit, added to `flops` / `bytes`.  `heads` = 3: the three
+// shared-weight heads of one launch; a conv that absorbs its first-layer producer is credited with that layer's flops too.
+// A conv's weights are read once per launch, however many lanes it covers: run_pass counts them.
+void shf_net::add_cost(int li, bool fused, int heads, double& flops, double& bytes) const {
+  const Layer& L = layers[li];
+  if (L.op == OP_TAIL) {
+    const Blob& f = blobs[tail_feat_blobs[0]];
+    const double K = (double)f.shape[2] * f.shape[3];
+    flops += 2.0 * K * tail_A * 6 * tail_Cf;
+    bytes += 4.0 * K * (tail_heads * tail_Cf + tail_A * 18);
+    return;
+  }
+  const Blob& ib = blobs[L.bottoms[0]];
+  const Blob& ob = blobs[L.tops[0]];
+  bytes += 4.0 * (ib.count() + heads * (double)ob.count());
+  if (L.op == OP_DECONV) flops += 2.0 * ob.count() * 4;
+  if (L.op != OP_CONV) return;
+  flops += heads * conv_flops(L, ib.shape, ob.shape);
+  if (absorbs_first(li, fused)) {
+    const Layer& F = layers[L.first_src];
+    flops += conv_flops(F, blobs[F.bottoms[0]].shape, blobs[F.tops[0]].shape);
+  }
+}
+
+void run_pass(const Pass& p) {
+  shf_net& h = *p.head;
+  const shf_net& n0 = *p.u[0].lane;   // (every lane holds the same graph and parameter tensors)
+  int* const flag = (int*)h.range_flag.p;
+  // the profiler's flops / bytes of layer li on lanes m0 .. m1 - 1 in one launch: each lane's share, a conv's weights once
+  auto cost = [&](int li, int m0, int m1, int heads) {
+    const Layer& L = n0.layers[li];
+    double fl = 0, by = L.op == OP_CONV ? 4.0 * L.params[0]->count() : 0;
+    for (int m = m0; m < m1; ++m) p.u[m].lane->add_cost(li, p.fused, heads, fl, by);
+    return std::make_pair(fl, by);
   };
-  for (size_t li = 0; li < layers.size(); ++li) {
-    if (only_layer >= 0 && (int)li != only_layer) continue;
-    Layer& L = layers[li];
+  ConvArgs a1[kMaxGroup], a2[kMaxGroup], a4[kMaxGroup];
+  int heads3_done = -1;   // index of a dilation-1 head whose launch also wrote its dilation-2 / -4 siblings
+  for (int li = 0; li < (int)n0.layers.size(); ++li) {
+    const Layer& L = n0.layers[li];
+    if (li == p.wait_logits_at)
+      for (int m = 0; m < p.n; ++m)
+        if (p.u[m].lane->logits_done) HIP_THROW(hipStreamWaitEvent(p.s, p.u[m].lane->logits_done, 0));
     switch (L.op) {
       case OP_SKIP: break;
       case OP_CONV: {
-        ConvArgs a;
-        Blob& ib = blobs[L.bottoms[0]];
-        a.out = view_of(L.tops[0]);
-        a.k = L.k; a.dil = L.dil; a.pad = L.pad; a.relu = L.relu;
-        a.bias = L.params.size() > 1 ? (const float*)L.params[1]->raw.p : nullptr;
-        a.wraw = (const float*)L.params[0]->raw.p;
-        a.wpacked = (const float*)L.params[0]->packed.p;
-        a.wfirst = (const float*)L.params[0]->first_t.p;
-        const bool bf = conv_mode == 4;
-        const bool split16 = conv_mode >= 1 && L.kclass == 0 && (bf ? L.params[0]->packed16b.p : L.params[0]->packed16.p) &&
-                             conv_f16x3_eligible(ib.shape[1], L.nout, L.k, L.pad, L.dil);
-        a.wsplit16 = split16 ? (bf ? L.params[0]->packed16b.p : L.params[0]->packed16.p) : nullptr;
-        a.wsplit16h = split16 ? (bf ? L.params[0]->packed16hb.p : L.params[0]->packed16h.p) : nullptr;
-        a.wsplit16r = split16 ? (bf ? L.params[0]->packed16rb.p : L.params[0]->packed16r.p) : nullptr;
-        a.wscale_inv = bf ? 1.f : L.params[0]->wscale_inv;
-        a.bf16 = bf && split16 ? 1 : 0;
-        if (fused_path && L.fuse_pool >= 0) {
-          a.pool = view_of(layers[L.fuse_pool].tops[0]);
-          a.write_main = L.pool_only ? 0 : 1;
-          a.pool_split = split16 && !bf && blobs[layers[L.fuse_pool].tops[0]].split_fused;
+        if (L.first_dst >= 0 && n0.absorbs_first(L.first_dst, p.fused)) break;   // computed inside the next conv's halo staging
+        if (L.heads3_lead >= 0 && heads3_done == L.heads3_lead) break;        // written by the dilation-1 sibling's launch
+        for (int m = 0; m < p.n; ++m) a1[m] = p.u[m].lane->conv_args(li, p.fused, flag);
+        if (L.kclass != 0) {   // the first-layer kernel (NCHW image in) and the generic direct one: a launch per lane
+          for (int m = 0; m < p.n; ++m) {
+            const auto c = cost(li, m, m + 1, 1);
+            ProfScope ps(h.prof, p.s, L.kclass == 1 ? PC_CONV_FIRST : PC_CONV_DIRECT, c.first, c.second);
+            CHECK_RC(L.kclass == 1 ? launch_conv_first(p.u[m].lane->nchw_input(L.bottoms[0]), a1[m], p.s)
+                                   : launch_conv_direct(a1[m], p.s));
+          }
+          break;
         }
-        // split-fp16 mode: every producer of a map that a split-fp16 conv may read guards the fp16 range
-        // (bf16 has fp32's exponent range: no fp16 range guard; amax_slot() is null in that mode)
-        a.range_flag = conv_mode >= 1 && !bf ? (flag_ptr ? flag_ptr : (int*)range_flag.p) : nullptr;
-        a.in_amax = amax_slot(L.bottoms[0]);
-        a.out_amax = amax_slot(L.tops[0]);
-        if (a.pool.p) a.pool_amax = amax_slot(layers[L.fuse_pool].tops[0]);
-        if (split16) {  // how many of the three fp16 products this layer forms
-          a.nprod = conv_mode == 1 ? 3 : conv_mode == 2 ? 2 : 1;   // (modes 3 "f16" and 4 "bf16": one product)
-          auto it = sh->layer_products.find(L.name);
-          if (it != sh->layer_products.end()) a.nprod = it->second;
-        }
-        if (fused_path && split16 && !bf) {   // (bf16 mode keeps fp32 activations in HBM)
-          a.in_split = ib.split_fused;
-          a.out_split = blobs[L.tops[0]].split_fused;
-        }
-        // bf16 mode has the fused first pair on the producer/consumer kernel only: without its preconditions conv1_1
-        // runs on its own kernel and this layer as a plain bf16 convolution (the fp16 modes fall back to the 8-wave
-        // FUSE1 form instead)
-        auto pair_fused = [&](const Layer& F1, const Layer& F2) {
-          if (!bf) return true;
-          return conv_knobs().pc && F1.params[0]->first_frag_b.p != nullptr && F1.nout == 64 && F2.nout == 64;
-        };
-        if (fused_path && split16 && L.first_src >= 0 && pair_fused(layers[L.first_src], L)) {
-          Layer& F = layers[L.first_src];
-          Blob& db = blobs[F.bottoms[0]];
-          a.img = db.ext_dev ? db.ext_dev : (const float*)db.dev.p;
-          a.w1t = (const float*)F.params[0]->first_t.p;
-          a.w1f = bf ? F.params[0]->first_frag_b.p : F.params[0]->first_frag.p;
-          a.b1 = F.params.size() > 1 ? (const float*)F.params[1]->raw.p : nullptr;
-        }
-        if (fused_path && conv_mode >= 1 && L.first_dst >= 0 &&
-            (bf ? layers[L.first_dst].params[0]->packed16b.p : layers[L.first_dst].params[0]->packed16.p) &&
-            pair_fused(L, layers[L.first_dst]))
-          break;  // computed inside the next conv's halo staging
-        const double fl = conv_flops(L, ib.shape, blobs[L.tops[0]].shape);
-        const double by = 4.0 * (ib.count() + blobs[L.tops[0]].count() + L.params[0]->count());
-        if (L.kclass == 1) {
-          a.in.B = ib.shape[0]; a.in.C = ib.shape[1]; a.in.H = ib.shape[2]; a.in.W = ib.shape[3];
-          const float* src = ib.ext_dev ? ib.ext_dev : (const float*)ib.dev.p;
-          ProfScope ps(pf, st, PC_CONV_FIRST, fl, by);
-          CHECK_RC(launch_conv_first(src, a, st));
-        } else {
-          a.in = view_of(L.bottoms[0]);
-          if (L.kclass == 0 && collect) {
-            *collect = a;  // grouped launch: the caller batches this layer over several units
-          } else if (L.kclass == 0 && split16 && L.heads3_lead >= 0 && heads3_done == L.heads3_lead) {
-            // written by the dilation-1 sibling's launch (the three shared-weight heads in one kernel)
-          } else if (L.kclass == 0 && split16 && L.heads3_d2 >= 0 && only_layer < 0 && try_heads3((int)li, a, st, pf)) {
-            heads3_done = (int)li;
-          } else if (L.kclass == 0) {
-            CHECK_RC_LAYER(run_conv_plan(plan_conv(&a, 1), st, pf, fl, by), L.name);
-          } else {
-            ProfScope ps(pf, st, PC_CONV_DIRECT, fl, by);
-            CHECK_RC(launch_conv_direct(a, st));
+        if (L.heads3_d2 >= 0) {   // the three shared-weight heads in one launch (conv_f16x3_h3.h), if shapes and mode allow
+          for (int m = 0; m < p.n; ++m) {
+            a2[m] = p.u[m].lane->conv_args(L.heads3_d2, p.fused, flag);
+            a4[m] = p.u[m].lane->conv_args(L.heads3_d4, p.fused, flag);
+          }
+          const ConvPlan pl = plan_conv_heads3(a1, a2, a4, p.n);
+          if (pl.nl > 0 || !pl.err.empty()) {
+            const auto c = cost(li, 0, p.n, 3);
+            CHECK_RC_LAYER(run_conv_plan(pl, p.s, h.prof, c.first, c.second), L.name);
+            heads3_done = li;
+            break;
           }
         }
+        const auto c = cost(li, 0, p.n, 1);
+        CHECK_RC_LAYER(run_conv_plan(plan_conv(a1, p.n), p.s, h.prof, c.first, c.second), L.name);
         break;
       }
-      case OP_POOL: {
-        if (fused_path && L.fused_into >= 0) break;  // done by the producing conv's epilogue
-        ProfScope ps(pf, st, PC_POOL, 0, 4.0 * (blobs[L.bottoms[0]].count() + blobs[L.tops[0]].count()));
-        CHECK_RC(launch_maxpool(view_of(L.bottoms[0]), view_of(L.tops[0]), L.k, L.stride, L.pad, st));
-        if (amax_slot(L.tops[0]))  // max |pooled| <= max |input|: the bound serves as the pooled blob's activation exponent
-          CHECK_RC(launch_amax_raise(amax_slot(L.tops[0]), amax_slot(L.bottoms[0]), st));
+      case OP_POOL:
+        if (p.fused && L.fused_into >= 0) break;  // done by the producing conv's epilogue
+        for (int m = 0; m < p.n; ++m) {
+          const shf_net& ln = *p.u[m].lane;
+          const auto c = cost(li, m, m + 1, 1);
+          ProfScope ps(h.prof, p.s, PC_POOL, c.first, c.second);
+          CHECK_RC(launch_maxpool(ln.view_of(L.bottoms[0]), ln.view_of(L.tops[0]), L.k, L.stride, L.pad, p.s));
+          if (ln.amax_slot(L.tops[0]))  // max |pooled| <= max |input|: the bound serves as the pooled blob's activation exponent
+            CHECK_RC(launch_amax_raise(ln.amax_slot(L.tops[0]), ln.amax_slot(L.bottoms[0]), p.s));
+        }
         break;
-      }
       case OP_DECONV: {
-        ProfScope ps(pf, st, PC_DECONV, 2.0 * blobs[L.tops[0]].count() * 4,
-                     4.0 * (blobs[L.bottoms[0]].count() + blobs[L.tops[0]].count()));
-        CHECK_RC(launch_deconv_depthwise(view_of(L.bottoms[0]), view_of(L.tops[0]), (const float*)L.params[0]->raw.p,
-                                         L.params.size() > 1 ? (const float*)L.params[1]->raw.p : nullptr, L.k,
-                                         L.stride, L.pad, st,
-                                         conv_mode >= 1 && conv_mode != 4 ? (flag_ptr ? flag_ptr : (int*)range_flag.p) : nullptr,
-                                         amax_slot(L.tops[0])));
+        View in[kMaxGroup], out[kMaxGroup];
+        unsigned* slot[kMaxGroup];
+        bool batch1 = true;
+        for (int m = 0; m < p.n; ++m) {
+          const shf_net& ln = *p.u[m].lane;
+          in[m] = ln.view_of(L.bottoms[0]);
+          out[m] = ln.view_of(L.tops[0]);
+          slot[m] = ln.amax_slot(L.tops[0]);
+          batch1 = batch1 && in[m].B == 1;
+        }
+        const float* w = (const float*)L.params[0]->raw.p;
+        const float* b = L.params.size() > 1 ? (const float*)L.params[1]->raw.p : nullptr;
+        int* const dflag = h.fp16_mode() ? flag : nullptr;
+        if (p.n > 1 && batch1) {   // the units' depthwise up-samplings as one launch (ten serial 5..60-us launches otherwise)
+          const auto c = cost(li, 0, p.n, 1);
+          ProfScope ps(h.prof, p.s, PC_DECONV, c.first, c.second);
+          CHECK_RC(launch_deconv_depthwise_group(in, out, p.n, w, b, L.k, L.stride, L.pad, p.s, dflag, slot));
+          break;
+        }
+        for (int m = 0; m < p.n; ++m) {
+          const auto c = cost(li, m, m + 1, 1);
+          ProfScope ps(h.prof, p.s, PC_DECONV, c.first, c.second);
+          CHECK_RC(launch_deconv_depthwise(in[m], out[m], w, b, L.k, L.stride, L.pad, p.s, dflag, slot[m]));
+        }
         break;
       }
       case OP_TAIL: {
-        if (plain_skip_tail) break;   // (ensure_plain: the intermediates only -- the tail's outputs stay the forward's own)
-        TailArgs t = tail_args(im_h, im_w, im_scale, fused_path);
-        const double K = (double)t.h * t.w;
-        ProfScope ps(pf, st, PC_TAIL, 2.0 * K * tail_A * 6 * tail_Cf,
-                     4.0 * K * (tail_heads * tail_Cf + tail_A * 18));
-        if (fused_path && !ev_logits) HIP_THROW(hipEventCreateWithFlags(&ev_logits, hipEventDisableTiming));
-        CHECK_RC(launch_tail(t, tw, (float*)blobs[boxes_blob].dev.p,
-                             prob_blob >= 0 ? (float*)blobs[prob_blob].dev.p : (float*)tw_rec.p, st,
-                             fused_path ? ev_logits : nullptr, 0));
-        if (fused_path) logits_done = ev_logits;
+        if (p.tail == TAIL_NONE) break;
+        TailArgs t[kMaxGroup];
+        TailWork* tws[kMaxGroup];
+        float *boxes[kMaxGroup], *probs[kMaxGroup];
+        for (int m = 0; m < p.n; ++m) {
+          shf_net& ln = *p.u[m].lane;
+          t[m] = ln.tail_args(p.u[m].im_h, p.u[m].im_w, p.u[m].im_scale, p.materialize);
+          tws[m] = &ln.tw;
+          boxes[m] = (float*)ln.blobs[ln.boxes_blob].dev.p;
+          probs[m] = ln.probs_out();
+        }
+        if (p.tail == TAIL_LANE) {
+          for (int m = 0; m < p.n; ++m) {
+            shf_net& ln = *p.u[m].lane;
+            const auto c = cost(li, m, m + 1, 1);
+            ProfScope ps(h.prof, p.s, PC_TAIL, c.first, c.second);
+            if (p.fused && !ln.ev_logits) HIP_THROW(hipEventCreateWithFlags(&ln.ev_logits, hipEventDisableTiming));
+            CHECK_RC(launch_tail(t[m], ln.tw, boxes[m], probs[m], p.s, p.fused ? ln.ev_logits : nullptr, 0));
+            if (p.fused) ln.logits_done = ln.ev_logits;
+          }
+          break;
+        }
+        // TAIL_HANDOVER: the tails of all units as ONE launch per stage (counters reset, logits, decode, sort stages,
+        // gather): ~15 launches per image instead of ~100.  Phase 1 (reset + logits) is what reads the feature maps and
+        // runs on the layers' stream; phase 2 works on the lanes' tail workspaces only and runs on the head's stream.
+        for (int m = 1; m < p.n; ++m) t[m].wcls[0] = t[0].wcls[0], t[m].bcls[0] = t[0].bcls[0];  // lanes hold identical copies
+        if (!h.ev_convs) HIP_THROW(hipEventCreateWithFlags(&h.ev_convs, hipEventDisableTiming));
+        // the lanes' tail workspaces were last used by the predecessor head's tails (its own stream)
+        if (h.pred && h.pred->ev_mark) HIP_THROW(hipStreamWaitEvent(p.s, h.pred->ev_mark, 0));
+        {
+          const auto c = cost(li, 0, p.n, 1);
+          ProfScope ps(h.prof, p.s, PC_TAIL, c.first, c.second);
+          CHECK_RC(launch_tail_group(t, tws, boxes, probs, p.n, p.s, nullptr, 1));
+        }
+        // recorded AFTER phase 1: its reset kernel zeroes the lanes' activation-exponent slots, which the successor head's
+        // first convolutions (an early start waits for this event only) publish into and read
+        HIP_THROW(hipEventRecord(h.ev_convs, p.s));
+        // a pipelined head's layers ran on the shared conv stream: the feature maps are consumed and ev_convs is every
+        // lane's hand-over mark; otherwise each lane gets its own, for passes issued from another head without a pipeline
+        const bool shared = p.s != h.stream;
+        if (shared) HIP_THROW(hipStreamWaitEvent(h.stream, h.ev_convs, 0));
+        for (int m = 0; m < p.n; ++m) {
+          shf_net& ln = *p.u[m].lane;
+          if (!shared) {
+            if (!ln.ev_logits) HIP_THROW(hipEventCreateWithFlags(&ln.ev_logits, hipEventDisableTiming));
+            HIP_THROW(hipEventRecord(ln.ev_logits, h.stream));
+          }
+          ln.logits_done = shared ? h.ev_convs : ln.ev_logits;
+        }
+        {
+          ProfScope ps(h.prof, h.stream, PC_TAIL, 0, 0);
+          CHECK_RC(launch_tail_group(t, tws, boxes, probs, p.n, h.stream, nullptr, 2));
+        }
         break;
       }
     }
   }
+}
+
+void shf_net::run_unit(bool fused, const float im_info[3], TailStep tail, bool materialize) {
+  Pass p;
+  p.head = this;
+  p.u[0] = {this, im_info[0], im_info[1], im_info[2]};
+  p.fused = fused;
+  p.s = stream;
+  p.tail = tail;
+  p.materialize = materialize;
+  run_pass(p);
 }
 
 // the fused path's kernels behind Net.forward(): a split-fp16 mode, a detector graph whose outputs are the proposal
@@ -237,51 +346,40 @@ void shf_net::forward() {
   memcpy(last_im_info, ii, 12);
   inputs_reshaped = false;
   const bool fast = forward_fast_eligible();
-  struct Scope {   // (forward_ops may throw)
-    bool& f;
-    explicit Scope(bool& f_) : f(f_) { f = true; }
-    ~Scope() { f = false; }
-  };
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    if (conv_mode >= 1) HIP_THROW(hipMemsetAsync(range_flag.p, 0, 4, stream));
-    reset_amax(stream);
-    {
-      Scope sc(in_net_forward);
-      forward_ops(fast, ii[0], ii[1], ii[2]);
-    }
-    plain_stale = fast;
-    int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, flag = 0;
-    {
-      ProfScope ps(prof, stream, PC_D2H, 0, sizeof(cnt) + 4);
+  if (conv_mode >= 1) HIP_THROW(hipMemsetAsync(range_flag.p, 0, 4, stream));
+  reset_amax(stream);
+  run_unit(fast, ii, TAIL_LANE, true);
+  plain_stale = fast;
+  int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, flag = 0;
+  {
+    ProfScope ps(prof, stream, PC_D2H, 0, sizeof(cnt) + 4);
+    if (tail_layer >= 0) HIP_THROW(hipMemcpyAsync(cnt, tw.counters, sizeof(cnt), hipMemcpyDeviceToHost, stream));
+    if (conv_mode >= 1) HIP_THROW(hipMemcpyAsync(&flag, range_flag.p, 4, hipMemcpyDeviceToHost, stream));
+  }
+  HIP_THROW(hipStreamSynchronize(stream));
+  if (flag && conv_mode >= 1) {
+    const int mode_was = conv_mode;
+    // a convolution produced |x| > 65504: fp16(hi) of the split overflowed somewhere downstream.  The reference
+    // computes in fp32 (_caffe.cpp:46-48): redo THIS forward on the exact fp32 matrix-core kernels (per-layer path:
+    // every blob materialised).
+    ++sh->range_fallbacks;
+    conv_mode = 0;
+    try {
+      reset_amax(stream);
+      run_unit(false, ii, TAIL_LANE, true);
+      plain_stale = false;
       if (tail_layer >= 0) HIP_THROW(hipMemcpyAsync(cnt, tw.counters, sizeof(cnt), hipMemcpyDeviceToHost, stream));
-      if (conv_mode >= 1) HIP_THROW(hipMemcpyAsync(&flag, range_flag.p, 4, hipMemcpyDeviceToHost, stream));
-    }
-    HIP_THROW(hipStreamSynchronize(stream));
-    if (flag && conv_mode >= 1) {
-      const int mode_was = conv_mode;
-      // a convolution produced |x| > 65504: fp16(hi) of the split overflowed somewhere downstream.  The reference
-      // computes in fp32 (_caffe.cpp:46-48): redo THIS forward on the exact fp32 matrix-core kernels (per-layer path:
-      // every blob materialised).
-      ++sh->range_fallbacks;
-      conv_mode = 0;
-      try {
-        reset_amax(stream);
-        forward_ops(false, ii[0], ii[1], ii[2]);
-        plain_stale = false;
-        if (tail_layer >= 0) HIP_THROW(hipMemcpyAsync(cnt, tw.counters, sizeof(cnt), hipMemcpyDeviceToHost, stream));
-        HIP_THROW(hipStreamSynchronize(stream));
-      } catch (...) {
-        conv_mode = mode_was;
-        throw;
-      }
+      HIP_THROW(hipStreamSynchronize(stream));
+    } catch (...) {
       conv_mode = mode_was;
+      throw;
     }
-    if (tail_layer >= 0) {
-      const int R = cnt[2];
-      blobs[boxes_blob].shape = {std::max(R, 1), 5};
-      if (prob_blob >= 0) blobs[prob_blob].shape = {R, 2};
-    }
-    break;
+    conv_mode = mode_was;
+  }
+  if (tail_layer >= 0) {
+    const int R = cnt[2];
+    blobs[boxes_blob].shape = {std::max(R, 1), 5};
+    if (prob_blob >= 0) blobs[prob_blob].shape = {R, 2};
   }
   // (tail-fused blobs too: "newer" for them means the tail workspace holds this forward's logits -- read on demand)
   for (size_t i = 0; i < blobs.size(); ++i)
@@ -294,13 +392,9 @@ void shf_net::ensure_plain() {
   if (!plain_stale) return;
   if (inputs_reshaped || (data_blob >= 0 && blobs[data_blob].shape != last_data_shape))
     throw std::runtime_error("an input was reshaped after the last forward(): call forward() before reading intermediate blobs");
-  struct Scope {
-    bool& f;
-    explicit Scope(bool& f_) : f(f_) { f = true; }
-    ~Scope() { f = false; }
-  } sc(plain_skip_tail);
   reset_amax(stream);
-  forward_ops(false, last_im_info[0], last_im_info[1], last_im_info[2]);
+  run_unit(false, last_im_info, TAIL_NONE);
+  reset_amax(stream);   // (a pass without a tail leaves its slots raised: the next pass starts from zero, see prepare_unit)
   HIP_THROW(hipStreamSynchronize(stream));
   plain_stale = false;
 }

@@ -646,7 +646,7 @@ void shf_net::ensure_tail_workspace(size_t total) {
   tw.rec = (float*)tw_rec.p;
   tw.keys = (unsigned long long*)tw_keys.p;
   tw.counters = (int*)tw_counters.p;
-  tw.amax = conv_mode >= 1 && conv_mode != 4 ? (unsigned*)amax_slots.p : nullptr;   // (the tail's reset kernel zeroes the slots for the next pass)
+  tw.amax = fp16_mode() ? (unsigned*)amax_slots.p : nullptr;   // (the tail's reset kernel zeroes the slots for the next pass)
   tw.n_amax = (int)blobs.size();
   tw.cap_anchors = total;
   tw.cap_keys = npad;

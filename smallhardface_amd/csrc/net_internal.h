@@ -1,6 +1,7 @@
-// Internal declarations of the Net runtime (net_graph.cpp: build / shapes / parameters; net_forward.cpp: the per-layer
-// executor and the profiler classes; net_detect.cpp: the fused per-image detection pipeline; net_api.cpp: the rest of the
-// C ABI of include/shf_hip.h).  One struct, four translation units (split in round 5 out of a 2 400-line net.cpp).
+// Internal declarations of the Net runtime (net_graph.cpp: build / shapes / parameters; net_forward.cpp: the layer walk
+// of one lane or a group of lanes (run_pass), Net.forward() and the profiler classes; net_detect.cpp: the fused per-image
+// detection pipeline; net_api.cpp: the rest of the C ABI of include/shf_hip.h).  One struct, four translation units (split
+// in round 5 out of a 2 400-line net.cpp).
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -342,6 +343,13 @@ struct NetShared {
   }
 };
 
+// what a pass of the layer walk does at the proposal layer: the one step its callers differ in
+enum TailStep {
+  TAIL_NONE,      // nothing (ensure_plain: the intermediates only -- the tail's outputs stay the forward's own)
+  TAIL_LANE,      // one phase-0 launch per lane; a fused pass records the lane's ev_logits behind its logits kernel
+  TAIL_HANDOVER   // the grouped pipeline's two phases with their hand-over events (shf_detect_add_levels)
+};
+
 struct shf_net {
   std::shared_ptr<NetShared> sh;
   int& conv_mode;
@@ -384,29 +392,30 @@ struct shf_net {
   shf_net* pred = nullptr;         // shf_net_set_predecessor: the head lane whose image precedes this one's
   bool pipelined = false;   // shf_net_set_pipeline: convolutions go to sh->conv_stream, the rest stays on `stream`
   hipStream_t cstream() { return pipelined && sh->conv_stream ? sh->conv_stream : stream; }
-  int* flag_ptr = nullptr;  // the flag this net's kernels raise: its own, or the head's during a grouped pass
+  // an fp16 mode (split-fp16, f16x2, f16): its producers guard the fp16 range and it keeps activation-exponent slots (bf16
+  // has fp32's exponent range)
+  bool fp16_mode() const { return conv_mode >= 1 && conv_mode != 4; }
   // activation-exponent slots (conv_common.h): one u32 per blob of THIS lane = bit pattern of max |value| of the unit
   // it currently holds; zeroed at the start of every forward / unit, raised by the producers' epilogues, read by the
   // single-accumulator split-fp16 kernels.  Concat members share their owner's slot.
   DevBuf amax_slots;
-  unsigned* amax_slot(int bi) {
-    if (!amax_slots.p || conv_mode < 1 || conv_mode == 4) return nullptr;
+  unsigned* amax_slot(int bi) const {
+    if (!amax_slots.p || !fp16_mode()) return nullptr;
     const int o = blobs[bi].owner >= 0 ? blobs[bi].owner : bi;
     return (unsigned*)amax_slots.p + o;
   }
   void reset_amax(hipStream_t st) {
-    if (conv_mode >= 1 && conv_mode != 4 && amax_slots.p) HIP_THROW(hipMemsetAsync(amax_slots.p, 0, blobs.size() * 4, st));
+    if (fp16_mode() && amax_slots.p) HIP_THROW(hipMemsetAsync(amax_slots.p, 0, blobs.size() * 4, st));
   }
   DevBuf range_flag;  // device int: raised by a split-fp16 conv epilogue that produced |x| > 65504 (fp16 hi overflows)
   TailWork tw;
   DevBuf tw_logits, tw_rec, tw_keys, tw_counters;
-  bool materialize_tail = true;
   // Net.forward() in a split-fp16 mode on a detector graph runs the FUSED path's kernels (fused first pair, pools in the
-  // convolutions' epilogues, split activation format: forward_ops(true) -- the very pass shf_detect_add_level runs, so
-  // lib/test.py's ten net.forward() calls give the detections of the device-resident path bit for bit) and leaves the
-  // intermediate blobs unmaterialised: `plain_stale`.  Reading one of them (Blob.data) then runs the per-layer kernels
-  // once, everything but the proposal tail (ensure_plain), so every name in net.blobs stays readable (pycaffe.py:24-32).
-  bool in_net_forward = false, plain_stale = false, plain_skip_tail = false, inputs_reshaped = false;
+  // convolutions' epilogues, split activation format -- the very pass shf_detect_add_level runs, so lib/test.py's ten
+  // net.forward() calls give the detections of the device-resident path bit for bit) and leaves the intermediate blobs
+  // unmaterialised: `plain_stale`.  Reading one of them (Blob.data) then runs the per-layer kernels once, everything but
+  // the proposal tail (ensure_plain), so every name in net.blobs stays readable (pycaffe.py:24-32).
+  bool plain_stale = false, inputs_reshaped = false;
   float last_im_info[3] = {0.f, 0.f, 1.f};
   bool forward_fast_eligible() const;
   void ensure_plain();
@@ -440,10 +449,10 @@ struct shf_net {
     return (int)blobs.size() - 1;
   }
 
-  View view_of(int bi) {
-    Blob& b = blobs[bi];
+  View view_of(int bi) const {
+    const Blob& b = blobs[bi];
     const int o = b.owner >= 0 ? b.owner : bi;
-    Blob& ob = blobs[o];
+    const Blob& ob = blobs[o];
     View v;
     v.p = (float*)ob.dev.p;
     v.B = b.shape[0]; v.C = b.shape[1]; v.H = b.shape[2]; v.W = b.shape[3];
@@ -451,6 +460,8 @@ struct shf_net {
     v.coff = b.coff;
     return v;
   }
+  // an NCHW net input on the device: bound externally (fused path) or its own buffer
+  const float* nchw_input(int bi) const { return blobs[bi].ext_dev ? blobs[bi].ext_dev : (const float*)blobs[bi].dev.p; }
 
   void build(const std::string& text, const char* caffemodel);
   void infer_shapes();
@@ -458,10 +469,17 @@ struct shf_net {
   void ensure_tail_workspace(size_t total_anchors);
   void commit_params(int li);
   void build_tail_weights();
-  TailArgs tail_args(float im_h, float im_w, float im_scale, bool fused_path);
+  // the proposal stage's arguments (rebuilds the combined weights after a commit, sizes the workspace); `materialize`:
+  // the tail also writes the cls_prob_reshape / bbox_pred blobs (Net.forward())
+  TailArgs tail_args(float im_h, float im_w, float im_scale, bool materialize);
   float* probs_out() { return prob_blob >= 0 ? (float*)blobs[prob_blob].dev.p : (float*)tw_rec.p; }
-  void forward_ops(bool fused_path, float im_h, float im_w, float im_scale, hipStream_t s_override = nullptr,
-                   Prof* prof_override = nullptr, int only_layer = -1, ConvArgs* collect = nullptr);
+  // this lane's part of the layer walk (net_forward.cpp run_pass), none of which launches anything
+  bool split16(const Layer& L) const;          // a split-fp16 kernel runs this conv (kclass 0, packed, eligible shape)
+  bool absorbs_first(int li, bool fused) const;   // conv li computes its first-layer producer in its halo staging
+  ConvArgs conv_args(int li, bool fused, int* flag) const;   // `flag`: the range flag of the pass
+  void add_cost(int li, bool fused, int heads, double& flops, double& bytes) const;
+  // one unit on this lane: its own stream, range flag and profiler
+  void run_unit(bool fused, const float im_info[3], TailStep tail, bool materialize = false);
   void prepare_unit(const float* data, int data_on_device, int H, int W, hipStream_t st);
   void ensure_img_cap(int units_after);
   void forward();
@@ -472,7 +490,20 @@ struct shf_net {
 
 constexpr int kMaxGroup = 16;  // units per grouped pass (conv_common.h MAX_GROUP, tail.hip TG)
 
-double conv_flops(const Layer& L, const std::vector<int>& in, const std::vector<int>& out);   // net_forward.cpp
+// One pass of the layer walk (net_forward.cpp run_pass): the layers of one net over the units of 1..16 of its lanes, every
+// convolution as ONE launch over the group.  Everything a layer needs comes with the pass.
+struct Pass {
+  shf_net* head;   // its range flag and profiler serve the pass; TAIL_HANDOVER: its stream runs the tails, it owns ev_convs
+  int n = 1;
+  struct Unit { shf_net* lane; float im_h, im_w, im_scale; } u[kMaxGroup];   // a lane and its unit's im_info
+  bool fused;   // the fused path's kernels (fused first pair, pools in the epilogues, split activations); false: per layer
+  hipStream_t s;           // the layers' stream
+  TailStep tail;
+  bool materialize = false;  // TAIL_LANE: the tail also writes the cls_prob_reshape / bbox_pred blobs (Net.forward())
+  int wait_logits_at = -1;   // before this layer the stream waits for every lane's logits_done (the grouped early start)
+};
+void run_pass(const Pass& p);
+
 // net_detect.cpp: append a group of finished units to `net`'s image list (or, per_member, to each member's own) in ONE launch
 void append_units(shf_net* net, shf_net* const* srcs, int n, const int* im_w, const float* im_scale, const int* flip,
                   float thresh, bool per_member, hipStream_t st = nullptr, Prof* pf = nullptr);

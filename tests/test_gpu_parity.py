@@ -365,6 +365,17 @@ def test_every_blob_is_readable_after_forward(dd, conv_mode):
             gnet.blobs["conv3_3"].data
         H.run_both(gnet, onet, data2, np.array([[48, 64, 1.0]], np.float32))
         assert H.rel_err(gnet.blobs["conv3_3"].data, onet.blobs["conv3_3"].data) < ACT_TOL
+        # that read-back is a pass without the proposal tail, whose reset kernel zeroes the lane's activation-exponent
+        # slots for the next pass: it must leave them zeroed too.  After a forward of 2^6 x larger activations (still far
+        # inside the fp16 range: no fp32 redo) and a read of an intermediate, a fused pass on the same net gives the
+        # detections of a fresh lane, not ones whose exponents come from the earlier image.
+        from smallhardface_amd import test as T
+        redos = gnet.range_fallbacks
+        gnet.forward(data=data2 * 64.0, im_info=np.array([[48, 64, 1.0]], np.float32))
+        assert gnet.range_fallbacks == redos
+        gnet.blobs["conv3_3"].data
+        unit = [(data2, data2.shape[2], data2.shape[3], 48, 64, 1.0, False)]
+        np.testing.assert_array_equal(T.detect_fused(gnet, unit), T.detect_fused(gnet.clone(), unit))
 
 
 @pytest.mark.parametrize("bad,msg", [
