@@ -198,8 +198,11 @@ def test_conv_identity_is_transpose_detecting():
     (256, 128, 33, 47, True, False),    # pooled AND un-pooled output both read (the conv4_3 case)
 ])
 def test_four_wave_kernel_fused_pool(cin, cout, h, w, relu, consumer):
-    """The register epilogue of the 4-wave kernels (conv_epilogue_regs): MFMA as D[cout][pixel], half-wave quad exchange,
-    2x2/2 max-pool as a DPP quad max with Caffe's clipped windows on odd maps -- against the oracle's conv + pool."""
+    """A convolution of the 4-wave kernels' shape class followed by a 2x2/2 max-pool on odd maps, with and without ReLU,
+    against the oracle's conv + pool.  This graph has no proposal tail, so Net.forward() runs the PER-LAYER forms: the
+    convolution's register epilogue (conv_epilogue_regs: MFMA as D[cout][pixel], half-wave quad exchange) without a pool,
+    then the stand-alone maxpool_kernel with Caffe's clipped windows -- the profile says so.  The pool folded into the
+    epilogue (a DPP quad max) is held to the oracle in tests/test_gpu_fused_forms.py."""
     pool = 'layer { name: "p" type: "Pooling" bottom: "c1" top: "p" pooling_param { pool: MAX kernel_size: 2 stride: 2 } }\n'
     txt = H.single_layer_net(conv_layer("c0", "data", cin, 3, 1) + conv_layer("c1", "c0", cout, 3, 1, 1, relu) + pool +
                              conv_layer("c2", "p", 64, 1, 0) + ("" if consumer else conv_layer("c3", "c1", 64, 1, 0)), 3, h, w)
@@ -209,7 +212,12 @@ def test_four_wave_kernel_fused_pool(cin, cout, h, w, relu, consumer):
         onet.params[name][1][...] = rng.normal(0, 0.5, onet.params[name][1].shape).astype(np.float32)
     H.load_params(gnet, onet.params)
     data = rng.normal(0, 1, (1, 3, h, w)).astype(np.float32)
+    gnet.prof_enable(True)
+    gnet.prof_reset()
     go, oo = H.run_both(gnet, onet, data, np.array([[h, w, 1]], np.float32))
+    prof = gnet.prof_read()
+    gnet.prof_enable(False)
+    assert prof["maxpool_kernel"]["launches"] == 1, "the pool of this graph runs as a kernel of its own"
     for name in ("p", "c2") + (() if consumer else ("c1", "c3")):
         a, b = gnet.blobs[name].data, onet.blobs[name].data
         assert a.shape == b.shape, name
