@@ -207,6 +207,27 @@ int shf_generate_anchors(int base_size, const double* ratios, int n_ratios, cons
                          int n_scales, const double* shifts, int n_shifts, const double* strides,
                          double* out, int cap_rows);
 
+/* image_eval + img_pr_info + dataset_pr_info   lib/wider_eval_tools/wider_eval.py:62-130, for all images and up to 8
+ * settings (easy / medium / hard subsets of the same ground truth) in one call, on the current device.
+ *   pred5     (N,5) x, y, w, h, score; the rows of image i are pred_off[i] .. pred_off[i+1] (n_images + 1 offsets) and
+ *             score-descending; the scores are compared as given (the caller normalises them, wider_eval.py:42-59)
+ *   gt4       (G,4) x, y, w, h with gt_off alike; counted (n_settings, G): 1 where the box belongs to the setting's subset
+ *   thresh    n_thresh score thresholds as the caller computes them (1 - (t + 1) / 1000, wider_eval.py:109)
+ *   totals    (n_settings, n_thresh, 2): over all images, the number of proposals and of subset faces found with
+ *             score >= thresh -- exact integers, the sums dataset_pr_info forms
+ *   hits_out / proposal_out   (n_settings, N) each, or NULL (diagnostics, tests): per detection the number of subset
+ *             faces found so far in its image, and 0 where it sits on a face outside the subset (proposal_list = -1)
+ * A detection is attributed to the FIRST ground-truth box with the largest IoU (fp64, +1 pixel convention, zero-union
+ * guard :62-79), with mimic_eval_bug != 0 the largest floor(IoU + 0.5) (:92-95), and matched when that value is
+ * >= iou_thresh.  All buffers are host memory.  Images without detections or without ground truth contribute nothing.
+ * Refused with a message, before anything is allocated or launched: negative or non-monotone offsets, iou_thresh outside
+ * (0, 1], n_settings outside 1..8, n_settings x N or n_settings x G of 2^31 rows or more, an image with more than
+ * 65 536 ground-truth boxes (one lane walks them all).  Non-finite boxes or scores are the caller's to keep away
+ * (numpy's arg-max of NaN is not reproduced). */
+int shf_wider_eval_counts(const double* pred5, const int* pred_off, const double* gt4, const int* gt_off,
+                          const uint8_t* counted, int n_images, int n_settings, double iou_thresh, int mimic_eval_bug,
+                          const double* thresh, int n_thresh, long long* totals, int* hits_out, uint8_t* proposal_out);
+
 /* Read parameter blob `idx` of layer `layer` from a binary .caffemodel (the reader behind
  * shf_net_create's weight loading; caffe.proto NetParameter.layer=100 / BlobProto data=5).
  * Returns the element count (out may be NULL to query), fills dims/ndim.  Needs no GPU. */

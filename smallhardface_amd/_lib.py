@@ -112,6 +112,8 @@ def _declare(lib):
         "shf_caffemodel_read_blob": (ci, [C.c_char_p, C.c_char_p, ci, fp, ci, ip, ip]),
         "shf_nms": (ci, [fp, ci, cf, ci, C.POINTER(C.c_int32), ip]),
         "shf_bbox_vote": (ci, [fp, ci, cf, dp, ci, ip]),
+        "shf_wider_eval_counts": (ci, [dp, ip, dp, ip, C.POINTER(C.c_uint8), ci, ci, C.c_double, ci, dp, ci,
+                                       C.POINTER(C.c_longlong), ip, C.POINTER(C.c_uint8)]),
         "shf_generate_anchors": (ci, [ci, dp, ci, dp, ci, dp, ci, dp, dp, ci]),
         "shf_prof_enable": (ci, [vp, ci]),
         "shf_prof_only": (ci, [vp, ci]),

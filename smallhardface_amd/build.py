@@ -3,8 +3,8 @@
     python -m smallhardface_amd.build          # incremental
     python -m smallhardface_amd.build --force
 
-hipcc cross-compiles without a GPU.  The box-arithmetic kernels (tail.hip, merge.hip)
-and the image resize (pre.hip) are built with -ffp-contract=off so IoU / decode round like numpy and devIoU.
+hipcc cross-compiles without a GPU.  The box-arithmetic kernels (tail.hip, merge.hip,
+eval.hip) and the image resize (pre.hip) are built with -ffp-contract=off so IoU / decode round like numpy and devIoU.
 """
 import os
 import subprocess
@@ -24,6 +24,7 @@ SOURCES = [
     ("tail.hip", ["-ffp-contract=off"]),
     ("merge.hip", ["-ffp-contract=off"]),
     ("pre.hip", ["-ffp-contract=off"]),
+    ("eval.hip", ["-ffp-contract=off"]),
     ("calib.hip", []),
     ("net_graph.cpp", []),
     ("net_forward.cpp", []),
@@ -31,7 +32,7 @@ SOURCES = [
     ("net_api.cpp", []),
 ]
 HEADERS = ["shf_internal.h", "conv_common.h", "conv_f16x3_types.h", "conv_f16x3_8w.h", "conv_f16x3_w4d.h", "conv_f16x3_pc.h", "conv_f16x3_k1.h", "conv_f16x3_h3.h",
-           "proto_text.h", "net_internal.h", os.path.join("..", "..", "include", "shf_hip.h")]
+           "proto_text.h", "net_internal.h", "eval.h", os.path.join("..", "..", "include", "shf_hip.h")]
 
 
 def _newer(target, deps):

@@ -1,0 +1,25 @@
+// Launchers of the WIDER evaluation kernels (eval.hip), called by shf_wider_eval_counts (net_api.cpp).
+#pragma once
+#include "shf_internal.h"
+
+namespace shf {
+
+// A lane of the match kernel walks all the ground-truth boxes of its image one after the other: the cap bounds how long one
+// wave can run (WIDER's largest image has under 2 000 faces).
+constexpr int kEvalMaxGtPerImage = 65536;
+// gt4 (G,4) x-y-w-h -> gt5 (G,5) x1-y1-x2-y2-area; first[g] = INT_MAX
+int launch_eval_prep(const double* gt4, int G, double* gt5, int* first, hipStream_t s);
+// tile k covers detections tile_start[k] .. + 63 of image tile_img[k]; match[h] = matched box (global index) or -1,
+// first[g] = the earliest detection matched to box g
+int launch_eval_match(const double* pred5, const int* pred_off, const int* gt_off, const double* gt5, const int* tile_img,
+                      const int* tile_start, int n_tiles, double iou_thresh, int mimic_eval_bug, int* match, int* first,
+                      hipStream_t s);
+// hits / cum_prop (S,N): inclusive scans per (setting, image); proposal (S,N) may be null
+int launch_eval_counts(const int* pred_off, const int* match, const int* first, const uint8_t* counted, int n_images,
+                       int n_settings, int N, int G, int* hits, int* cum_prop, uint8_t* proposal, hipStream_t s);
+// totals (S,T,2) must be zero on entry
+int launch_eval_sweep(const double* pred5, const int* pred_off, const int* gt_off, const int* hits, const int* cum_prop,
+                      int n_images, int n_settings, int N, const double* thresh, int T, unsigned long long* totals,
+                      hipStream_t s);
+
+}  // namespace shf

@@ -1,0 +1,176 @@
+// WIDER FACE evaluation on the device: the per-image matching and the threshold sweep of
+//   image_eval / img_pr_info / dataset_pr_info    lib/wider_eval_tools/wider_eval.py:62-130
+// in the parallel form of DESIGN.md 4.11 (tests/wider_eval_cases.py: parallel_counts is its numpy restatement):
+//   match   the ground-truth box a detection is attributed to is the first arg-max of its IoU row (of floor(IoU + 0.5)
+//           under mimic_eval_bug); it depends on the boxes alone, not on the detections before it and not on the setting.
+//           One lane per detection walks the image's boxes in index order and keeps a strictly greater key, so the
+//           first index wins without any cross-lane reduction; an atomic min leaves first[g], the earliest detection
+//           matched to box g.
+//   counts  per (image, setting): proposal[h] and flag[h] (h is the first hit of a box of the subset) from match, first
+//           and the subset mask; inclusive wave scans with a carry give hits[] and the running number of proposals.
+//   sweep   per (image, setting): per threshold a binary search in the score-descending detections, then two 64-bit
+//           vector atomic adds into the (S, T, 2) totals.  Integer sums: exact in any order.
+// All box arithmetic is fp64 in the operation order of _overlaps(); compiled with -ffp-contract=off, so every add, multiply
+// and divide rounds like numpy's.
+#include "eval.h"
+
+namespace shf {
+
+typedef unsigned long long u64;
+
+static inline unsigned eval_grid_for(long long n, int block = 256) {
+  long long g = (n + block - 1) / block;
+  if (g > 256 * 16) g = 256 * 16;
+  if (g < 1) g = 1;
+  return (unsigned)g;
+}
+
+// every ground-truth box once: (x, y, w, h) -> x1, y1, x2 = w + x, y2 = h + y and its +1-pixel area, as image_counts and
+// _overlaps form them; first[] starts at "no detection"
+__global__ void eval_prep_kernel(const double* __restrict__ gt4, int G, double* __restrict__ gt5, int* __restrict__ first) {
+  for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < G; g += gridDim.x * blockDim.x) {
+    const double x1 = gt4[(size_t)g * 4 + 0], y1 = gt4[(size_t)g * 4 + 1];
+    const double x2 = gt4[(size_t)g * 4 + 2] + x1, y2 = gt4[(size_t)g * 4 + 3] + y1;
+    double* o = gt5 + (size_t)g * 5;
+    o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2;
+    o[4] = (x2 - x1 + 1) * (y2 - y1 + 1);
+    first[g] = 0x7FFFFFFF;
+  }
+}
+
+// one wave per tile of 64 detections of one image; lane = detection.  The box index of the loop is wave-uniform: every
+// lane reads the same converted box.  match[h] = global index of the box detection h is matched to, or -1.
+__global__ __launch_bounds__(64) void eval_match_kernel(const double* __restrict__ pred5, const int* __restrict__ pred_off,
+                                                        const int* __restrict__ gt_off, const double* __restrict__ gt5,
+                                                        const int* __restrict__ tile_img, const int* __restrict__ tile_start,
+                                                        double iou_thresh, int mimic_eval_bug, int* __restrict__ match,
+                                                        int* __restrict__ first) {
+  const int img = tile_img[blockIdx.x];
+  const int h = tile_start[blockIdx.x] + (int)threadIdx.x;
+  if (h >= pred_off[img + 1]) return;
+  const int g0 = gt_off[img], g1 = gt_off[img + 1];
+  const double* p = pred5 + (size_t)h * 5;
+  const double b0 = p[0], b1 = p[1], b2 = p[2] + b0, b3 = p[3] + b1;
+  const double area_det = (b2 - b0 + 1) * (b3 - b1 + 1);
+  double best = 0;
+  int idx = -1;
+  for (int g = g0; g < g1; ++g) {
+    const double* q = gt5 + (size_t)g * 5;
+    const double iw = (q[2] < b2 ? q[2] : b2) - (q[0] > b0 ? q[0] : b0) + 1;
+    const double ih = (q[3] < b3 ? q[3] : b3) - (q[1] > b1 ? q[1] : b1) + 1;
+    const double inter = iw * ih;
+    double uni = q[4] + area_det - inter;
+    if (uni == 0) uni = INFINITY;
+    double o = inter / uni;
+    if (iw <= 0 || ih <= 0) o = 0;
+    if (mimic_eval_bug) o = floor(o + 0.5);
+    if (idx < 0 || o > best) { best = o; idx = g; }   // np.argmax: the first of equal keys
+  }
+  const bool matched = idx >= 0 && best >= iou_thresh;
+  match[h] = matched ? idx : -1;
+  if (matched) atomicMin(first + idx, h);
+}
+
+__device__ __forceinline__ int wave_inclusive_scan(int v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+
+// one wave per (image, setting): segmented inclusive scans over the image's detections, 64 at a time with a carry
+__global__ __launch_bounds__(64) void eval_counts_kernel(const int* __restrict__ pred_off, const int* __restrict__ match,
+                                                         const int* __restrict__ first, const uint8_t* __restrict__ counted,
+                                                         int N, int G, int* __restrict__ hits, int* __restrict__ cum_prop,
+                                                         uint8_t* __restrict__ proposal) {
+  const int img = blockIdx.x, s = blockIdx.y, lane = threadIdx.x;
+  const int h0 = pred_off[img], h1 = pred_off[img + 1];
+  const uint8_t* cnt = counted + (size_t)s * G;
+  const size_t row = (size_t)s * N;
+  int carry_hits = 0, carry_prop = 0;
+  for (int base = h0; base < h1; base += 64) {
+    const int h = base + lane;
+    int flag = 0, prop = 0;
+    if (h < h1) {
+      const int m = match[h];
+      const bool in_subset = m >= 0 && cnt[m] != 0;
+      flag = in_subset && first[m] == h;
+      prop = !(m >= 0 && !in_subset);
+    }
+    const int sf = wave_inclusive_scan(flag, lane), sp = wave_inclusive_scan(prop, lane);
+    if (h < h1) {
+      hits[row + h] = carry_hits + sf;
+      cum_prop[row + h] = carry_prop + sp;
+      if (proposal) proposal[row + h] = (uint8_t)prop;
+    }
+    carry_hits += __shfl(sf, 63, 64);
+    carry_prop += __shfl(sp, 63, 64);
+  }
+}
+
+// one block per (image, setting), a thread per threshold: cnt = number of detections with score >= thresh (the scores fall),
+// then info = (cum_prop[cnt - 1], hits[cnt - 1]) when cnt > 0 (image_pr_info)
+__global__ __launch_bounds__(256) void eval_sweep_kernel(const double* __restrict__ pred5, const int* __restrict__ pred_off,
+                                                         const int* __restrict__ gt_off, const int* __restrict__ hits,
+                                                         const int* __restrict__ cum_prop, int N,
+                                                         const double* __restrict__ thresh, int T, u64* __restrict__ totals) {
+  const int img = blockIdx.x, s = blockIdx.y;
+  const int h0 = pred_off[img], n = pred_off[img + 1] - h0;
+  if (n == 0 || gt_off[img + 1] == gt_off[img]) return;   // (evaluate_setting skips such an image)
+  const double* score = pred5 + (size_t)h0 * 5 + 4;
+  const size_t row = (size_t)s * N + h0;
+  for (int t = threadIdx.x; t < T; t += blockDim.x) {
+    const double thr = thresh[t];
+    int lo = 0, hi = n;
+    while (lo < hi) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (score[(size_t)mid * 5] >= thr) lo = mid + 1; else hi = mid;
+    }
+    if (lo > 0) {
+      const int np = cum_prop[row + lo - 1], nh = hits[row + lo - 1];
+      u64* o = totals + ((size_t)s * T + t) * 2;
+      if (np) atomicAdd(o, (u64)np);
+      if (nh) atomicAdd(o + 1, (u64)nh);
+    }
+  }
+}
+
+int launch_eval_prep(const double* gt4, int G, double* gt5, int* first, hipStream_t s) {
+  if (G == 0) return 0;
+  hipLaunchKernelGGL(eval_prep_kernel, dim3(eval_grid_for(G)), dim3(256), 0, s, gt4, G, gt5, first);
+  SHF_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int launch_eval_match(const double* pred5, const int* pred_off, const int* gt_off, const double* gt5, const int* tile_img,
+                      const int* tile_start, int n_tiles, double iou_thresh, int mimic_eval_bug, int* match, int* first,
+                      hipStream_t s) {
+  if (n_tiles == 0) return 0;
+  hipLaunchKernelGGL(eval_match_kernel, dim3((unsigned)n_tiles), dim3(64), 0, s, pred5, pred_off, gt_off, gt5, tile_img,
+                     tile_start, iou_thresh, mimic_eval_bug, match, first);
+  SHF_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int launch_eval_counts(const int* pred_off, const int* match, const int* first, const uint8_t* counted, int n_images,
+                       int n_settings, int N, int G, int* hits, int* cum_prop, uint8_t* proposal, hipStream_t s) {
+  if (n_images == 0 || N == 0) return 0;
+  hipLaunchKernelGGL(eval_counts_kernel, dim3((unsigned)n_images, (unsigned)n_settings), dim3(64), 0, s, pred_off, match,
+                     first, counted, N, G, hits, cum_prop, proposal);
+  SHF_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int launch_eval_sweep(const double* pred5, const int* pred_off, const int* gt_off, const int* hits, const int* cum_prop,
+                      int n_images, int n_settings, int N, const double* thresh, int T, unsigned long long* totals,
+                      hipStream_t s) {
+  if (n_images == 0 || N == 0) return 0;
+  hipLaunchKernelGGL(eval_sweep_kernel, dim3((unsigned)n_images, (unsigned)n_settings), dim3(256), 0, s, pred5, pred_off,
+                     gt_off, hits, cum_prop, N, thresh, T, totals);
+  SHF_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+}  // namespace shf

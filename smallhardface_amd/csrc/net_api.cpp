@@ -13,6 +13,7 @@
 //     one fused device-side tail (no D2H, no Python re-entry);
 //   * buffers are grow-only and shape changes re-plan nothing but pointers/sizes.
 #include "net_internal.h"
+#include "eval.h"
 
 namespace shf {
 thread_local std::string g_err;
@@ -24,6 +25,33 @@ static std::mutex g_box_mu;
 static MergeCtx* g_box_ctx = nullptr;
 static hipStream_t g_box_stream = nullptr;
 static DevBuf* g_box_in = nullptr;
+
+// device memory and stream of ONE shf_wider_eval_counts call, on the device current at the call: nothing outlives it
+namespace {
+struct CallBuf {
+  void* p = nullptr;
+  void alloc(size_t bytes) { HIP_THROW(hipMalloc(&p, bytes ? bytes : 1)); }
+  template <typename T> T* as() const { return (T*)p; }
+  ~CallBuf() { if (p) (void)hipFree(p); }
+  CallBuf() = default;
+  CallBuf(const CallBuf&) = delete;
+  CallBuf& operator=(const CallBuf&) = delete;
+};
+struct CallStream {
+  hipStream_t s = nullptr;
+  void create() { HIP_THROW(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+  ~CallStream() { if (s) (void)hipStreamDestroy(s); }
+};
+
+// offsets of n_images segments: 0 when they are non-negative and non-decreasing, else the message is set
+int refuse_offsets(const int* off, int n_images, const char* name) {
+  for (int i = 0; i <= n_images; ++i) {
+    if (off[i] < 0) { set_error(std::string("wider_eval_counts: negative offset in ") + name); return -1; }
+    if (i && off[i] < off[i - 1]) { set_error(std::string("wider_eval_counts: non-monotone offsets in ") + name); return -1; }
+  }
+  return 0;
+}
+}  // namespace
 
 extern "C" {
 
@@ -359,6 +387,83 @@ int shf_bbox_vote(const float* dets5, int n, float thresh, double* out5, int cap
   g_box_in->ensure((size_t)n * 5 * 4);
   HIP_THROW(hipMemcpyAsync(g_box_in->p, dets5, (size_t)n * 5 * 4, hipMemcpyHostToDevice, g_box_stream));
   return g_box_ctx->run((const float*)g_box_in->p, n, 0, thresh, out5, cap, n_out, nullptr, g_box_stream);
+  API_END(-1)
+}
+
+int shf_wider_eval_counts(const double* pred5, const int* pred_off, const double* gt4, const int* gt_off,
+                          const uint8_t* counted, int n_images, int n_settings, double iou_thresh, int mimic_eval_bug,
+                          const double* thresh, int n_thresh, long long* totals, int* hits_out, uint8_t* proposal_out) {
+  API_BEGIN
+  // ---- refusals: argument checks only, before anything is allocated or launched
+  if (!pred_off || !gt_off || !thresh || !totals || n_images < 0)
+    throw std::runtime_error("wider_eval_counts: null argument or negative n_images");
+  if (n_settings < 1 || n_settings > 8) throw std::runtime_error("wider_eval_counts: n_settings must be 1..8");
+  if (!(iou_thresh > 0.0 && iou_thresh <= 1.0)) throw std::runtime_error("wider_eval_counts: iou_thresh must be in (0, 1]");
+  if (n_thresh < 1 || n_thresh > (1 << 20)) throw std::runtime_error("wider_eval_counts: n_thresh must be 1..2^20");
+  CHECK_RC(refuse_offsets(pred_off, n_images, "pred_off"));
+  CHECK_RC(refuse_offsets(gt_off, n_images, "gt_off"));
+  const long long N = pred_off[n_images], G = gt_off[n_images];
+  if (N * n_settings >= (1ll << 31) || G * n_settings >= (1ll << 31))
+    throw std::runtime_error("wider_eval_counts: n_settings x rows reaches 2^31 (detections " + std::to_string(N) +
+                             ", ground-truth boxes " + std::to_string(G) + ")");
+  long long n_tiles = 0;
+  for (int i = 0; i < n_images; ++i) {
+    const int g = gt_off[i + 1] - gt_off[i];
+    if (g > kEvalMaxGtPerImage)
+      throw std::runtime_error("wider_eval_counts: image " + std::to_string(i) + " has " + std::to_string(g) +
+                               " ground-truth boxes, the cap per image is " + std::to_string(kEvalMaxGtPerImage));
+    n_tiles += ((long long)pred_off[i + 1] - pred_off[i] + 63) / 64;
+  }
+  if ((N && !pred5) || (G && (!gt4 || !counted))) throw std::runtime_error("wider_eval_counts: null box array");
+  const size_t S = (size_t)n_settings, T = (size_t)n_thresh;
+  memset(totals, 0, S * T * 2 * sizeof(long long));
+  if (N == 0 || G == 0) {   // nothing can be matched: every detection is a proposal of an image that is skipped
+    if (hits_out) memset(hits_out, 0, S * (size_t)N * sizeof(int));
+    if (proposal_out) memset(proposal_out, 1, S * (size_t)N);
+    return 0;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    throw std::runtime_error("no HIP device available: wider_eval_counts has no CPU fallback");
+
+  std::vector<int> tile_img((size_t)n_tiles), tile_start((size_t)n_tiles);
+  size_t k = 0;
+  for (int i = 0; i < n_images; ++i)
+    for (int h = pred_off[i]; h < pred_off[i + 1]; h += 64) { tile_img[k] = i; tile_start[k++] = h; }
+
+  CallStream st;
+  st.create();
+  CallBuf d_pred, d_poff, d_gt4, d_goff, d_counted, d_thresh, d_tiles, d_gt5, d_first, d_match, d_hits, d_cprop, d_prop, d_tot;
+  const size_t offb = ((size_t)n_images + 1) * sizeof(int);
+  d_pred.alloc((size_t)N * 5 * 8); d_poff.alloc(offb); d_gt4.alloc((size_t)G * 4 * 8); d_goff.alloc(offb);
+  d_counted.alloc(S * (size_t)G); d_thresh.alloc(T * 8); d_tiles.alloc((size_t)n_tiles * 2 * sizeof(int));
+  d_gt5.alloc((size_t)G * 5 * 8); d_first.alloc((size_t)G * sizeof(int)); d_match.alloc((size_t)N * sizeof(int));
+  d_hits.alloc(S * (size_t)N * sizeof(int)); d_cprop.alloc(S * (size_t)N * sizeof(int));
+  if (proposal_out) d_prop.alloc(S * (size_t)N);
+  d_tot.alloc(S * T * 2 * 8);
+  auto up = [&](CallBuf& b, const void* src, size_t bytes) {
+    HIP_THROW(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st.s));
+  };
+  up(d_pred, pred5, (size_t)N * 5 * 8); up(d_poff, pred_off, offb); up(d_gt4, gt4, (size_t)G * 4 * 8); up(d_goff, gt_off, offb);
+  up(d_counted, counted, S * (size_t)G); up(d_thresh, thresh, T * 8);
+  up(d_tiles, tile_img.data(), (size_t)n_tiles * sizeof(int));
+  HIP_THROW(hipMemcpyAsync(d_tiles.as<int>() + n_tiles, tile_start.data(), (size_t)n_tiles * sizeof(int),
+                           hipMemcpyHostToDevice, st.s));
+  HIP_THROW(hipMemsetAsync(d_tot.p, 0, S * T * 2 * 8, st.s));
+  CHECK_RC(launch_eval_prep(d_gt4.as<double>(), (int)G, d_gt5.as<double>(), d_first.as<int>(), st.s));
+  CHECK_RC(launch_eval_match(d_pred.as<double>(), d_poff.as<int>(), d_goff.as<int>(), d_gt5.as<double>(), d_tiles.as<int>(),
+                             d_tiles.as<int>() + n_tiles, (int)n_tiles, iou_thresh, mimic_eval_bug != 0, d_match.as<int>(),
+                             d_first.as<int>(), st.s));
+  CHECK_RC(launch_eval_counts(d_poff.as<int>(), d_match.as<int>(), d_first.as<int>(), d_counted.as<uint8_t>(), n_images,
+                              n_settings, (int)N, (int)G, d_hits.as<int>(), d_cprop.as<int>(), d_prop.as<uint8_t>(), st.s));
+  CHECK_RC(launch_eval_sweep(d_pred.as<double>(), d_poff.as<int>(), d_goff.as<int>(), d_hits.as<int>(), d_cprop.as<int>(),
+                             n_images, n_settings, (int)N, d_thresh.as<double>(), n_thresh,
+                             d_tot.as<unsigned long long>(), st.s));
+  HIP_THROW(hipMemcpyAsync(totals, d_tot.p, S * T * 2 * 8, hipMemcpyDeviceToHost, st.s));
+  if (hits_out) HIP_THROW(hipMemcpyAsync(hits_out, d_hits.p, S * (size_t)N * sizeof(int), hipMemcpyDeviceToHost, st.s));
+  if (proposal_out) HIP_THROW(hipMemcpyAsync(proposal_out, d_prop.p, S * (size_t)N, hipMemcpyDeviceToHost, st.s));
+  HIP_THROW(hipStreamSynchronize(st.s));
+  return 0;
   API_END(-1)
 }
 

@@ -102,7 +102,9 @@ class ImageList(object):
             # lib/datasets/wider.py:169-195 (the tarball / tensorboard side effects are not reproduced)
             from .config import cfg
             from .wider_eval import wider_eval
+            # SHF_DEVICE_EVAL=1: matching and threshold sweep on the GPU (an environment switch like SHF_HOST_PREPROCESS,
+            # not a cfg key: the config dump is the reference's)
             ap, _ = wider_eval(out, self._ground_truth, mimic_eval_bug=cfg.MISC.MIMIC_EVAL_BUG,
-                               IoU_thresh=cfg.TEST.IOU_THRESH)
+                               IoU_thresh=cfg.TEST.IOU_THRESH, device=os.environ.get("SHF_DEVICE_EVAL") == "1")
             return 'Easy: {:.4f}, Medium: {:.4f}, Hard: {:.4f}'.format(*ap)
         return 'detections written to {}'.format(out)

@@ -16,8 +16,15 @@ because they decide the published AP numbers:
 
 The implementation is organised around in-memory structures (``WiderGT`` / lists of (n, 5) arrays) with separate
 readers for the toolbox's ``.mat`` ground truth and the detection text files, and the per-image threshold sweep is a
-``searchsorted`` instead of a 1000-step loop.  Host-side utility: nothing here touches the GPU.
+``searchsorted`` instead of a 1000-step loop.
+
+The default path is host numpy.  ``evaluate(..., device=True)`` / ``wider_eval(..., device=True)`` run the matching and
+the threshold sweep -- the loop over every detection of every image, three times -- on the GPU instead
+(``shf_wider_eval_counts``, csrc/eval.hip): sorting, score normalisation, the final divisions and ``voc_ap`` stay on the
+host, the device returns exact integer counts, and the curves come out bit for bit the host's.
 """
+import ctypes as C
+import logging
 import os
 
 import numpy as np
@@ -179,18 +186,128 @@ def evaluate_setting(norm_preds, gt, iou_thresh=0.5, mimic_eval_bug=True, thresh
         return np.stack([total[:, 1] / total[:, 0], total[:, 1] / count_face], axis=1)
 
 
-def evaluate(preds, gts, iou_thresh=0.5, mimic_eval_bug=True):
+# ---- device path ------------------------------------------------------------------------------------------------------
+MAX_DEVICE_SETTINGS = 8      # shf_wider_eval_counts takes 1..8 subset masks over one set of boxes
+_FINITE_BOUND = 1e150        # below it no product or sum of _overlaps() can overflow to inf (and inf / inf to NaN)
+
+
+def flatten_inputs(norm_preds, boxes, keeps):
+    """The flat arrays of ``shf_wider_eval_counts``: ``norm_preds`` per image (n, 5) score-descending rows (None or
+    empty: no rows), ``boxes`` per image (g, 4), ``keeps`` per SETTING the per-image index arrays of its subset.
+    Returns a dict: pred5 (N, 5), pred_off (I + 1), gt4 (G, 4), gt_off (I + 1), counted (S, G) uint8."""
+    n_img = len(boxes)
+    pl = [np.zeros((0, 5)) if p is None else np.asarray(p, dtype=np.float64).reshape(-1, 5) for p in norm_preds]
+    bl = [np.asarray(b, dtype=np.float64).reshape(-1, 4) for b in boxes]
+    pred_off = np.zeros(n_img + 1, dtype=np.int64)
+    gt_off = np.zeros(n_img + 1, dtype=np.int64)
+    np.cumsum([p.shape[0] for p in pl], out=pred_off[1:])
+    np.cumsum([b.shape[0] for b in bl], out=gt_off[1:])
+    if max(int(pred_off[-1]), int(gt_off[-1])) >= 2 ** 31:
+        raise ValueError('flatten_inputs: 2^31 rows or more')
+    counted = np.zeros((len(keeps), int(gt_off[-1])), dtype=np.uint8)
+    for s, keep in enumerate(keeps):
+        for j in range(n_img):
+            if bl[j].shape[0]:
+                # (a view of the image's segment: counted[keep] = True of image_counts, out-of-range indices raise alike)
+                counted[s, gt_off[j]:gt_off[j + 1]][np.asarray(keep[j], dtype=np.int64).reshape(-1)] = 1
+    return dict(pred5=np.ascontiguousarray(np.concatenate(pl, axis=0) if pl else np.zeros((0, 5))),
+                pred_off=pred_off.astype(np.int32),
+                gt4=np.ascontiguousarray(np.concatenate(bl, axis=0) if bl else np.zeros((0, 4))),
+                gt_off=gt_off.astype(np.int32), counted=counted)
+
+
+def split_flat(flat, off):
+    """Inverse of the flattening: the per-image blocks of rows ``off[i] .. off[i + 1]`` of ``flat`` (pred5, gt4, or one
+    setting's row of ``counted``)."""
+    return [flat[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+
+def sweep_thresholds(thresh_num=THRESH_NUM):
+    t = np.arange(thresh_num, dtype=np.float64)
+    return 1 - (t + 1.) / thresh_num       # (the expression of image_pr_info; the device is handed these values)
+
+
+def device_counts(flat, iou_thresh=0.5, mimic_eval_bug=True, thresh=None, diagnostics=False):
+    """One ``shf_wider_eval_counts`` call on flattened inputs.  Returns totals (S, T, 2) int64 = summed [proposals,
+    subset faces found] per setting and threshold; with ``diagnostics`` also hits (S, N) int32 and proposal (S, N) bool,
+    the per-detection outputs of ``image_counts``."""
+    from . import _lib
+    lib = _lib.load()                       # raises ShfError when the library or a GPU is missing
+    thresh = np.ascontiguousarray(sweep_thresholds() if thresh is None else thresh, dtype=np.float64)
+    pred5 = np.ascontiguousarray(flat['pred5'], dtype=np.float64)
+    gt4 = np.ascontiguousarray(flat['gt4'], dtype=np.float64)
+    pred_off = np.ascontiguousarray(flat['pred_off'], dtype=np.int32)
+    gt_off = np.ascontiguousarray(flat['gt_off'], dtype=np.int32)
+    counted = np.ascontiguousarray(flat['counted'], dtype=np.uint8)
+    n_set, n_rows = counted.shape[0], pred5.shape[0]
+    totals = np.zeros((n_set, thresh.shape[0], 2), dtype=np.int64)
+    hits = np.zeros((n_set, n_rows), dtype=np.int32) if diagnostics else None
+    prop = np.zeros((n_set, n_rows), dtype=np.uint8) if diagnostics else None
+    dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_uint8)
+    _lib.check(lib.shf_wider_eval_counts(
+        pred5.ctypes.data_as(dp), pred_off.ctypes.data_as(ip), gt4.ctypes.data_as(dp), gt_off.ctypes.data_as(ip),
+        counted.ctypes.data_as(bp), len(pred_off) - 1, n_set, float(iou_thresh), int(bool(mimic_eval_bug)),
+        thresh.ctypes.data_as(dp), thresh.shape[0], totals.ctypes.data_as(C.POINTER(C.c_longlong)),
+        hits.ctypes.data_as(ip) if diagnostics else None, prop.ctypes.data_as(bp) if diagnostics else None),
+        "wider_eval_counts")
+    return (totals, hits, prop.astype(bool)) if diagnostics else totals
+
+
+def _share_images(gts):
+    """Do the settings list the same images with the same boxes (the toolbox's three .mat files do)?"""
+    a = gts[0]
+    for b in gts[1:]:
+        if len(b) != len(a) or any(np.shape(x) != np.shape(y) or not np.array_equal(x, y)
+                                   for x, y in zip(a.boxes, b.boxes)):
+            return False
+    return True
+
+
+def _device_safe(norm_preds, gts):
+    """Every box and score finite and far from overflow: only then is the device arithmetic numpy's bit for bit (the
+    arg-max of a row holding NaN is numpy's own business)."""
+    def ok(x):
+        x = np.asarray(x, dtype=np.float64)
+        return bool(np.all(np.abs(x) < _FINITE_BOUND))
+    return all(ok(p) for p in norm_preds if p is not None) and all(ok(b) for g in gts for b in g.boxes)
+
+
+def _device_curves(norm_preds, gts, iou_thresh, mimic_eval_bug, thresh_num=THRESH_NUM):
+    """evaluate_setting for every gt of ``gts`` with the counting on the device: one call for all settings when they
+    share images and boxes, else one call per setting."""
+    share = len(gts) <= MAX_DEVICE_SETTINGS and _share_images(gts)
+    groups = [list(range(len(gts)))] if share else [[s] for s in range(len(gts))]
+    curves = [None] * len(gts)
+    for grp in groups:
+        flat = flatten_inputs(norm_preds, gts[grp[0]].boxes, [gts[s].keep for s in grp])
+        totals = device_counts(flat, iou_thresh, mimic_eval_bug, sweep_thresholds(thresh_num))
+        for k, s in enumerate(grp):
+            count_face = sum(np.asarray(kp, dtype=np.int64).reshape(-1).shape[0] for kp in gts[s].keep)
+            total = totals[k].astype(np.float64)       # (exact: the host sums the same integers as float64)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                curves[s] = np.stack([total[:, 1] / total[:, 0], total[:, 1] / count_face], axis=1)
+    return curves
+
+
+def evaluate(preds, gts, iou_thresh=0.5, mimic_eval_bug=True, device=False):
     """``preds``: per image (n, 5) x-y-w-h-score arrays (any order; None = missing) in the image order shared by the
-    three ``gts`` (easy, medium, hard WiderGT).  Returns ([ap_easy, ap_medium, ap_hard], [pr_curves])."""
+    three ``gts`` (easy, medium, hard WiderGT).  Returns ([ap_easy, ap_medium, ap_hard], [pr_curves]).
+    ``device=True``: matching and threshold sweep on the GPU (same curves, bit for bit; ShfError without a GPU)."""
     norm = normalise_scores([None if p is None else sort_by_score(p) for p in preds])
-    curves = [evaluate_setting(norm, g, iou_thresh, mimic_eval_bug) for g in gts]
+    if device and not _device_safe(norm, gts):
+        logging.getLogger(__name__).warning('wider_eval: non-finite boxes or scores, evaluating on the host')
+        device = False
+    if device:
+        curves = _device_curves(norm, gts, iou_thresh, mimic_eval_bug)
+    else:
+        curves = [evaluate_setting(norm, g, iou_thresh, mimic_eval_bug) for g in gts]
     return [voc_ap(c[:, 1], c[:, 0]) for c in curves], curves
 
 
-def wider_eval(pred_dir, gt_dir_base, silent=True, parallel=False, mimic_eval_bug=True, IoU_thresh=0.5):
+def wider_eval(pred_dir, gt_dir_base, silent=True, parallel=False, mimic_eval_bug=True, IoU_thresh=0.5, device=False):
     """The reference's entry point (wider_eval.py:180-222): detection text files + the toolbox's ground_truth
     directory -> (ap[3], pr_curve[3])."""
     face = load_gt_mat(os.path.join(gt_dir_base, 'wider_face_val.mat'))
     preds = read_predictions(pred_dir, face)
     gts = [load_gt_mat(os.path.join(gt_dir_base, 'wider_%s.mat' % s)) for s in SETTINGS]
-    return evaluate(preds, gts, IoU_thresh, mimic_eval_bug)
+    return evaluate(preds, gts, IoU_thresh, mimic_eval_bug, device=device)
