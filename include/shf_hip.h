@@ -95,7 +95,12 @@ int shf_net_get_conv_mode(shf_net* net);
  * the 2- and 1-product instantiations; the fused pair's conv1_1 (0.5 % of the FLOPs) always forms three.
  * Mode 4 = bf16: ONE v_mfma_f32_32x32x16_bf16 product per fp32 product, operands rounded to bf16 (8 mantissa bits), fp32
  * accumulate, fp32 activations in HBM.  bf16 has fp32's exponent range: no range guard, no weight refusal.  Like modes 2
- * and 3 it is a drift-labelled throughput mode, not a parity mode (bench.py reports its drift beside the headline). */
+ * and 3 it is a drift-labelled throughput mode, not a parity mode (bench.py reports its drift beside the headline).
+ * Mode 5 = f64: out = fl32(bias + sum a*w) with the fp32 operands widened to binary64, the products (exact there) and the
+ * sum in binary64 on v_mfma_f64_16x16x4_f64, ONE rounding to fp32 -- in every Convolution, the cls / bbox predictors of the
+ * tail and the depthwise deconvolution.  Activations stay fp32.  It is the on-device truth the drift of modes 0 and 1 is
+ * measured against (tools/precision_ladder.py), not a throughput mode: it always runs layer by layer like mode 0, keeps
+ * no packs, has no range guard, and shf_net_set_layer_products has no effect in it. */
 int shf_net_set_layer_products(shf_net* net, const char* layer, int nprod);
 /* fp16 range guard of mode 1 (the reference is fp32 everywhere, caffe/python/caffe/_caffe.cpp:46-48): hi = fp16(x)
  * overflows above 65504.  Weights are checked when they are packed (shf_net_param_commit / shf_net_set_conv_mode

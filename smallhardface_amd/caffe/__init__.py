@@ -39,8 +39,10 @@ def set_device(device_id):
 
 
 # arithmetic of the MFMA convolutions (C ABI shf_net_set_conv_mode): exact fp32; split-fp16 with three products
-# (fp32-class: the mode every parity test runs); the reduced ladder with two / one product (drift-labelled)
-CONV_MODES = {"fp32": 0, "f16x3": 1, "f16x2": 2, "f16": 3, "bf16": 4, 0: 0, 1: 1, 2: 2, 3: 3, 4: 4}
+# (fp32-class: the mode every parity test runs); the reduced ladder with two / one product (drift-labelled); binary64
+# accumulation with one rounding to fp32 (the on-device truth the drift of the others is measured against)
+CONV_MODES = {"fp32": 0, "f16x3": 1, "f16x2": 2, "f16": 3, "bf16": 4, "f64": 5, 0: 0, 1: 1, 2: 2, 3: 3, 4: 4, 5: 5}
+CONV_MODE_NAMES = {0: "fp32", 1: "f16x3", 2: "f16x2", 3: "f16", 4: "bf16", 5: "f64"}
 
 
 class Layer(object):
@@ -177,14 +179,17 @@ class Net(object):
     def set_conv_mode(self, mode):
         """Arithmetic of the MFMA convolutions: "fp32" (exact fp32 MFMA), "f16x3" (split-fp16, three fp16 products per
         fp32 product: fp32-class accuracy, the parity mode), and the reduced, drift-labelled modes "f16x2", "f16" (two /
-        one fp16 product; fp16 range guard applies) and "bf16" (one bf16 product; fp32's exponent range, no guard)."""
+        one fp16 product; fp16 range guard applies) and "bf16" (one bf16 product; fp32's exponent range, no guard).
+        "f64" accumulates every dot product (convolutions, the cls / bbox predictors, the deconvolution) in binary64 and
+        rounds once to fp32: the best answer fp32 blobs can hold, for measuring the drift of the other modes on the device
+        at any size.  It always runs layer by layer, as "fp32" does, and is not a throughput mode."""
         m = CONV_MODES[mode]
         self.commit_params()
         _lib.check(self._lib.shf_net_set_conv_mode(self._h, m), "set_conv_mode")
 
     @property
     def conv_mode(self):
-        return {0: "fp32", 1: "f16x3", 2: "f16x2", 3: "f16", 4: "bf16"}[int(self._lib.shf_net_get_conv_mode(self._h))]
+        return CONV_MODE_NAMES[int(self._lib.shf_net_get_conv_mode(self._h))]
 
     def set_layer_products(self, table):
         """{layer name: 1 | 2 | 3 (0 clears)}: fp16 products per fp32 product for single layers of a split-fp16 mode

@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "conv_common.h"
+#include "conv_f64.h"
 #include "shf_internal.h"
 
 namespace shf {
@@ -429,7 +430,7 @@ static ConvPlan plan_conv_f32(const ConvArgs* as, int n) {
   return pl;
 }
 
-long long conv_fill(ConvPlan& pl, const ConvArgs* as, int n, int nct, int th, int tw) {
+long long conv_fill(ConvPlan& pl, const ConvArgs* as, int n, int nct, int th, int tw, bool scalar_loads) {
   if (n < 1 || n > MAX_GROUP) { pl.err = "conv group: 1..16 members"; return -1; }
   const ConvArgs& a = as[0];
   ConvK& p = pl.k;
@@ -447,7 +448,7 @@ long long conv_fill(ConvPlan& pl, const ConvArgs* as, int n, int nct, int th, in
   long long tiles = 0;
   for (int i = 0; i < n; ++i) {
     const ConvArgs& q = as[i];
-    if ((q.in.cstride % 4) || (q.in.coff % 4)) { pl.err = "conv: input view not 16-byte aligned"; return -1; }
+    if (!scalar_loads && ((q.in.cstride % 4) || (q.in.coff % 4))) { pl.err = "conv: input view not 16-byte aligned"; return -1; }
     if (q.in.C != p.Cin || q.out.C != p.Cout || q.in.cstride != p.in_stride || q.out.cstride != p.out_stride || q.k != a.k ||
         q.dil != a.dil || q.wpacked != a.wpacked || q.wsplit16 != a.wsplit16 || q.wsplit16h != a.wsplit16h || !q.img != !a.img ||
         q.in_split != a.in_split || q.out_split != a.out_split || q.pool_split != a.pool_split) {
@@ -498,6 +499,7 @@ int conv_init_attributes() {
 }
 
 ConvPlan plan_conv(const ConvArgs* as, int n) {
+  if (n >= 1 && as[0].f64) return plan_conv_f64(as, n);
   return (n >= 1 && as[0].wsplit16) ? plan_conv_f16x3(as, n) : plan_conv_f32(as, n);
 }
 

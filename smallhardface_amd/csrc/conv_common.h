@@ -747,7 +747,8 @@ struct ConvPlan {
   void (*timing_report)(const ConvPlan&, hipStream_t) = nullptr;   // SHF_CONV_TIMING builds: after the last launch
   int rows = 0;                                                    // ... the dual-tile family's tile rows
 };
-// grouped launch over 1..16 members that share the layer; the mode follows the arguments (wsplit16: split-fp16, else fp32)
+// grouped launch over 1..16 members that share the layer; the mode follows the arguments (f64: binary64 accumulation,
+// wsplit16: split-fp16, else fp32)
 ConvPlan plan_conv(const ConvArgs* as, int n);
 // the three shared-weight dilated heads (dilation 1 / 2 / 4) as one launch; nl == 0 with no error: the triple does not
 // qualify and the heads run one by one
@@ -755,8 +756,8 @@ ConvPlan plan_conv_heads3(const ConvArgs* a1, const ConvArgs* a2, const ConvArgs
 int launch_conv_plan(const ConvPlan& pl, int i, hipStream_t s);
 // the ConvK header and member table every kernel kind shares, with the group-consistency and size-limit checks: th x tw pixel
 // tiles (th == 0: flat tiles of tw pixels over each member's pixel list), nct cout tiles.  The group's pixel tiles, or -1
-// with pl.err set.
-long long conv_fill(ConvPlan& pl, const ConvArgs* as, int n, int nct, int th, int tw);
+// with pl.err set.  `scalar_loads`: the kernel reads its input value by value, so the views need no 16-byte alignment.
+long long conv_fill(ConvPlan& pl, const ConvArgs* as, int n, int nct, int th, int tw, bool scalar_loads = false);
 // the kernel tables' LDS opt-in (160 KiB)
 int conv_set_lds_attributes(const ConvKernel* t, int n);
 ConvPlan plan_conv_f16x3(const ConvArgs* as, int n);   // (conv_f16x3.hip: the split-fp16 modes)

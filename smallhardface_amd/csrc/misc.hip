@@ -246,6 +246,43 @@ int launch_deconv_depthwise_group(const View* ins, const View* outs, int n, cons
   return 0;
 }
 
+// conv mode "f64": the same taps with the products and the sum in binary64 (exact products, at most k*k additions), the
+// bias added in binary64, ONE rounding to fp32.  One thread per output value; any channel count and view alignment.
+__global__ void deconv_dw_f64_kernel(const float* __restrict__ in, const float* __restrict__ w,
+                                     const float* __restrict__ bias, float* __restrict__ out, int H, int W, int C, int Ho,
+                                     int Wo, int k, int stride, int pad, int in_stride, int out_stride) {
+  const unsigned n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= (unsigned)Wo * (unsigned)C) return;
+  const int c = (int)(n % (unsigned)C), ox = (int)(n / (unsigned)C), oy = blockIdx.y, b = blockIdx.z;
+  double acc = 0.0;
+  for (int a = (oy + pad) % stride; a < k; a += stride) {
+    const int ty = oy + pad - a;
+    if (ty < 0) break;
+    const int iy = ty / stride;
+    if (iy >= H) continue;
+    for (int bb = (ox + pad) % stride; bb < k; bb += stride) {
+      const int tx = ox + pad - bb;
+      if (tx < 0) break;
+      const int ix = tx / stride;
+      if (ix >= W) continue;
+      acc += (double)in[((size_t)(b * H + iy) * W + ix) * in_stride + c] * (double)w[((size_t)c * k + a) * k + bb];
+    }
+  }
+  if (bias) acc += (double)bias[c];
+  out[((size_t)(b * Ho + oy) * Wo + ox) * out_stride + c] = (float)acc;
+}
+
+int launch_deconv_depthwise_f64(const View& in, const View& out, const float* w, const float* bias, int k, int stride,
+                                int pad, hipStream_t s) {
+  const unsigned long long per_row = (unsigned long long)out.W * (unsigned long long)in.C;
+  if (per_row >= (1ull << 31) || out.H > 65535 || out.B > 65535) { set_error("deconv (f64 mode): map too large"); return -1; }
+  hipLaunchKernelGGL(deconv_dw_f64_kernel, dim3((unsigned)((per_row + 255) / 256), out.H, out.B), dim3(256), 0, s,
+                     in.p + in.coff, w, bias, out.p + out.coff, in.H, in.W, in.C, out.H, out.W, k, stride, pad, in.cstride,
+                     out.cstride);
+  SHF_HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int launch_deconv_depthwise(const View& in, const View& out, const float* w, const float* bias, int k, int stride,
                             int pad, hipStream_t s, int* range_flag, unsigned* out_amax) {
   if (in.C % 4 || in.cstride % 4 || in.coff % 4 || out.cstride % 4 || out.coff % 4) {

@@ -201,12 +201,12 @@ int shf_net_set_proposal_cfg(shf_net* net, int pre_nms_topN, float score_thresh,
 
 int shf_net_set_conv_mode(shf_net* net, int mode) {
   API_BEGIN
-  if (mode < 0 || mode > 4)
-    throw std::runtime_error("conv mode must be 0 (fp32), 1 (split-fp16 x3), 2 (x2), 3 (plain fp16) or 4 (bf16)");
+  if (mode < 0 || mode > 5)
+    throw std::runtime_error("conv mode must be 0 (fp32), 1 (split-fp16 x3), 2 (x2), 3 (plain fp16), 4 (bf16) or 5 (f64)");
   if (net->conv_mode == mode) return 0;
   HIP_THROW(hipDeviceSynchronize());  // the mode is shared with every lane: nothing may be in flight while it flips
   net->conv_mode = mode;
-  if (mode >= 1) {
+  if (net->split_mode()) {   // (fp32 and f64 modes read the fp32 packs / the raw weights, which always exist)
     // the fp32 packs always exist; the split-fp16 packs are made on first use, re-made by every commit in a split
     // mode, and re-made here when a commit in fp32 mode left them stale (also re-runs the |w| <= 65504 check)
     try {

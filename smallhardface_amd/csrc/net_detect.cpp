@@ -9,7 +9,7 @@ static const char* kRangeMsg =
     "split-fp16 range exceeded: a convolution output has |x| > 65504 (fp16 hi overflows); this image must be "
     "re-run with conv mode fp32";
 static void throw_if_out_of_range(shf_net* net) {
-  if (net->conv_mode < 1) return;
+  if (!net->split_mode()) return;
   int flag = 0;
   HIP_THROW(hipMemcpyAsync(&flag, net->range_flag.p, 4, hipMemcpyDeviceToHost, net->stream));
   HIP_THROW(hipStreamSynchronize(net->stream));
@@ -205,7 +205,7 @@ int shf_detect_add_levels(shf_net* net, int n, shf_net** members, const float* c
 static int detect_count_checked(shf_net* net, bool check_range) {
   int c[2] = {0, 0}, flag = 0;
   HIP_THROW(hipMemcpyAsync(c, net->img_count.p, 8, hipMemcpyDeviceToHost, net->stream));
-  if (check_range && net->conv_mode >= 1)
+  if (check_range && net->split_mode())
     HIP_THROW(hipMemcpyAsync(&flag, net->range_flag.p, 4, hipMemcpyDeviceToHost, net->stream));
   HIP_THROW(hipStreamSynchronize(net->stream));
   if (flag) throw std::runtime_error(kRangeMsg);

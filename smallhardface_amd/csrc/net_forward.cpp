@@ -24,7 +24,7 @@ const char* const kProfNames[PC_COUNT] = {"conv_mfma_f32_kernel<3, 1, 128, 8, 16
                                            "conv_mfma_f16x3_pc_kernel<3, false, true>", "conv_mfma_f16x3_k1_kernel<true, 3>",
                                            "conv_mfma_f16x3_w4d_kernel<true, 4, 1, 3, false, 2>", "conv_mfma_f16x3_w4d_kernel<true, 4, 1, 3, false, 4>",
                                            "conv_mfma_f16x3_heads3_kernel<true, 3>",
-                                           "conv_first_kernel", "conv_direct_kernel", "maxpool_kernel",
+                                           "conv_first_kernel", "conv_direct_kernel", "conv_mfma_f64_kernel", "maxpool_kernel",
                                            "deconv_depthwise", "detect_tail", "box_merge", "layout", "h2d_copy", "d2h_copy"};
 
 int run_conv_plan(const ConvPlan& pl, hipStream_t s, Prof& prof, double flops, double bytes) {
@@ -70,7 +70,7 @@ TailArgs shf_net::tail_args(float im_h, float im_w, float im_scale, bool materia
 
 bool shf_net::split16(const Layer& L) const {
   const ParamBlob& w = *L.params[0];
-  return conv_mode >= 1 && L.kclass == 0 && (conv_mode == 4 ? w.packed16b.p : w.packed16.p) &&
+  return split_mode() && L.kclass == 0 && (conv_mode == 4 ? w.packed16b.p : w.packed16.p) &&
          conv_f16x3_eligible(blobs[L.bottoms[0]].shape[1], L.nout, L.k, L.pad, L.dil);
 }
 
@@ -102,6 +102,8 @@ ConvArgs shf_net::conv_args(int li, bool fused, int* flag) const {
   a.wsplit16r = s16 ? (bf ? w.packed16rb.p : w.packed16r.p) : nullptr;
   a.wscale_inv = bf ? 1.f : w.wscale_inv;
   a.bf16 = bf && s16 ? 1 : 0;
+  a.f64 = f64_mode() ? 1 : 0;
+  if (a.f64 && L.kclass == 1) a.img = nchw_input(L.bottoms[0]);   // (the one f64 kernel reads the first layer's NCHW image itself)
   // an fp16 mode: every producer of a map that a split-fp16 conv may read guards the fp16 range
   a.range_flag = fp16_mode() ? flag : nullptr;
   a.in_amax = amax_slot(L.bottoms[0]);
@@ -159,12 +161,14 @@ void shf_net::add_cost(int li, bool fused, int heads, double& flops, double& byt
 void run_pass(const Pass& p) {
   shf_net& h = *p.head;
   const shf_net& n0 = *p.u[0].lane;   // (every lane holds the same graph and parameter tensors)
+  // f64 mode runs every pass layer by layer (one kernel for every conv class, pools and the first layer on their own)
+  const bool f64 = h.f64_mode(), fused = p.fused && !f64;
   int* const flag = (int*)h.range_flag.p;
   // the profiler's flops / bytes of layer li on lanes m0 .. m1 - 1 in one launch: each lane's share, a conv's weights once
   auto cost = [&](int li, int m0, int m1, int heads) {
     const Layer& L = n0.layers[li];
     double fl = 0, by = L.op == OP_CONV ? 4.0 * L.params[0]->count() : 0;
-    for (int m = m0; m < m1; ++m) p.u[m].lane->add_cost(li, p.fused, heads, fl, by);
+    for (int m = m0; m < m1; ++m) p.u[m].lane->add_cost(li, fused, heads, fl, by);
     return std::make_pair(fl, by);
   };
   ConvArgs a1[kMaxGroup], a2[kMaxGroup], a4[kMaxGroup];
@@ -177,10 +181,10 @@ void run_pass(const Pass& p) {
     switch (L.op) {
       case OP_SKIP: break;
       case OP_CONV: {
-        if (L.first_dst >= 0 && n0.absorbs_first(L.first_dst, p.fused)) break;   // computed inside the next conv's halo staging
+        if (L.first_dst >= 0 && n0.absorbs_first(L.first_dst, fused)) break;   // computed inside the next conv's halo staging
         if (L.heads3_lead >= 0 && heads3_done == L.heads3_lead) break;        // written by the dilation-1 sibling's launch
-        for (int m = 0; m < p.n; ++m) a1[m] = p.u[m].lane->conv_args(li, p.fused, flag);
-        if (L.kclass != 0) {   // the first-layer kernel (NCHW image in) and the generic direct one: a launch per lane
+        for (int m = 0; m < p.n; ++m) a1[m] = p.u[m].lane->conv_args(li, fused, flag);
+        if (L.kclass != 0 && !f64) {   // the first-layer kernel (NCHW image in) and the generic direct one: a launch per lane
           for (int m = 0; m < p.n; ++m) {
             const auto c = cost(li, m, m + 1, 1);
             ProfScope ps(h.prof, p.s, L.kclass == 1 ? PC_CONV_FIRST : PC_CONV_DIRECT, c.first, c.second);
@@ -189,10 +193,10 @@ void run_pass(const Pass& p) {
           }
           break;
         }
-        if (L.heads3_d2 >= 0) {   // the three shared-weight heads in one launch (conv_f16x3_h3.h), if shapes and mode allow
+        if (L.heads3_d2 >= 0 && !f64) {   // the three shared-weight heads in one launch (conv_f16x3_h3.h), if shapes and mode allow
           for (int m = 0; m < p.n; ++m) {
-            a2[m] = p.u[m].lane->conv_args(L.heads3_d2, p.fused, flag);
-            a4[m] = p.u[m].lane->conv_args(L.heads3_d4, p.fused, flag);
+            a2[m] = p.u[m].lane->conv_args(L.heads3_d2, fused, flag);
+            a4[m] = p.u[m].lane->conv_args(L.heads3_d4, fused, flag);
           }
           const ConvPlan pl = plan_conv_heads3(a1, a2, a4, p.n);
           if (pl.nl > 0 || !pl.err.empty()) {
@@ -207,7 +211,7 @@ void run_pass(const Pass& p) {
         break;
       }
       case OP_POOL:
-        if (p.fused && L.fused_into >= 0) break;  // done by the producing conv's epilogue
+        if (fused && L.fused_into >= 0) break;  // done by the producing conv's epilogue
         for (int m = 0; m < p.n; ++m) {
           const shf_net& ln = *p.u[m].lane;
           const auto c = cost(li, m, m + 1, 1);
@@ -231,6 +235,14 @@ void run_pass(const Pass& p) {
         const float* w = (const float*)L.params[0]->raw.p;
         const float* b = L.params.size() > 1 ? (const float*)L.params[1]->raw.p : nullptr;
         int* const dflag = h.fp16_mode() ? flag : nullptr;
+        if (f64) {   // binary64 accumulation: one launch per unit
+          for (int m = 0; m < p.n; ++m) {
+            const auto c = cost(li, m, m + 1, 1);
+            ProfScope ps(h.prof, p.s, PC_DECONV, c.first, c.second);
+            CHECK_RC(launch_deconv_depthwise_f64(in[m], out[m], w, b, L.k, L.stride, L.pad, p.s));
+          }
+          break;
+        }
         if (p.n > 1 && batch1) {   // the units' depthwise up-samplings as one launch (ten serial 5..60-us launches otherwise)
           const auto c = cost(li, 0, p.n, 1);
           ProfScope ps(h.prof, p.s, PC_DECONV, c.first, c.second);
@@ -252,6 +264,7 @@ void run_pass(const Pass& p) {
         for (int m = 0; m < p.n; ++m) {
           shf_net& ln = *p.u[m].lane;
           t[m] = ln.tail_args(p.u[m].im_h, p.u[m].im_w, p.u[m].im_scale, p.materialize);
+          t[m].f64 = f64 ? 1 : 0;
           tws[m] = &ln.tw;
           boxes[m] = (float*)ln.blobs[ln.boxes_blob].dev.p;
           probs[m] = ln.probs_out();
@@ -319,7 +332,7 @@ void shf_net::run_unit(bool fused, const float im_info[3], TailStep tail, bool m
 // layer's (nothing else is an output: a conv top that is a net output must hold plain fp32 after forward())
 bool shf_net::forward_fast_eligible() const {
   static const bool knob = !(getenv("SHF_FORWARD_FAST") && atoi(getenv("SHF_FORWARD_FAST")) == 0);
-  if (!knob || conv_mode < 1 || tail_layer < 0 || data_blob < 0) return false;
+  if (!knob || !split_mode() || tail_layer < 0 || data_blob < 0) return false;
   for (int o : outputs)
     if (o != boxes_blob && o != prob_blob) return false;
   return true;
@@ -346,7 +359,7 @@ void shf_net::forward() {
   memcpy(last_im_info, ii, 12);
   inputs_reshaped = false;
   const bool fast = forward_fast_eligible();
-  if (conv_mode >= 1) HIP_THROW(hipMemsetAsync(range_flag.p, 0, 4, stream));
+  if (split_mode()) HIP_THROW(hipMemsetAsync(range_flag.p, 0, 4, stream));
   reset_amax(stream);
   run_unit(fast, ii, TAIL_LANE, true);
   plain_stale = fast;
@@ -354,10 +367,10 @@ void shf_net::forward() {
   {
     ProfScope ps(prof, stream, PC_D2H, 0, sizeof(cnt) + 4);
     if (tail_layer >= 0) HIP_THROW(hipMemcpyAsync(cnt, tw.counters, sizeof(cnt), hipMemcpyDeviceToHost, stream));
-    if (conv_mode >= 1) HIP_THROW(hipMemcpyAsync(&flag, range_flag.p, 4, hipMemcpyDeviceToHost, stream));
+    if (split_mode()) HIP_THROW(hipMemcpyAsync(&flag, range_flag.p, 4, hipMemcpyDeviceToHost, stream));
   }
   HIP_THROW(hipStreamSynchronize(stream));
-  if (flag && conv_mode >= 1) {
+  if (flag && split_mode()) {
     const int mode_was = conv_mode;
     // a convolution produced |x| > 65504: fp16(hi) of the split overflowed somewhere downstream.  The reference
     // computes in fp32 (_caffe.cpp:46-48): redo THIS forward on the exact fp32 matrix-core kernels (per-layer path:

@@ -326,7 +326,8 @@ using namespace shf;
 // layer reads from the global cfg at every forward (lib/layers/proposal_layer.py:88-92)
 struct NetShared {
   int conv_mode = 0;  // 0: exact fp32 MFMA everywhere; 1: split-fp16, 3 products (fp32-class accuracy); 2 / 3: the
-                      // reduced ladder -- 2 products (activations rounded to fp16) / 1 product (plain fp16 operands)
+                      // reduced ladder -- 2 products (activations rounded to fp16) / 1 product (plain fp16 operands); 4: bf16;
+                      // 5: binary64 accumulation, one rounding to fp32 (conv_f64.h: the on-device truth for drift)
   std::map<std::string, int> layer_products;  // per-layer override of the number of fp16 products (shf_net_set_layer_products)
   int pre_nms_topN = 10000;
   float score_thresh = 0.002f, min_size = 0.f;
@@ -394,7 +395,11 @@ struct shf_net {
   hipStream_t cstream() { return pipelined && sh->conv_stream ? sh->conv_stream : stream; }
   // an fp16 mode (split-fp16, f16x2, f16): its producers guard the fp16 range and it keeps activation-exponent slots (bf16
   // has fp32's exponent range)
-  bool fp16_mode() const { return conv_mode >= 1 && conv_mode != 4; }
+  bool fp16_mode() const { return conv_mode >= 1 && conv_mode <= 3; }
+  // a 16-bit mode (the fp16 modes and bf16): split weight packs, the fused path's kernels, the range flag's read-back
+  bool split_mode() const { return conv_mode >= 1 && conv_mode <= 4; }
+  // binary64 accumulation (conv_f64.h): always the per-layer path, like fp32 mode -- no packs, no slots, no range guard
+  bool f64_mode() const { return conv_mode == 5; }
   // activation-exponent slots (conv_common.h): one u32 per blob of THIS lane = bit pattern of max |value| of the unit
   // it currently holds; zeroed at the start of every forward / unit, raised by the producers' epilogues, read by the
   // single-accumulator split-fp16 kernels.  Concat members share their owner's slot.

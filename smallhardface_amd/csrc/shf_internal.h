@@ -32,7 +32,7 @@ enum ProfClass {
   PC_CONV_F16X3_64_K1, PC_CONV_F16X3_PC,
   PC_CONV_F16X3_W4D_0, PC_CONV_F16X3_W4D_7 = PC_CONV_F16X3_W4D_0 + 7,   // dual-tile family: + in_split * 4 + (rows == 8) * 2 + (tiles == 1)
   PC_CONV_F16X3_PCP, PC_CONV_F16X3_K1G, PC_CONV_F16X3_W4D_D2, PC_CONV_F16X3_W4D_D4, PC_CONV_F16X3_H3,
-  PC_CONV_FIRST, PC_CONV_DIRECT, PC_POOL, PC_DECONV, PC_TAIL, PC_MERGE, PC_LAYOUT, PC_H2D, PC_D2H, PC_COUNT
+  PC_CONV_FIRST, PC_CONV_DIRECT, PC_CONV_F64, PC_POOL, PC_DECONV, PC_TAIL, PC_MERGE, PC_LAYOUT, PC_H2D, PC_D2H, PC_COUNT
 };
 
 // ---- convolution (stride 1, "same" geometry: pad == dil*(k-1)/2) ------------
@@ -62,6 +62,8 @@ struct ConvArgs {
                   // activations in HBM, no fp16 range guard and no activation exponent (bf16 has fp32's range)
   int nprod = 3;  // split-fp16 kernels: fp16 products formed per fp32 product -- 3 (hi*hi + hi*lo + lo*hi: fp32-class),
                   // 2 (drops a_lo*b_hi: activations effectively fp16) or 1 (hi*hi only: plain fp16 operands)
+  int f64 = 0;    // conv mode "f64": binary64 accumulation on the fp64 matrix cores from the raw weights (conv_f64.h); `img`
+                  // then marks a first layer (the NCHW image is its input)
   int* range_flag = nullptr;  // split-fp16 kernels raise it when an output leaves the fp16 range (net_forward.cpp: fp32 re-run)
   // activation-exponent slots (conv_common.h ConvMember): max |value| of the input blob as left by its producers, and
   // where this launch raises the max of what it writes (main output / fused pool output); null = not tracked
@@ -115,6 +117,9 @@ int launch_amax_raise(unsigned* dst, const unsigned* src, hipStream_t s);
 // depthwise transposed conv (group == C), weights (C,1,k,k) Caffe layout
 int launch_deconv_depthwise(const View& in, const View& out, const float* w, const float* bias, int k,
                             int stride, int pad, hipStream_t s, int* range_flag = nullptr, unsigned* out_amax = nullptr);
+// conv mode "f64": the same sum in binary64, rounded once to fp32 (any batch; one thread per output value)
+int launch_deconv_depthwise_f64(const View& in, const View& out, const float* w, const float* bias, int k, int stride,
+                                int pad, hipStream_t s);
 int launch_deconv_depthwise_group(const View* ins, const View* outs, int n, const float* w, const float* bias, int k,
                                   int stride, int pad, hipStream_t s, int* range_flag = nullptr,
                                   unsigned* const* out_amax = nullptr);
@@ -146,6 +151,7 @@ struct TailArgs {
   // optional materialised Caffe blobs (NCHW), may be null
   float* cls_prob_reshape_nchw = nullptr;  // (1,2A,h,w)
   float* bbox_pred_nchw = nullptr;         // (1,4A,h,w)
+  int f64 = 0;               // conv mode "f64": the predictors' dot products accumulate in binary64, one rounding to fp32
   int probs_given = 0;       // diagnostics: the logits workspace already holds bg/fg probabilities (launch_tail_inject)
 };
 struct TailWork {  // device workspace owned by the net, sized for the largest level seen

@@ -9,6 +9,7 @@
 #include <math.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "shf_internal.h"
 
@@ -73,7 +74,11 @@ struct TailGK {
 };
 
 // ---- 1x1 cls/reg convs: wave handles two pixels, 32 lanes x float4 per pixel -------------
+// F64 (conv mode "f64"): the products and the sum in binary64 (a product of two fp32 values is exact there), the bias added
+// in binary64, ONE rounding to fp32
+template <bool F64>
 __global__ __launch_bounds__(256) void tail_logits_kernel(TailGK g) {
+  typedef typename std::conditional<F64, double, float>::type acc_t;
   const int mi = tail_find_member(g.blk_start, blockIdx.x);
   const TailGM& p = g.m[mi];
   const int lb = blockIdx.x - g.blk_start[mi], lgrid = g.blk_start[mi + 1] - g.blk_start[mi];
@@ -87,14 +92,17 @@ __global__ __launch_bounds__(256) void tail_logits_kernel(TailGK g) {
     const int fs = p.fstride[a];
     for (long long pr = wave; pr < npairs; pr += nwaves) {
       const long long k = pr * 2 + sub;
-      float part[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      acc_t part[6] = {0, 0, 0, 0, 0, 0};
       if (k < p.K) {
         for (int c0 = 0; c0 < g.Cf; c0 += 128) {
           const float4 x = *(const float4*)(f + (size_t)k * fs + c0 + q * 4);
 #pragma unroll
           for (int o = 0; o < 6; ++o) {
             const float4 wv = *(const float4*)(g.Wt + ((size_t)a * 6 + o) * g.Cf + c0 + q * 4);
-            part[o] += x.x * wv.x + x.y * wv.y + x.z * wv.z + x.w * wv.w;
+            if constexpr (F64)
+              part[o] += (double)x.x * (double)wv.x + (double)x.y * (double)wv.y + (double)x.z * (double)wv.z + (double)x.w * (double)wv.w;
+            else
+              part[o] += x.x * wv.x + x.y * wv.y + x.z * wv.z + x.w * wv.w;
           }
         }
       }
@@ -103,6 +111,12 @@ __global__ __launch_bounds__(256) void tail_logits_kernel(TailGK g) {
       // lane 8 / 4 places round the 16-lane row (DPP row_ror), and steps 2 / 1 are quad permutes: the same tree, the same bits
 #pragma unroll
       for (int o = 0; o < 6; ++o) {
+        if constexpr (F64) {
+          double v = part[o];
+#pragma unroll
+          for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+          part[o] = v;
+        } else {
         float v = part[o];
         v += __shfl_xor(v, 16, 64);
         v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));   // row_ror:8
@@ -110,13 +124,14 @@ __global__ __launch_bounds__(256) void tail_logits_kernel(TailGK g) {
         v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, false));    // quad_perm [2,3,0,1]
         v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));    // quad_perm [1,0,3,2]
         part[o] = v;
+        }
       }
       if (q == 0 && k < p.K) {
         float* L = p.logits + ((size_t)k * g.A + a) * 6;
         bool of = false;
 #pragma unroll
         for (int o = 0; o < 6; ++o) {
-          const float v = part[o] + g.bt[a * 6 + o];
+          const float v = (float)(part[o] + (acc_t)g.bt[a * 6 + o]);
           L[o] = v;
           if (o >= 4) of |= delta_overflows(v, o == 4 ? g.aw[a] : g.ah[a]);
         }
@@ -463,7 +478,7 @@ int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* ou
     const long long total = (long long)as[m].h * as[m].w * as[m].A;
     if ((size_t)total > wss[m]->cap_anchors) { set_error("tail: workspace too small"); return -1; }
     if (as[m].Cf % 128) { set_error("tail: head feature width must be a multiple of 128"); return -1; }
-    if (as[m].A != a0.A || as[m].Cf != a0.Cf || as[m].wcls[0] != a0.wcls[0]) {
+    if (as[m].A != a0.A || as[m].Cf != a0.Cf || as[m].wcls[0] != a0.wcls[0] || as[m].f64 != a0.f64) {
       set_error("tail group: members must share the proposal layer");
       return -1;
     }
@@ -497,7 +512,10 @@ int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* ou
       blocks += (int)grid_for(((long long)g.K + 1) / 2 * 64);
     }
     lk.blk_start[n] = blocks;
-    hipLaunchKernelGGL(tail_logits_kernel, dim3(blocks), dim3(256), 0, s, lk);
+    if (a0.f64)
+      hipLaunchKernelGGL(tail_logits_kernel<true>, dim3(blocks), dim3(256), 0, s, lk);
+    else
+      hipLaunchKernelGGL(tail_logits_kernel<false>, dim3(blocks), dim3(256), 0, s, lk);
     // from here on the tails only touch their own workspaces: the head feature maps may be overwritten
     if (after_logits) SHF_HIP_OK(hipEventRecord(after_logits, s));
   }
