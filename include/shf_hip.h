@@ -71,6 +71,21 @@ int shf_blob_shape(shf_net* net, int blob, int* dims);
  * syncs device->host (NHWC->NCHW) if the device copy is newer, marks host as head.
  * The pointer stays valid until the blob grows. */
 float* shf_blob_mutable_host_data(shf_net* net, int blob);
+/* Blob::set_gpu_data               caffe/src/caffe/blob.cpp:114-121 -> SyncedMemory::set_gpu_data syncedmem.cpp:121-134, with
+ * forward_net's pad and detect()'s flip (lib/test.py:35-38,150) folded in: src_dev is an (n, c, h, w) fp32 NCHW contiguous
+ * block in DEVICE memory; it lands in the (n, c, H, W) input blob mirrored along x when flip = 1, every element below h /
+ * right of w written as +0.0f (csrc/blob_io.hip pad_flip_nchw_kernel, enqueued on the net's stream).  The device copy becomes
+ * the blob's head (a later shf_blob_mutable_host_data reads it back).  Refused with a message, before anything is launched:
+ * a blob that is not a 4-D net input, a NULL source, n / c other than the blob's, h / w below 1 or above the blob's, flip
+ * outside {0, 1}.  The source must be complete when the call is made and stay alive until the net next synchronises. */
+int shf_blob_load_device(shf_net* net, int blob, const float* src_dev, int n, int c, int h, int w, int flip);
+/* Blob.gpu_data()                  caffe/src/caffe/blob.cpp:108-111 -> SyncedMemory::gpu_data syncedmem.cpp:110-119 (to_gpu
+ * :66-91; pycaffe's Blob._gpu_data_ptr, _caffe.cpp:468-470): a DEVICE pointer to the blob's fp32 NCHW image (inputs:
+ * uploaded first when the host copy is newer; NHWC activations: transposed into the blob's staging buffer), valid until
+ * the next forward, reshape or load on this net.  The net's stream is synchronised before the call returns, so a consumer
+ * on any stream may read.  NULL with a message for a tail-fused blob (read those through shf_blob_mutable_host_data), a
+ * blob that was never forwarded or written, and a blob with zero elements. */
+const float* shf_blob_device_data(shf_net* net, int blob);
 /* Net._forward(0, n-1)             _caffe.cpp:414 -> Net::ForwardFromTo net.cpp:516 */
 int shf_net_forward(shf_net* net);
 
@@ -120,6 +135,11 @@ void shf_alloc_counts(long long* device_allocs, long long* pinned_host_allocs);
  * fp32 blob; lvl_h / lvl_w from shf_pyramid_level_shape.  The reference calls a native library (OpenCV) at this point too. */
 int shf_image_blobs(const uint8_t* im_bgr_host, int im_h, int im_w, int n, const double* scales, const double* pixel_means,
                     float* const* out_host, const int* lvl_h, const int* lvl_w);
+/* The same with the levels written straight to caller-owned DEVICE buffers (a torch allocation, say) and nothing copied
+ * back: out_dev[i] receives the unpadded, unflipped (1,3,lvl_h[i],lvl_w[i]) fp32 blob.  Same argument checks, same kernel,
+ * same stream; synchronised before the call returns.  Feed the levels to a net with shf_blob_load_device. */
+int shf_image_blobs_device(const uint8_t* im_bgr_host, int im_h, int im_w, int n, const double* scales,
+                           const double* pixel_means, float* const* out_dev, const int* lvl_h, const int* lvl_w);
 /* PCI bus id ("0000:c5:00.0") of the device the runtime is set to (shf_set_device; caffe.set_device,
  * caffe/python/caffe/_caffe.cpp:394-396), so that a host-side sampler can find the card's sysfs hwmon files (clock, socket
  * power) without a GPU call of its own.  Measurement only (bench.py `telemetry`). */

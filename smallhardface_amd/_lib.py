@@ -83,6 +83,8 @@ def _declare(lib):
         "shf_blob_reshape": (ci, [vp, ci, ip, ci]),
         "shf_blob_shape": (ci, [vp, ci, ip]),
         "shf_blob_mutable_host_data": (fp, [vp, ci]),
+        "shf_blob_load_device": (ci, [vp, ci, vp, ci, ci, ci, ci, ci]),
+        "shf_blob_device_data": (vp, [vp, ci]),
         "shf_net_forward": (ci, [vp]),
         "shf_net_set_proposal_cfg": (ci, [vp, ci, cf, cf]),
         "shf_net_set_conv_mode": (ci, [vp, ci]),
@@ -91,6 +93,7 @@ def _declare(lib):
         "shf_alloc_counts": (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
         "shf_device_pci_bus_id": (ci, [C.c_char_p, ci]),
         "shf_image_blobs": (ci, [vp, ci, ci, ci, dp, dp, C.POINTER(vp), ip, ip]),
+        "shf_image_blobs_device": (ci, [vp, ci, ci, ci, dp, dp, C.POINTER(vp), ip, ip]),
         "shf_net_set_layer_products": (ci, [vp, C.c_char_p, ci]),
         "shf_net_record_event": (ci, [vp]),
         "shf_net_wait_event": (ci, [vp, vp]),

@@ -24,6 +24,7 @@ SOURCES = [
     ("tail.hip", ["-ffp-contract=off"]),
     ("merge.hip", ["-ffp-contract=off"]),
     ("pre.hip", ["-ffp-contract=off"]),
+    ("blob_io.hip", []),
     ("eval.hip", ["-ffp-contract=off"]),
     ("calib.hip", []),
     ("net_graph.cpp", []),
@@ -32,7 +33,7 @@ SOURCES = [
     ("net_api.cpp", []),
 ]
 HEADERS = ["shf_internal.h", "conv_common.h", "conv_f16x3_types.h", "conv_f16x3_8w.h", "conv_f16x3_w4d.h", "conv_f16x3_pc.h", "conv_f16x3_k1.h", "conv_f16x3_h3.h", "conv_f64.h",
-           "proto_text.h", "net_internal.h", "eval.h", os.path.join("..", "..", "include", "shf_hip.h")]
+           "proto_text.h", "net_internal.h", "eval.h", "blob_io.h", os.path.join("..", "..", "include", "shf_hip.h")]
 
 
 def _newer(target, deps):

@@ -8,6 +8,7 @@ reference's inference driver touches:
   net.forward(**inputs) + its two exceptions  pycaffe.py:88-134
   Blob.data (writable zero-copy fp32 view), .shape, .reshape(*dims), .count/.num/...
                                               _caffe.cpp:222-256,453-477
+  Blob.device / Blob.load_device (DeviceArray) Blob::gpu_data / set_gpu_data blob.cpp:108-121, _caffe.cpp:468-470
   caffe.Layer (param_str / phase attributes)  include/caffe/layers/python_layer.hpp:27-30
 
 Solvers, backward, forward_all, io, Classifier, NCCL are not part of the hot path.
@@ -23,7 +24,7 @@ from .. import _lib
 TRAIN = 0
 TEST = 1
 
-__all__ = ["Net", "Blob", "Layer", "TEST", "TRAIN", "set_mode_gpu", "set_mode_cpu", "set_device"]
+__all__ = ["Net", "Blob", "DeviceArray", "Layer", "TEST", "TRAIN", "set_mode_gpu", "set_mode_cpu", "set_device"]
 
 
 def set_mode_gpu():
@@ -64,6 +65,87 @@ class Layer(object):
         pass
 
 
+_FLIP_X = (Ellipsis, slice(None, None, -1))
+
+
+class DeviceArray(object):
+    """An fp32, C-contiguous, 4-D NCHW block in DEVICE memory: what ``Blob.load_device`` / ``Net.forward`` take and
+    ``Blob.device`` returns (pycaffe: Blob.gpu_data() / set_gpu_data()).  It holds a pointer, a shape, a reference to
+    whatever owns the memory and a ``flipped`` flag -- nothing is ever copied or launched here.
+
+    Built from any object with ``__cuda_array_interface__`` (a torch tensor on the GPU has one); a wrong dtype,
+    non-contiguous strides or ``ndim != 4`` is a ValueError.  ``a[..., ::-1]`` -- the only indexing detect() needs
+    (lib/test.py:150) -- returns a view with ``flipped`` toggled; the mirroring itself happens when the view is loaded
+    into a blob.  While unflipped the array exposes ``__cuda_array_interface__`` itself, so
+    ``torch.as_tensor(a, device="cuda")`` is zero-copy."""
+
+    def __init__(self, src, flipped=False):
+        if isinstance(src, DeviceArray):
+            self.ptr, self.shape, self.owner = src.ptr, src.shape, src.owner
+            self.flipped = bool(src.flipped) != bool(flipped)
+            self._complete, self._blob = src._complete, src._blob
+            return
+        cai = getattr(src, "__cuda_array_interface__", None)
+        if cai is None:
+            raise TypeError("DeviceArray needs an object with __cuda_array_interface__, got %s" % type(src).__name__)
+        shape = tuple(int(d) for d in cai["shape"])
+        if cai.get("typestr") not in ("<f4", "=f4"):
+            raise ValueError("DeviceArray holds float32, got typestr %r" % (cai.get("typestr"),))
+        if len(shape) != 4:
+            raise ValueError("DeviceArray holds a 4-D NCHW block, got %d axes" % len(shape))
+        strides = cai.get("strides")
+        if strides is not None:
+            want, acc = [], 4
+            for d in reversed(shape):
+                want.append(acc)
+                acc *= d
+            # (an axis of length 1 may carry any stride)
+            if any(d != 1 and int(st) != w for d, st, w in zip(shape, strides, reversed(want))):
+                raise ValueError("DeviceArray needs C-contiguous memory, got strides %r for shape %r" % (tuple(strides), shape))
+        self.ptr = int(cai["data"][0])
+        self.shape = shape
+        self.owner = src
+        self.flipped = bool(flipped)
+        self._complete = False    # True for a block the runtime itself produced and synchronised: no wait on torch's stream
+        self._blob = None         # (net, blob index) when this is a blob's own device image (Blob.device)
+
+    @classmethod
+    def _wrap(cls, ptr, shape, owner, blob=None):
+        """A block the runtime itself produced and synchronised (any number of axes: Blob.device of a 2-D blob)."""
+        a = cls.__new__(cls)
+        a.ptr, a.shape, a.owner, a.flipped = int(ptr), tuple(int(d) for d in shape), owner, False
+        a._complete, a._blob = True, blob
+        return a
+
+    def __getitem__(self, key):
+        if isinstance(key, tuple) and len(key) == 2 and key[0] is Ellipsis and key[1] == _FLIP_X[1]:
+            return DeviceArray(self, flipped=True)
+        raise TypeError("DeviceArray supports only a[..., ::-1] (the horizontal flip); use numpy() or torch.as_tensor() "
+                        "for anything else")
+
+    def __getattr__(self, name):
+        # exposed only while unflipped: a mirrored view is not describable by (pointer, shape, positive strides)
+        if name == "__cuda_array_interface__" and not self.__dict__.get("flipped", True):
+            return {"shape": self.shape, "typestr": "<f4", "data": (self.ptr, False), "version": 2, "strides": None}
+        raise AttributeError(name)
+
+    @property
+    def ndim(self):
+        return len(self.shape)
+
+    def numpy(self):
+        """A host copy (the flip applied)."""
+        import torch
+        plain = DeviceArray(self, flipped=self.flipped)    # the unflipped view of the same memory
+        if not self._complete:
+            torch.cuda.current_stream().synchronize()
+        a = torch.as_tensor(plain, device="cuda").cpu().numpy()
+        return np.ascontiguousarray(a[..., ::-1]) if self.flipped else a
+
+    def __repr__(self):
+        return "DeviceArray(ptr=0x%x, shape=%r%s)" % (self.ptr, self.shape, ", flipped" if self.flipped else "")
+
+
 class Blob(object):
     def __init__(self, net, index, name):
         self._net = net
@@ -94,6 +176,35 @@ class Blob(object):
         a.flags.writeable = True
         self._keep = self._net  # the view borrows from the net
         return a
+
+    @property
+    def device(self):
+        """The blob's fp32 NCHW image in device memory (Blob.gpu_data(), C ABI shf_blob_device_data), valid until the next
+        forward, reshape or load on this net.  Tail-fused blobs have none (ShfError naming the blob): read their ``data``."""
+        p = self._net._lib.shf_blob_device_data(self._net._h, self._i)
+        if not p:
+            raise _lib.ShfError(_lib.last_error())
+        return DeviceArray._wrap(p, self.shape, self._net, blob=(self._net, self._i))
+
+    def load_device(self, src, flip=False):
+        """Blob::set_gpu_data for a net input, with forward_net's zero pad and detect()'s flip folded in (C ABI
+        shf_blob_load_device): ``src`` -- a DeviceArray or anything it accepts -- of shape (n, c, h <= H, w <= W) lands in
+        this (n, c, H, W) blob, mirrored along x when ``flip`` XOR the source's own ``flipped``.  The net keeps ``src``
+        alive until its next forward has returned."""
+        a = src if isinstance(src, DeviceArray) else DeviceArray(src)
+        if a.ndim != 4:
+            raise ValueError("load_device needs a 4-D NCHW block, got shape %r" % (a.shape,))
+        if a._blob is not None and a._blob[0] is self._net and a._blob[1] == self._i:
+            if a.flipped != bool(flip):
+                raise ValueError("load_device cannot mirror blob '%s' into itself: copy its device image first" % self.name)
+            return    # the blob's own device image: already in place
+        if not a._complete:
+            import torch
+            torch.cuda.current_stream().synchronize()    # the producer's kernels: the source must be complete
+        n, c, h, w = a.shape
+        _lib.check(self._net._lib.shf_blob_load_device(self._net._h, self._i, C.c_void_p(a.ptr), n, c, h, w,
+                                                       1 if bool(a.flipped) != bool(flip) else 0), "Blob.load_device")
+        self._net._dev_sources.append(a)
 
     @property
     def count(self):
@@ -144,6 +255,7 @@ class Net(object):
         self._layer_names = [L.shf_net_layer_name(self._h, i).decode() for i in range(L.shf_net_num_layers(self._h))]
         self._layer_types = [L.shf_net_layer_type(self._h, i).decode() for i in range(L.shf_net_num_layers(self._h))]
         self._dirty_layers = set()
+        self._dev_sources = []    # device sources of Blob.load_device, kept alive until the next forward has returned
         self._apply_cfg()
 
     def clone(self):
@@ -159,6 +271,7 @@ class Net(object):
             setattr(lane, k, getattr(self, k))
         lane._blobs = [Blob(lane, i, n) for i, n in enumerate(lane._blob_names)]
         lane._dirty_layers = set()
+        lane._dev_sources = []
         return lane
 
     def _apply_cfg(self):
@@ -242,7 +355,10 @@ class Net(object):
     def _forward(self, start=0, end=None):
         self.commit_params()
         self._apply_cfg()
-        _lib.check(self._lib.shf_net_forward(self._h), "Net.forward")
+        try:
+            _lib.check(self._lib.shf_net_forward(self._h), "Net.forward")
+        finally:
+            del self._dev_sources[:]    # (forward synchronises: the loads' kernels are done with their sources)
 
     def forward(self, blobs=None, start=None, end=None, **kwargs):
         """pycaffe.py:88-134 (whole-net forward only: start/end are not supported)."""
@@ -257,8 +373,22 @@ class Net(object):
             if set(kwargs.keys()) != set(self.inputs):
                 raise Exception('Input blob arguments do not match net inputs.')
             for in_, blob in kwargs.items():
+                if not isinstance(blob, (np.ndarray, DeviceArray)) and hasattr(blob, "__cuda_array_interface__"):
+                    blob = DeviceArray(blob)    # e.g. a torch tensor on the GPU
                 if blob.shape[0] != self.blobs[in_].shape[0]:
                     raise Exception('Input is not batch sized')
+                if isinstance(blob, DeviceArray):
+                    b = self.blobs[in_]
+                    if tuple(blob.shape) != tuple(b.shape):
+                        fmt = lambda sh: "(%s)" % ",".join(str(int(d)) for d in sh)
+                        raise ValueError("could not broadcast input array from shape %s into shape %s"
+                                         % (fmt(blob.shape), fmt(b.shape)))
+                    # (the blob's own device image -- test.forward_net after Blob.load_device -- is already in place)
+                    own = (not blob.flipped and blob._blob is not None and blob._blob[0] is self
+                           and blob._blob[1] == b._i and blob.ptr == b.device.ptr)
+                    if not own:
+                        b.load_device(blob)
+                    continue
                 dst = self.blobs[in_].data
                 # (a caller that filled the blob's own host mirror in place -- test.forward_net -- hands that view back)
                 if not (isinstance(blob, np.ndarray) and blob.ctypes.data == dst.ctypes.data and blob.shape == dst.shape
@@ -271,7 +401,7 @@ class Net(object):
         if tm is not None:
             t3 = time.perf_counter()
             tm["calls"] = tm.get("calls", 0) + 1
-            tm["input_copy_s"] = tm.get("input_copy_s", 0.0) + (t1 - t0)     # host blob -> the pinned mirror (Blob.data[...] = x)
+            tm["input_copy_s"] = tm.get("input_copy_s", 0.0) + (t1 - t0)     # host blob -> the pinned mirror (Blob.data[...] = x), or a DeviceArray's load
             tm["forward_call_s"] = tm.get("forward_call_s", 0.0) + (t2 - t1)  # shf_net_forward: H2D + kernels + the count read-back
             tm["output_read_s"] = tm.get("output_read_s", 0.0) + (t3 - t2)   # Blob.data of the outputs: D2H
         return out

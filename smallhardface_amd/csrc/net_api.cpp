@@ -13,6 +13,7 @@
 //     one fused device-side tail (no D2H, no Python re-entry);
 //   * buffers are grow-only and shape changes re-plan nothing but pointers/sizes.
 #include "net_internal.h"
+#include "blob_io.h"
 #include "eval.h"
 
 namespace shf {
@@ -182,6 +183,44 @@ float* shf_blob_mutable_host_data(shf_net* net, int blob) {
   API_END(nullptr)
 }
 
+// Blob::set_gpu_data with forward_net's pad and detect()'s flip folded in: a level that is already in HBM lands in the
+// input blob through blob_io.hip's pad_flip_nchw_kernel on the net's stream, and the device copy becomes the blob's head.
+int shf_blob_load_device(shf_net* net, int blob, const float* src_dev, int n, int c, int h, int w, int flip) {
+  API_BEGIN
+  if (blob < 0 || blob >= (int)net->blobs.size()) throw std::runtime_error("bad blob index");
+  Blob& b = net->blobs[blob];
+  const std::string what = "blob_load_device: blob '" + b.name + "' ";
+  if (!std::count(net->inputs.begin(), net->inputs.end(), blob) || b.shape.size() != 4)
+    throw std::runtime_error(what + "is not a 4-D net input");
+  if (!src_dev) throw std::runtime_error(what + "got a NULL source");
+  if (n != b.shape[0] || c != b.shape[1])
+    throw std::runtime_error(what + "is (" + std::to_string(b.shape[0]) + ", " + std::to_string(b.shape[1]) +
+                             ", ...), the source (" + std::to_string(n) + ", " + std::to_string(c) + ", ...)");
+  if (h < 1 || w < 1 || h > b.shape[2] || w > b.shape[3])
+    throw std::runtime_error(what + "holds " + std::to_string(b.shape[2]) + " x " + std::to_string(b.shape[3]) +
+                             " planes, the source has " + std::to_string(h) + " x " + std::to_string(w));
+  if (flip != 0 && flip != 1) throw std::runtime_error(what + "flip must be 0 or 1");
+  if (b.count() == 0) throw std::runtime_error(what + "has zero elements");
+  b.dev.ensure(b.count() * 4);
+  {
+    ProfScope ps(net->prof, net->stream, PC_LAYOUT, 0, 4.0 * ((double)n * c * h * w + (double)b.count()));
+    CHECK_RC(launch_pad_flip_nchw(src_dev, n, c, h, w, (float*)b.dev.p, b.shape[2], b.shape[3], flip, net->stream));
+  }
+  b.host_newer = false;
+  b.dev_newer = true;
+  b.ext_dev = nullptr;
+  net->inputs_reshaped = true;   // (as after a reshape: the intermediates of the last forward no longer belong to this input)
+  return 0;
+  API_END(-1)
+}
+
+const float* shf_blob_device_data(shf_net* net, int blob) {
+  API_BEGIN
+  if (blob < 0 || blob >= (int)net->blobs.size()) throw std::runtime_error("bad blob index");
+  return net->device_data(blob);
+  API_END(nullptr)
+}
+
 int shf_net_forward(shf_net* net) {
   API_BEGIN
   net->forward();
@@ -255,14 +294,16 @@ void shf_alloc_counts(long long* device_allocs, long long* pinned_host_allocs) {
 
 static void box_ctx_init();
 
-// _get_image_blob of a whole scale list for callers that work with HOST blobs (lib/test.py's detect(): the reference calls
-// cv2.resize here -- a native library as well): the uint8 image goes up once, every level is formed by pre.hip's kernel
-// (the arithmetic of the host mirror, bit for bit) on the box context's stream and comes back as an UNPADDED (1,3,h,w) blob.
-int shf_image_blobs(const uint8_t* im_bgr_host, int im_h, int im_w, int n, const double* scales, const double* pixel_means,
-                    float* const* out_host, const int* lvl_h, const int* lvl_w) {
+// _get_image_blob of a whole scale list (lib/test.py's detect(): the reference calls cv2.resize here -- a native library as
+// well): the uint8 image goes up once and every level is formed by pre.hip's kernel (the arithmetic of the host mirror,
+// bit for bit) on the box context's stream, as an UNPADDED (1,3,h,w) blob.  `to_host`: the levels are formed in a buffer of
+// the runtime's and copied to out[i] on the host (shf_image_blobs); otherwise out[i] is a caller-owned DEVICE buffer and
+// the kernel writes there (shf_image_blobs_device).
+static int image_blobs(const char* who, const uint8_t* im_bgr_host, int im_h, int im_w, int n, const double* scales,
+                       const double* pixel_means, float* const* out, const int* lvl_h, const int* lvl_w, bool to_host) {
   API_BEGIN
-  if (!im_bgr_host || !scales || !pixel_means || !out_host || !lvl_h || !lvl_w || n < 1 || im_h < 1 || im_w < 1)
-    throw std::runtime_error("image_blobs: bad argument");
+  if (!im_bgr_host || !scales || !pixel_means || !out || !lvl_h || !lvl_w || n < 1 || im_h < 1 || im_w < 1)
+    throw std::runtime_error(std::string(who) + ": bad argument");
   std::lock_guard<std::mutex> lk(g_box_mu);
   box_ctx_init();
   static DevBuf* im_dev = new DevBuf();
@@ -270,23 +311,35 @@ int shf_image_blobs(const uint8_t* im_bgr_host, int im_h, int im_w, int n, const
   const size_t im_bytes = (size_t)im_h * im_w * 3;
   size_t total = 0;
   for (int i = 0; i < n; ++i) {
-    if (lvl_h[i] < 1 || lvl_w[i] < 1 || !(scales[i] > 0)) throw std::runtime_error("image_blobs: bad level geometry");
+    if (lvl_h[i] < 1 || lvl_w[i] < 1 || !(scales[i] > 0)) throw std::runtime_error(std::string(who) + ": bad level geometry");
+    if (!to_host && !out[i]) throw std::runtime_error(std::string(who) + ": NULL level buffer");
     total += (size_t)3 * lvl_h[i] * lvl_w[i];
   }
   im_dev->ensure(im_bytes);
-  lv_dev->ensure(total * 4);
+  if (to_host) lv_dev->ensure(total * 4);
   HIP_THROW(hipMemcpyAsync(im_dev->p, im_bgr_host, im_bytes, hipMemcpyHostToDevice, g_box_stream));
   size_t off = 0;
   for (int i = 0; i < n; ++i) {
-    float* o = (float*)lv_dev->p + off;
+    float* o = to_host ? (float*)lv_dev->p + off : out[i];
     CHECK_RC(launch_pyramid_level((const uint8_t*)im_dev->p, im_h, im_w, scales[i], 0, pixel_means, o, lvl_h[i], lvl_w[i],
                                   lvl_h[i], lvl_w[i], g_box_stream));
-    HIP_THROW(hipMemcpyAsync(out_host[i], o, (size_t)3 * lvl_h[i] * lvl_w[i] * 4, hipMemcpyDeviceToHost, g_box_stream));
+    if (to_host)
+      HIP_THROW(hipMemcpyAsync(out[i], o, (size_t)3 * lvl_h[i] * lvl_w[i] * 4, hipMemcpyDeviceToHost, g_box_stream));
     off += (size_t)3 * lvl_h[i] * lvl_w[i];
   }
   HIP_THROW(hipStreamSynchronize(g_box_stream));
   return 0;
   API_END(-1)
+}
+
+int shf_image_blobs(const uint8_t* im_bgr_host, int im_h, int im_w, int n, const double* scales, const double* pixel_means,
+                    float* const* out_host, const int* lvl_h, const int* lvl_w) {
+  return image_blobs("image_blobs", im_bgr_host, im_h, im_w, n, scales, pixel_means, out_host, lvl_h, lvl_w, true);
+}
+
+int shf_image_blobs_device(const uint8_t* im_bgr_host, int im_h, int im_w, int n, const double* scales,
+                           const double* pixel_means, float* const* out_dev, const int* lvl_h, const int* lvl_w) {
+  return image_blobs("image_blobs_device", im_bgr_host, im_h, im_w, n, scales, pixel_means, out_dev, lvl_h, lvl_w, false);
 }
 
 int shf_device_pci_bus_id(char* out, int cap) {

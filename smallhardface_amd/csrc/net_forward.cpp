@@ -397,6 +397,7 @@ void shf_net::forward() {
   // (tail-fused blobs too: "newer" for them means the tail workspace holds this forward's logits -- read on demand)
   for (size_t i = 0; i < blobs.size(); ++i)
     if (!std::count(inputs.begin(), inputs.end(), (int)i)) blobs[i].dev_newer = true;
+  forwarded = true;
 }
 
 // the intermediate blobs after a fast forward (see net_internal.h `plain_stale`): run the per-layer kernels once, in the
@@ -501,4 +502,44 @@ float* shf_net::host_data(int bi) {
   }
   if (is_input) b.host_newer = true;
   return b.host.p;
+}
+
+// Blob.gpu_data() (syncedmem.cpp:110-119): the blob's fp32 NCHW image as a device pointer, valid until the next forward,
+// reshape or load.  Inputs are their own NCHW buffer (uploaded first when the host copy is the head, to_gpu :76-83); flat
+// and NCHW-matrix blobs likewise; an NHWC activation is transposed into the staging buffer Blob.data uses.  The stream is
+// synchronised, so a consumer on any other stream may read.
+const float* shf_net::device_data(int bi) {
+  Blob& b = blobs[bi];
+  if (b.kind == BK_FUSED)
+    throw std::runtime_error("blob '" + b.name + "' is fused into the detection tail: it has no device image, read Blob.data");
+  const size_t n = b.count();
+  if (n == 0) throw std::runtime_error("blob '" + b.name + "' has zero elements");
+  const bool is_input = std::count(inputs.begin(), inputs.end(), bi) > 0;
+  const float* out = nullptr;
+  if (is_input) {
+    if (b.host_newer && b.host.p) {
+      b.dev.ensure(n * 4);
+      ProfScope ps(prof, stream, PC_H2D, 0, 4.0 * n);
+      HIP_THROW(hipMemcpyAsync(b.dev.p, b.host.p, n * 4, hipMemcpyHostToDevice, stream));
+      b.host_newer = false;
+    } else if (!b.dev_newer && !forwarded) {
+      throw std::runtime_error("blob '" + b.name + "' was never written: nothing to read on the device");
+    }
+    out = (const float*)b.dev.p;
+  } else {
+    if (!forwarded) throw std::runtime_error("blob '" + b.name + "' was never forwarded: nothing to read on the device");
+    if (b.kind == BK_NHWC) {
+      if (b.shape.size() != 4) throw std::runtime_error("blob '" + b.name + "': an activation with " + std::to_string(b.shape.size()) + " axes has no NCHW image");
+      ensure_plain();   // (after a fast forward: the activations are not plain fp32 tensors yet)
+      b.stage.ensure(n * 4);
+      ProfScope ps(prof, stream, PC_LAYOUT, 0, 8.0 * n);
+      CHECK_RC(launch_nhwc_to_nchw(view_of(bi), (float*)b.stage.p, stream));
+      out = (const float*)b.stage.p;
+    } else {
+      out = (const float*)b.dev.p;
+    }
+  }
+  if (!out) throw std::runtime_error("blob '" + b.name + "' has no device buffer");
+  HIP_THROW(hipStreamSynchronize(stream));
+  return out;
 }

@@ -421,6 +421,7 @@ struct shf_net {
   // unmaterialised: `plain_stale`.  Reading one of them (Blob.data) then runs the per-layer kernels once, everything but
   // the proposal tail (ensure_plain), so every name in net.blobs stays readable (pycaffe.py:24-32).
   bool plain_stale = false, inputs_reshaped = false;
+  bool forwarded = false;   // forward() has run: the non-input blobs hold an activation (device_data)
   float last_im_info[3] = {0.f, 0.f, 1.f};
   bool forward_fast_eligible() const;
   void ensure_plain();
@@ -489,6 +490,7 @@ struct shf_net {
   void ensure_img_cap(int units_after);
   void forward();
   float* host_data(int bi);
+  const float* device_data(int bi);   // Blob.gpu_data(): the blob's fp32 NCHW image on the device (shf_blob_device_data)
   void materialize_fused(int bi);   // Blob.data of a tail-fused blob, re-ordered on the host from the tail workspace
   void load_caffemodel(const std::string& path);
 };

@@ -26,7 +26,8 @@ import numpy as np
 from . import _lib, caffe
 from .config import cfg
 from .nms import bbox_vote, nms
-from .test_utils import _compute_scaling_factor, _get_image_blob, _get_image_blob_device, pyramid_scales
+from .test_utils import _compute_scaling_factor, _get_image_blob, pyramid_scales
+from .test_utils import _get_image_blob_device as _get_image_blob_host_out
 from .timer import Timer
 
 logger = logging.getLogger(__name__)
@@ -42,6 +43,41 @@ def _imread(path):
         return np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1].copy()
 
 
+def _get_image_blob_device(im, im_scales, on_device=False):
+    """``test_utils._get_image_blob_device`` (levels formed on the GPU, HOST blobs out: C ABI shf_image_blobs), and with
+    ``on_device=True`` the same levels -- unpadded, unflipped, the same shapes -- left in HBM (C ABI
+    shf_image_blobs_device): ONE torch device allocation holds them and they come back as ``{'data': caffe.DeviceArray}``
+    for ``forward_net`` to load into the net (Blob.load_device pads and flips them there); nothing is copied to the host
+    and sent back."""
+    if not on_device:
+        return _get_image_blob_host_out(im, im_scales)
+    import ctypes as C
+    import torch
+    lib = _lib.load()
+    im = np.ascontiguousarray(im, dtype=np.uint8)
+    h, w = im.shape[:2]
+    n = len(im_scales)
+    shapes = [caffe.pyramid_level_shape(h, w, s, 1)[:2] for s in im_scales]
+    counts = [3 * a * b for a, b in shapes]
+    buf = torch.empty(max(sum(counts), 1), dtype=torch.float32, device="cuda")
+    outs, off = [], 0
+    for (a, b), cnt in zip(shapes, counts):
+        outs.append(buf[off:off + cnt].view(1, 3, a, b))
+        off += cnt
+    pm = (C.c_double * 3)(*[float(v) for v in np.asarray(cfg.PIXEL_MEANS).reshape(-1)[:3]])
+    sc = (C.c_double * n)(*[float(s) for s in im_scales])
+    ptrs = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+    lh = (C.c_int * n)(*[s_[0] for s_ in shapes])
+    lw = (C.c_int * n)(*[s_[1] for s_ in shapes])
+    _lib.check(lib.shf_image_blobs_device(im.ctypes.data_as(C.c_void_p), h, w, n, sc, pm, ptrs, lh, lw), "image_blobs_device")
+    blobs = []
+    for o in outs:
+        a = caffe.DeviceArray(o)
+        a._complete = True    # shf_image_blobs_device synchronises: the level is complete, whatever torch's stream holds
+        blobs.append({'data': a})
+    return blobs
+
+
 def forward_net(net, blob, im_scale, pyramid=False, flip=False):
     """Run one (scale, flip) unit; returns ([probs (R,2)], [pred_boxes (R,8)])."""
     blob['im_info'] = np.array([[blob['data'].shape[2], blob['data'].shape[3], im_scale]], dtype=np.float32)
@@ -55,12 +91,18 @@ def forward_net(net, blob, im_scale, pyramid=False, flip=False):
     # test.py:35-38 zero-pads with np.pad and hands the copy to forward(), which copies it again into the blob: here the
     # (possibly flipped, i.e. negatively strided) level is written ONCE, straight into the blob's host mirror, the pad rows /
     # columns zeroed around it -- the same (n, c, new_h, new_w) tensor, two 24-MB copies per 1408 x 1408 unit fewer
-    data = net.blobs['data'].data
-    data[:, :, :h, :w] = blob['data']
-    if new_h > h:
-        data[:, :, h:, :] = 0
-    if new_w > w:
-        data[:, :, :h, w:] = 0
+    if isinstance(blob['data'], caffe.DeviceArray):
+        # a level that is already in HBM (SHF_DEVICE_LEVELS=1): padded -- and mirrored, for a [..., ::-1] view -- into the
+        # blob's device buffer by one kernel (Blob.load_device); forward() then finds the blob's own image and copies nothing
+        net.blobs['data'].load_device(blob['data'])
+        data = net.blobs['data'].device
+    else:
+        data = net.blobs['data'].data
+        data[:, :, :h, :w] = blob['data']
+        if new_h > h:
+            data[:, :, h:, :] = 0
+        if new_w > w:
+            data[:, :, :h, w:] = 0
     net_args = {'data': data,
                 'im_info': blob['im_info'].astype(np.float32, copy=False)}
     blobs_out = net.forward(**net_args)
@@ -133,8 +175,14 @@ def detect(net, im_path, thresh=0.05, timers=None, pyramid=False, im=None):
         pyramid_scales = [float(scale) / cfg.TEST.PYRAMID_BASE_SIZE[0] * base_scale for scale in cfg.TEST.SCALES]
         # (the reference: cv2.resize per level, a native library; here the same step on the GPU with host blobs out -- bit-equal
         # to the numpy mirror _get_image_blob, which SHF_HOST_PREPROCESS=1 selects)
-        im_blobs = (_get_image_blob if os.environ.get("SHF_HOST_PREPROCESS") == "1" or im.dtype != np.uint8 else
-                    _get_image_blob_device)(im, pyramid_scales)
+        if os.environ.get("SHF_HOST_PREPROCESS") == "1" or im.dtype != np.uint8:
+            im_blobs = _get_image_blob(im, pyramid_scales)
+        elif os.environ.get("SHF_DEVICE_LEVELS") == "1":
+            # the levels stay in HBM as caffe.DeviceArray and forward_net loads them into the net on the device: no level
+            # D2H, no pad / flip on the host, no level H2D -- the same tensors in the net, the same detections
+            im_blobs = _get_image_blob_device(im, pyramid_scales, on_device=True)
+        else:
+            im_blobs = _get_image_blob_device(im, pyramid_scales)
         for i in range(len(pyramid_scales)):
             probs, boxes = forward_net(net, im_blobs[i], pyramid_scales[i], pyramid=True)
             for j in range(len(probs)):
