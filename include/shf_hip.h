@@ -86,8 +86,32 @@ int shf_blob_load_device(shf_net* net, int blob, const float* src_dev, int n, in
  * on any stream may read.  NULL with a message for a tail-fused blob (read those through shf_blob_mutable_host_data), a
  * blob that was never forwarded or written, and a blob with zero elements. */
 const float* shf_blob_device_data(shf_net* net, int blob);
+/* The same for the SAME input blob of n nets in ONE launch (csrc/blob_io.hip pad_flip_nchw_group_kernel: an image's ten
+ * (scale, flip) units are ten such loads, seven of them launch-bound): member i's blob `blob` -- (n_i, c_i, H_i, W_i), its own
+ * shape -- receives src_dev[i], an (n_i, c_i, h[i], w[i]) block, mirrored when flip[i] = 1.  members: as for
+ * shf_net_forward_group.  The per-member checks and messages of shf_blob_load_device, prefixed "member <i>: "; ALL checks run
+ * before anything is allocated or launched, so a refused call changes no member.  The same state changes per member; the
+ * copy is enqueued on `net`'s stream (follow with shf_net_forward_group on the same `net`). */
+int shf_blob_load_device_group(shf_net* net, int n, shf_net** members, int blob, const float* const* src_dev,
+                               const int* h, const int* w, const int* flip);
 /* Net._forward(0, n-1)             _caffe.cpp:414 -> Net::ForwardFromTo net.cpp:516 */
 int shf_net_forward(shf_net* net);
+/* Net::ForwardFromTo (net.cpp:516) for EACH of n nets, run as ONE grouped pass: every convolution, the deconvolution and
+ * every stage of the proposal tail is one launch over the group (the walk shf_detect_add_levels runs), whatever the
+ * members' spatial sizes -- this is not a batch axis, every member keeps its own shapes and buffers.  members[i] is `net`
+ * itself and / or lanes of the same root (shf_net_clone), pairwise distinct, 1 <= n <= 16 (one kernel-argument member
+ * table).  `net` is the head of the pass: its stream, range flag and profiler serve it; work enqueued earlier on a member's
+ * own stream (shf_blob_load_device) is waited for at entry.  Per member everything shf_net_forward does: shapes re-inferred
+ * and buffers grown when the data shape changed, inputs uploaded whose host copy is newer, im_info read from the member's
+ * own blob.  On return every member is in the state shf_net_forward(member) would have left it in (output shapes from its
+ * own proposal count, every blob readable through shf_blob_mutable_host_data / shf_blob_device_data), its results bit for
+ * bit those of a single forward, and the host mirrors of its proposal outputs are already filled (the counts are known
+ * here: one synchronisation for the group instead of two read-backs per member).
+ * Range guard: a grouped pass has ONE flag.  When it is raised in a split-fp16 mode the WHOLE group is redone on the exact
+ * fp32 per-layer kernels -- members that did not overflow are redone too -- and shf_net_range_fallbacks goes up by one.
+ * Refused with a message, before anything is allocated or launched: n outside 1..16, a NULL member, duplicate members, a
+ * member that does not share `net`'s parameter tensors, a head on which shf_net_set_pipeline is enabled. */
+int shf_net_forward_group(shf_net* net, int n, shf_net** members);
 
 /* The in-graph Python layer reads cfg.TEST.{N_DETS_PER_MODULE,SCORE_THRESH,
  * ANCHOR_MIN_SIZE} from the global config (lib/layers/proposal_layer.py:88-92);

@@ -86,6 +86,8 @@ def _declare(lib):
         "shf_blob_load_device": (ci, [vp, ci, vp, ci, ci, ci, ci, ci]),
         "shf_blob_device_data": (vp, [vp, ci]),
         "shf_net_forward": (ci, [vp]),
+        "shf_net_forward_group": (ci, [vp, ci, C.POINTER(vp)]),
+        "shf_blob_load_device_group": (ci, [vp, ci, C.POINTER(vp), ci, C.POINTER(vp), ip, ip, ip]),
         "shf_net_set_proposal_cfg": (ci, [vp, ci, cf, cf]),
         "shf_net_set_conv_mode": (ci, [vp, ci]),
         "shf_net_get_conv_mode": (ci, [vp]),

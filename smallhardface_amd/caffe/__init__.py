@@ -9,6 +9,7 @@ reference's inference driver touches:
   Blob.data (writable zero-copy fp32 view), .shape, .reshape(*dims), .count/.num/...
                                               _caffe.cpp:222-256,453-477
   Blob.device / Blob.load_device (DeviceArray) Blob::gpu_data / set_gpu_data blob.cpp:108-121, _caffe.cpp:468-470
+  net.forward_group(members) / caffe.load_device_group   Net::ForwardFromTo net.cpp:516 for each of several lanes, one pass
   caffe.Layer (param_str / phase attributes)  include/caffe/layers/python_layer.hpp:27-30
 
 Solvers, backward, forward_all, io, Classifier, NCCL are not part of the hot path.
@@ -360,6 +361,37 @@ class Net(object):
         finally:
             del self._dev_sources[:]    # (forward synchronises: the loads' kernels are done with their sources)
 
+    def _stage_inputs(self, kwargs, deferred=None):
+        """forward(**kwargs)'s checks and input copies (pycaffe.py:108-117).  ``deferred`` (forward_group): a device input is
+        not loaded here but appended as (net, input name, DeviceArray), for one grouped load of all members."""
+        if set(kwargs.keys()) != set(self.inputs):
+            raise Exception('Input blob arguments do not match net inputs.')
+        for in_, blob in kwargs.items():
+            if not isinstance(blob, (np.ndarray, DeviceArray)) and hasattr(blob, "__cuda_array_interface__"):
+                blob = DeviceArray(blob)    # e.g. a torch tensor on the GPU
+            if blob.shape[0] != self.blobs[in_].shape[0]:
+                raise Exception('Input is not batch sized')
+            if isinstance(blob, DeviceArray):
+                b = self.blobs[in_]
+                if tuple(blob.shape) != tuple(b.shape):
+                    fmt = lambda sh: "(%s)" % ",".join(str(int(d)) for d in sh)
+                    raise ValueError("could not broadcast input array from shape %s into shape %s"
+                                     % (fmt(blob.shape), fmt(b.shape)))
+                # (the blob's own device image -- test.forward_net after Blob.load_device -- is already in place)
+                own = (not blob.flipped and blob._blob is not None and blob._blob[0] is self
+                       and blob._blob[1] == b._i and blob.ptr == b.device.ptr)
+                if not own:
+                    if deferred is not None:
+                        deferred.append((self, in_, blob))
+                    else:
+                        b.load_device(blob)
+                continue
+            dst = self.blobs[in_].data
+            # (a caller that filled the blob's own host mirror in place -- test.forward_net -- hands that view back)
+            if not (isinstance(blob, np.ndarray) and blob.ctypes.data == dst.ctypes.data and blob.shape == dst.shape
+                    and blob.strides == dst.strides):
+                dst[...] = blob
+
     def forward(self, blobs=None, start=None, end=None, **kwargs):
         """pycaffe.py:88-134 (whole-net forward only: start/end are not supported)."""
         if start is not None or end is not None:
@@ -370,30 +402,7 @@ class Net(object):
         tm = getattr(self, "timing", None)     # measurement only (bench.py net_forward_path): a dict collects host seconds
         t0 = time.perf_counter() if tm is not None else 0.0
         if kwargs:
-            if set(kwargs.keys()) != set(self.inputs):
-                raise Exception('Input blob arguments do not match net inputs.')
-            for in_, blob in kwargs.items():
-                if not isinstance(blob, (np.ndarray, DeviceArray)) and hasattr(blob, "__cuda_array_interface__"):
-                    blob = DeviceArray(blob)    # e.g. a torch tensor on the GPU
-                if blob.shape[0] != self.blobs[in_].shape[0]:
-                    raise Exception('Input is not batch sized')
-                if isinstance(blob, DeviceArray):
-                    b = self.blobs[in_]
-                    if tuple(blob.shape) != tuple(b.shape):
-                        fmt = lambda sh: "(%s)" % ",".join(str(int(d)) for d in sh)
-                        raise ValueError("could not broadcast input array from shape %s into shape %s"
-                                         % (fmt(blob.shape), fmt(b.shape)))
-                    # (the blob's own device image -- test.forward_net after Blob.load_device -- is already in place)
-                    own = (not blob.flipped and blob._blob is not None and blob._blob[0] is self
-                           and blob._blob[1] == b._i and blob.ptr == b.device.ptr)
-                    if not own:
-                        b.load_device(blob)
-                    continue
-                dst = self.blobs[in_].data
-                # (a caller that filled the blob's own host mirror in place -- test.forward_net -- hands that view back)
-                if not (isinstance(blob, np.ndarray) and blob.ctypes.data == dst.ctypes.data and blob.shape == dst.shape
-                        and blob.strides == dst.strides):
-                    dst[...] = blob
+            self._stage_inputs(kwargs)
         t1 = time.perf_counter() if tm is not None else 0.0
         self._forward()
         t2 = time.perf_counter() if tm is not None else 0.0
@@ -404,6 +413,53 @@ class Net(object):
             tm["input_copy_s"] = tm.get("input_copy_s", 0.0) + (t1 - t0)     # host blob -> the pinned mirror (Blob.data[...] = x), or a DeviceArray's load
             tm["forward_call_s"] = tm.get("forward_call_s", 0.0) + (t2 - t1)  # shf_net_forward: H2D + kernels + the count read-back
             tm["output_read_s"] = tm.get("output_read_s", 0.0) + (t3 - t2)   # Blob.data of the outputs: D2H
+        return out
+
+    def forward_group(self, members, inputs=None):
+        """``forward()`` of several nets as ONE grouped pass (C ABI shf_net_forward_group): every convolution, the
+        deconvolution and every stage of the proposal tail is one launch over the group, whatever the members' sizes -- the
+        levels of a pyramid in one pass.  ``members``: a list of distinct nets, ``self`` and / or lanes from ``self.clone()``
+        (at most 16); ``self`` is the head, whose stream carries the pass.  ``inputs``: None (the members' input blobs as
+        they stand) or one entry per member, each None or a dict of what ``forward(**kwargs)`` accepts -- numpy arrays,
+        DeviceArray, anything with ``__cuda_array_interface__`` --, under forward()'s checks and exception texts; the
+        device inputs of all members go in with one launch per input name.  Returns a list of {output name: Blob.data},
+        one per member.  Afterwards every member is an ordinary forwarded net: its results are bit for bit those of its
+        own ``forward()``, and every blob of it reads as after one."""
+        members = list(members)
+        n = len(members)
+        if inputs is None:
+            inputs = [None] * n
+        inputs = list(inputs)
+        if len(inputs) != n:
+            raise ValueError("forward_group: %d members but %d input dicts" % (n, len(inputs)))
+        tm = getattr(self, "timing", None)     # measurement only, as in forward()
+        t0 = time.perf_counter() if tm is not None else 0.0
+        self.commit_params()
+        self._apply_cfg()
+        try:
+            deferred = []
+            for m, kw in zip(members, inputs):
+                if kw:
+                    m._stage_inputs(kw, deferred)
+            for name in sorted(set(d[1] for d in deferred)):
+                sel = [d for d in deferred if d[1] == name]
+                _load_device_group(self, [d[0] for d in sel], name, [d[2] for d in sel], None)
+            t1 = time.perf_counter() if tm is not None else 0.0
+            mem = (C.c_void_p * max(n, 1))(*[getattr(m, "_h", None) for m in members])
+            _lib.check(self._lib.shf_net_forward_group(self._h, n, mem), "Net.forward_group")
+        finally:
+            for m in members:       # (forward_group synchronises: the loads' kernels are done with their sources)
+                if isinstance(m, Net):
+                    del m._dev_sources[:]
+        t2 = time.perf_counter() if tm is not None else 0.0
+        out = [{o: m.blobs[o].data for o in m.outputs} for m in members]
+        if tm is not None:
+            t3 = time.perf_counter()
+            tm["calls"] = tm.get("calls", 0) + 1
+            tm["units"] = tm.get("units", 0) + n
+            tm["input_copy_s"] = tm.get("input_copy_s", 0.0) + (t1 - t0)
+            tm["forward_call_s"] = tm.get("forward_call_s", 0.0) + (t2 - t1)
+            tm["output_read_s"] = tm.get("output_read_s", 0.0) + (t3 - t2)
         return out
 
     # -- measurement helpers ------------------------------------------------------
@@ -559,6 +615,58 @@ class Net(object):
             if n.value <= cap:
                 return out[:n.value]
             cap = n.value  # rare: more merged boxes than expected -> the merge is re-run
+
+
+def _load_device_group(head, nets, name, sources, flips):
+    nets, sources = list(nets), list(sources)
+    flips = [False] * len(nets) if flips is None else list(flips)
+    if not (len(nets) == len(sources) == len(flips)):
+        raise ValueError("load_device_group: %d nets, %d sources, %d flips" % (len(nets), len(sources), len(flips)))
+    todo, wait = [], False
+    for i, (net, src, flip) in enumerate(zip(nets, sources, flips)):
+        b = net.blobs[name]
+        a = src if isinstance(src, DeviceArray) else DeviceArray(src)
+        if a.ndim != 4:
+            raise ValueError("load_device needs a 4-D NCHW block, got shape %r" % (a.shape,))
+        if a._blob is not None and a._blob[0] is net and a._blob[1] == b._i:
+            if a.flipped != bool(flip):
+                raise ValueError("load_device cannot mirror blob '%s' into itself: copy its device image first" % b.name)
+            continue    # the blob's own device image: already in place
+        shp = b.shape
+        if len(shp) == 4 and tuple(a.shape[:2]) != tuple(shp[:2]):    # (the C entry takes n and c from the blob itself)
+            raise _lib.ShfError("load_device_group: member %d: blob_load_device: blob '%s' is (%d, %d, ...), the source (%d, %d, ...)"
+                                % (i, b.name, shp[0], shp[1], a.shape[0], a.shape[1]))
+        wait = wait or not a._complete
+        todo.append((net, b._i, a, 1 if bool(a.flipped) != bool(flip) else 0))
+    if not todo:
+        return
+    if len(set(t[1] for t in todo)) != 1:
+        raise ValueError("load_device_group: the nets do not hold blob '%s' at the same index (not lanes of one net)" % name)
+    if wait:
+        import torch
+        torch.cuda.current_stream().synchronize()    # the producers' kernels: the sources must be complete
+    n = len(todo)
+    mem = (C.c_void_p * n)(*[t[0]._h for t in todo])
+    src = (C.c_void_p * n)(*[t[2].ptr for t in todo])
+    ia = lambda v: (C.c_int * n)(*[int(x) for x in v])
+    _lib.check(head._lib.shf_blob_load_device_group(head._h, n, mem, todo[0][1], src, ia(t[2].shape[2] for t in todo),
+                                                    ia(t[2].shape[3] for t in todo), ia(t[3] for t in todo)),
+               "load_device_group")
+    for net, _, a, _f in todo:
+        net._dev_sources.append(a)
+
+
+def load_device_group(nets, name, sources, flips=None):
+    """``Blob.load_device`` for input blob ``name`` of several nets -- lanes of one net -- in ONE launch (C ABI
+    shf_blob_load_device_group), enqueued on the first net's stream: ``sources[i]`` (a DeviceArray or anything it accepts,
+    (n, c, h <= H, w <= W)) lands in ``nets[i].blobs[name]``, mirrored along x when ``flips[i]`` XOR the source's own
+    ``flipped``.  Blob.load_device's rules hold per net: a blob's own device image is left in place (and cannot be
+    mirrored into itself), torch's stream is waited for when a source is not known to be complete, and each net keeps
+    its source alive until its next forward has returned."""
+    nets = list(nets)
+    if not nets:
+        raise ValueError("load_device_group: no nets")
+    _load_device_group(nets[0], nets, name, sources, flips)
 
 
 def pyramid_level_shape(im_h, im_w, scale, max_resolution):

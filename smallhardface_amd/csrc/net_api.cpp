@@ -214,6 +214,58 @@ int shf_blob_load_device(shf_net* net, int blob, const float* src_dev, int n, in
   API_END(-1)
 }
 
+// shf_blob_load_device for the same input blob of n members in ONE launch (blob_io.hip pad_flip_nchw_group_kernel) on the
+// head's stream: every check of every member first, then the buffers, the launch and the state changes
+int shf_blob_load_device_group(shf_net* net, int n, shf_net** members, int blob, const float* const* src_dev, const int* h,
+                               const int* w, const int* flip) {
+  API_BEGIN
+  check_group("blob_load_device_group", net, n, members);
+  if (!src_dev || !h || !w || !flip) throw std::runtime_error("blob_load_device_group: NULL argument list");
+  if (blob < 0 || blob >= (int)net->blobs.size()) throw std::runtime_error("bad blob index");
+  for (int m = 0; m < n; ++m) {
+    shf_net* ln = members[m];
+    Blob& b = ln->blobs[blob];
+    const std::string what = "member " + std::to_string(m) + ": blob_load_device: blob '" + b.name + "' ";
+    if (!std::count(ln->inputs.begin(), ln->inputs.end(), blob) || b.shape.size() != 4)
+      throw std::runtime_error(what + "is not a 4-D net input");
+    if (!src_dev[m]) throw std::runtime_error(what + "got a NULL source");
+    if (h[m] < 1 || w[m] < 1 || h[m] > b.shape[2] || w[m] > b.shape[3])
+      throw std::runtime_error(what + "holds " + std::to_string(b.shape[2]) + " x " + std::to_string(b.shape[3]) +
+                               " planes, the source has " + std::to_string(h[m]) + " x " + std::to_string(w[m]));
+    if (flip[m] != 0 && flip[m] != 1) throw std::runtime_error(what + "flip must be 0 or 1");
+    if (b.count() == 0) throw std::runtime_error(what + "has zero elements");
+  }
+  PadFlipUnit u[kMaxGroup];
+  double bytes = 0;
+  for (int m = 0; m < n; ++m) {
+    Blob& b = members[m]->blobs[blob];
+    b.dev.ensure(b.count() * 4);
+    u[m] = {src_dev[m], (float*)b.dev.p, b.shape[0], b.shape[1], h[m], w[m], b.shape[2], b.shape[3], flip[m]};
+    bytes += 4.0 * ((double)b.shape[0] * b.shape[1] * h[m] * w[m] + (double)b.count());
+  }
+  // a member's own stream may still read or write its blob (an earlier single load, a read-back): ordered before this copy
+  for (int m = 0; m < n; ++m)
+    if (members[m]->stream != net->stream) HIP_THROW(hipStreamSynchronize(members[m]->stream));
+  {
+    ProfScope ps(net->prof, net->stream, PC_LAYOUT, 0, bytes);
+    CHECK_RC(launch_pad_flip_nchw_group(u, n, net->stream));
+  }
+  // ... and a member's later reads of its blob (Blob.data, Blob.device, its own forward) run on its own stream: behind it
+  if (!net->ev_group) HIP_THROW(hipEventCreateWithFlags(&net->ev_group, hipEventDisableTiming));
+  HIP_THROW(hipEventRecord(net->ev_group, net->stream));
+  for (int m = 0; m < n; ++m)
+    if (members[m]->stream != net->stream) HIP_THROW(hipStreamWaitEvent(members[m]->stream, net->ev_group, 0));
+  for (int m = 0; m < n; ++m) {
+    Blob& b = members[m]->blobs[blob];
+    b.host_newer = false;
+    b.dev_newer = true;
+    b.ext_dev = nullptr;
+    members[m]->inputs_reshaped = true;
+  }
+  return 0;
+  API_END(-1)
+}
+
 const float* shf_blob_device_data(shf_net* net, int blob) {
   API_BEGIN
   if (blob < 0 || blob >= (int)net->blobs.size()) throw std::runtime_error("bad blob index");
@@ -224,6 +276,13 @@ const float* shf_blob_device_data(shf_net* net, int blob) {
 int shf_net_forward(shf_net* net) {
   API_BEGIN
   net->forward();
+  return 0;
+  API_END(-1)
+}
+
+int shf_net_forward_group(shf_net* net, int n, shf_net** members) {
+  API_BEGIN
+  forward_group(net, n, members);
   return 0;
   API_END(-1)
 }

@@ -1,5 +1,6 @@
 // Net runtime, part 2: the layer walk (run_pass: one lane's unit, or one grouped pass over the units of several lanes),
-// Net.forward() with its fp32 redo, Blob.data read-back, and the profiler's kernel classes.
+// Net.forward() with its fp32 redo, the same for a group of lanes (forward_group), Blob.data read-back, and the profiler's
+// kernel classes.
 #include "net_internal.h"
 
 namespace shf {
@@ -280,6 +281,13 @@ void run_pass(const Pass& p) {
           }
           break;
         }
+        if (p.tail == TAIL_GROUP) {   // Net.forward() of a group: the tails as ONE launch per stage, all on the pass's stream
+          for (int m = 1; m < p.n; ++m) t[m].wcls[0] = t[0].wcls[0], t[m].bcls[0] = t[0].bcls[0];  // lanes hold identical copies
+          const auto c = cost(li, 0, p.n, 1);
+          ProfScope ps(h.prof, p.s, PC_TAIL, c.first, c.second);
+          CHECK_RC(launch_tail_group(t, tws, boxes, probs, p.n, p.s, nullptr, 0));
+          break;
+        }
         // TAIL_HANDOVER: the tails of all units as ONE launch per stage (counters reset, logits, decode, sort stages,
         // gather): ~15 launches per image instead of ~100.  Phase 1 (reset + logits) is what reads the feature maps and
         // runs on the layers' stream; phase 2 works on the lanes' tail workspaces only and runs on the head's stream.
@@ -398,6 +406,135 @@ void shf_net::forward() {
   for (size_t i = 0; i < blobs.size(); ++i)
     if (!std::count(inputs.begin(), inputs.end(), (int)i)) blobs[i].dev_newer = true;
   forwarded = true;
+}
+
+// shf_net_forward_group's refusals: argument checks only, nothing is allocated or launched
+void check_group(const char* who, shf_net* head, int n, shf_net* const* members) {
+  const std::string w = std::string(who) + ": ";
+  if (!head) throw std::runtime_error(w + "NULL net");
+  if (n < 1 || n > kMaxGroup)
+    throw std::runtime_error(w + std::to_string(n) + " members: a group holds 1.." + std::to_string(kMaxGroup));
+  if (!members) throw std::runtime_error(w + "NULL member list");
+  for (int m = 0; m < n; ++m) {
+    if (!members[m]) throw std::runtime_error(w + "member " + std::to_string(m) + " is NULL");
+    for (int q = 0; q < m; ++q)
+      if (members[q] == members[m])
+        throw std::runtime_error(w + "members " + std::to_string(q) + " and " + std::to_string(m) + " are the same net: members must be distinct");
+    // lanes of one root share its NetShared and its parameter generation counter (shf_net_clone)
+    if (members[m]->sh != head->sh || members[m]->wgen != head->wgen || members[m]->layers.size() != head->layers.size())
+      throw std::runtime_error(w + "member " + std::to_string(m) + " does not share the head's parameter tensors (not a lane of the same net)");
+  }
+  if (head->pipelined)
+    throw std::runtime_error(w + "the head has shf_net_set_pipeline enabled: its convolutions belong to the shared stream of the image pipeline");
+}
+
+// Net.forward() of every member as ONE grouped pass on the head's stream: shf_net::forward() step by step, the
+// per-member steps in loops and the pass, the read-backs and the range redo once for the group
+void forward_group(shf_net* head, int n, shf_net* const* members) {
+  check_group("forward_group", head, n, members);
+  hipStream_t st = head->stream;
+  // a member's shf_blob_load_device was enqueued on its own stream: the pass is ordered after it
+  for (int m = 0; m < n; ++m)
+    if (members[m]->stream != st) HIP_THROW(hipStreamSynchronize(members[m]->stream));
+  Pass p;
+  p.head = head;
+  p.n = n;
+  p.s = st;
+  p.tail = TAIL_GROUP;
+  p.materialize = true;
+  for (int m = 0; m < n; ++m) {
+    shf_net& ln = *members[m];
+    if (ln.data_blob >= 0 && ln.blobs[ln.data_blob].shape != ln.last_data_shape) {
+      ln.infer_shapes();
+      ln.alloc_buffers();
+    }
+    for (int bi : ln.inputs) {
+      Blob& b = ln.blobs[bi];
+      b.ext_dev = nullptr;
+      if (b.host_newer && b.host.p) {
+        b.dev.ensure(b.count() * 4);
+        ProfScope ps(head->prof, st, PC_H2D, 0, 4.0 * b.count());
+        HIP_THROW(hipMemcpyAsync(b.dev.p, b.host.p, b.count() * 4, hipMemcpyHostToDevice, st));
+        b.host_newer = false;
+      }
+    }
+    float ii[3] = {0, 0, 1};
+    if (ln.im_info_blob >= 0 && ln.blobs[ln.im_info_blob].host.p && ln.blobs[ln.im_info_blob].count() >= 3)
+      memcpy(ii, ln.blobs[ln.im_info_blob].host.p, 12);
+    memcpy(ln.last_im_info, ii, 12);
+    ln.inputs_reshaped = false;
+    p.u[m] = {&ln, ii[0], ii[1], ii[2]};
+  }
+  const bool fast = head->forward_fast_eligible();
+  const bool has_tail = head->tail_layer >= 0;
+  if (head->split_mode()) HIP_THROW(hipMemsetAsync(head->range_flag.p, 0, 4, st));
+  for (int m = 0; m < n; ++m) members[m]->reset_amax(st);
+  p.fused = fast;
+  run_pass(p);
+  int cnt[kMaxGroup][8] = {{0}}, flag = 0;
+  auto read_counters = [&]() {
+    ProfScope ps(head->prof, st, PC_D2H, 0, (double)n * sizeof(cnt[0]) + 4);
+    if (has_tail)
+      for (int m = 0; m < n; ++m)
+        HIP_THROW(hipMemcpyAsync(cnt[m], members[m]->tw.counters, sizeof(cnt[m]), hipMemcpyDeviceToHost, st));
+  };
+  read_counters();
+  if (head->split_mode()) HIP_THROW(hipMemcpyAsync(&flag, head->range_flag.p, 4, hipMemcpyDeviceToHost, st));
+  HIP_THROW(hipStreamSynchronize(st));
+  bool plain = !fast;
+  if (flag && head->split_mode()) {
+    // a convolution of SOME member left the fp16 range (one flag per pass): the whole group again on the exact fp32
+    // matrix-core kernels, per layer, every blob materialised -- as forward() redoes one net
+    const int mode_was = head->conv_mode;
+    ++head->sh->range_fallbacks;
+    head->conv_mode = 0;
+    try {
+      for (int m = 0; m < n; ++m) members[m]->reset_amax(st);
+      p.fused = false;
+      run_pass(p);
+      plain = true;
+      read_counters();
+      HIP_THROW(hipStreamSynchronize(st));
+    } catch (...) {
+      head->conv_mode = mode_was;
+      throw;
+    }
+    head->conv_mode = mode_was;
+  }
+  for (int m = 0; m < n; ++m) {
+    shf_net& ln = *members[m];
+    ln.plain_stale = !plain;
+    if (has_tail) {
+      const int R = cnt[m][2];
+      ln.blobs[ln.boxes_blob].shape = {std::max(R, 1), 5};
+      if (ln.prob_blob >= 0) ln.blobs[ln.prob_blob].shape = {R, 2};
+    }
+    for (size_t i = 0; i < ln.blobs.size(); ++i)
+      if (!std::count(ln.inputs.begin(), ln.inputs.end(), (int)i)) ln.blobs[i].dev_newer = true;
+    ln.forwarded = true;
+  }
+  if (!has_tail) return;
+  // the proposal outputs' host mirrors, now that the counts are known: every member's rows behind ONE synchronisation
+  // (Blob.data of each would copy and synchronise on its own: 2 n round trips)
+  {
+    ProfScope ps(head->prof, st, PC_D2H, 0, 0);
+    for (int m = 0; m < n; ++m) {
+      shf_net& ln = *members[m];
+      for (int bi : {ln.boxes_blob, ln.prob_blob}) {
+        if (bi < 0) continue;
+        Blob& b = ln.blobs[bi];
+        const size_t c = b.count();
+        b.host.ensure(std::max<size_t>(c, 1) * 4);
+        if (c > 0) HIP_THROW(hipMemcpyAsync(b.host.p, b.dev.p, c * 4, hipMemcpyDeviceToHost, st));
+      }
+    }
+  }
+  HIP_THROW(hipStreamSynchronize(st));
+  for (int m = 0; m < n; ++m) {
+    shf_net& ln = *members[m];
+    ln.blobs[ln.boxes_blob].dev_newer = false;
+    if (ln.prob_blob >= 0) ln.blobs[ln.prob_blob].dev_newer = false;
+  }
 }
 
 // the intermediate blobs after a fast forward (see net_internal.h `plain_stale`): run the per-layer kernels once, in the

@@ -348,7 +348,8 @@ struct NetShared {
 enum TailStep {
   TAIL_NONE,      // nothing (ensure_plain: the intermediates only -- the tail's outputs stay the forward's own)
   TAIL_LANE,      // one phase-0 launch per lane; a fused pass records the lane's ev_logits behind its logits kernel
-  TAIL_HANDOVER   // the grouped pipeline's two phases with their hand-over events (shf_detect_add_levels)
+  TAIL_HANDOVER,  // the grouped pipeline's two phases with their hand-over events (shf_detect_add_levels)
+  TAIL_GROUP      // both phases of the group as one launch per stage on the pass's stream, no events (shf_net_forward_group)
 };
 
 struct shf_net {
@@ -390,6 +391,7 @@ struct shf_net {
                                      // after a pipelined grouped pass -- the head's ev_convs (ONE record for the group:
                                      // ten event records in a row were ~90 us of idle conv stream per image)
   hipEvent_t ev_convs = nullptr;   // group pass: recorded on the head's stream after the last layer before the tails
+  hipEvent_t ev_group = nullptr;   // head of shf_blob_load_device_group: recorded behind the copy, awaited by the members' streams
   shf_net* pred = nullptr;         // shf_net_set_predecessor: the head lane whose image precedes this one's
   bool pipelined = false;   // shf_net_set_pipeline: convolutions go to sh->conv_stream, the rest stays on `stream`
   hipStream_t cstream() { return pipelined && sh->conv_stream ? sh->conv_stream : stream; }
@@ -437,6 +439,7 @@ struct shf_net {
   ~shf_net() {
     if (ev_logits) (void)hipEventDestroy(ev_logits);
     if (ev_convs) (void)hipEventDestroy(ev_convs);
+    if (ev_group) (void)hipEventDestroy(ev_group);
     if (ev_mark) (void)hipEventDestroy(ev_mark);
     if (stream) {
       (void)hipStreamSynchronize(stream);
@@ -506,10 +509,15 @@ struct Pass {
   bool fused;   // the fused path's kernels (fused first pair, pools in the epilogues, split activations); false: per layer
   hipStream_t s;           // the layers' stream
   TailStep tail;
-  bool materialize = false;  // TAIL_LANE: the tail also writes the cls_prob_reshape / bbox_pred blobs (Net.forward())
+  bool materialize = false;  // TAIL_LANE / TAIL_GROUP: the tail also writes the cls_prob_reshape / bbox_pred blobs (Net.forward())
   int wait_logits_at = -1;   // before this layer the stream waits for every lane's logits_done (the grouped early start)
 };
 void run_pass(const Pass& p);
+
+// net_forward.cpp: Net.forward() of n members (the head and / or lanes of its root) as ONE grouped pass on the head's
+// stream (shf_net_forward_group); check_group is its refusals, shared with shf_blob_load_device_group (net_api.cpp)
+void check_group(const char* who, shf_net* head, int n, shf_net* const* members);
+void forward_group(shf_net* head, int n, shf_net* const* members);
 
 // net_detect.cpp: append a group of finished units to `net`'s image list (or, per_member, to each member's own) in ONE launch
 void append_units(shf_net* net, shf_net* const* srcs, int n, const int* im_w, const float* im_scale, const int* flip,

@@ -132,6 +132,88 @@ def forward_net(net, blob, im_scale, pyramid=False, flip=False):
     return probs, pred_boxes
 
 
+def group_units(n_levels, flip, max_group=16):
+    """The (level, flipped) units of an image's pyramid in the reference's order (test.py:141-158: level i, then level i
+    flipped) cut into consecutive chunks of at most ``max_group`` units, one grouped pass each.  Pure: no GPU access."""
+    if n_levels < 0 or max_group < 1:
+        raise ValueError("group_units: n_levels >= 0 and max_group >= 1")
+    units = [(i, f) for i in range(n_levels) for f in ([False, True] if flip else [False])]
+    return [units[a:a + max_group] for a in range(0, len(units), max_group)]
+
+
+def forward_net_group(nets, blobs, im_scales, flips):
+    """``forward_net(pyramid=True)`` for a list of units: ``nets[k]`` -- distinct lanes of one net -- runs ``blobs[k]`` at
+    ``im_scales[k]``, mirrored back when ``flips[k]``.  Per unit the same reshape / pad / flip fix / unscale / tiling; the
+    forwards are ONE ``Net.forward_group`` per chunk of at most GROUP_UNITS units (the chunk's first net is its head) and
+    the device-resident levels of a chunk go into their blobs with one launch.  Returns the per-unit
+    (probs, pred_boxes) of forward_net in unit order, as arrays of their own: with more than GROUP_UNITS units the nets
+    serve one unit per chunk, and a later chunk overwrites their blobs."""
+    n = len(blobs)
+    if not (len(nets) >= min(n, GROUP_UNITS) and len(im_scales) == n and len(flips) == n):
+        raise ValueError("forward_net_group: %d blobs, %d nets, %d scales, %d flips" % (n, len(nets), len(im_scales), len(flips)))
+    out = []
+    for a in range(0, n, GROUP_UNITS):
+        chunk = list(range(a, min(a + GROUP_UNITS, n)))
+        lanes = [nets[k - a] for k in chunk]
+        widths, dev = [], []
+        for k, net in zip(chunk, lanes):
+            blob = blobs[k]
+            blob['im_info'] = np.array([[blob['data'].shape[2], blob['data'].shape[3], im_scales[k]]], dtype=np.float32)
+            h, w = blob['data'].shape[2:]
+            widths.append(w)
+            new_h = int(np.ceil(1.0 * h / cfg.MAX_RESOLUTION) * cfg.MAX_RESOLUTION)
+            new_w = int(np.ceil(1.0 * w / cfg.MAX_RESOLUTION) * cfg.MAX_RESOLUTION)
+            nn, c = blob['data'].shape[:2]
+            net.blobs['data'].reshape(nn, c, new_h, new_w)
+            net.blobs['im_info'].reshape(*(blob['im_info'].shape))
+            # the inputs are written straight into the nets' blobs, as forward_net writes them, and forward_group runs on
+            # the blobs as they stand
+            if isinstance(blob['data'], caffe.DeviceArray):
+                dev.append((net, blob['data']))
+            else:
+                data = net.blobs['data'].data
+                data[:, :, :h, :w] = blob['data']
+                if new_h > h:
+                    data[:, :, h:, :] = 0
+                if new_w > w:
+                    data[:, :, :h, w:] = 0
+            net.blobs['im_info'].data[...] = blob['im_info']
+        if dev:
+            caffe._load_device_group(lanes[0], [d[0] for d in dev], 'data', [d[1] for d in dev], None)
+        outs = lanes[0].forward_group(lanes)
+        for k, net, w, blobs_out in zip(chunk, lanes, widths, outs):
+            if flips[k]:
+                for i in [key for key in blobs_out.keys() if key.startswith('boxes')]:
+                    blobs_out[i][:, [1, 3]] = w - blobs_out[i][:, [3, 1]]
+            if 'boxes' in net.blobs:
+                levels = [None]
+            else:
+                levels = [key.split('_')[-1] for key in net.blobs.keys() if key.startswith('boxes')]
+                if len(cfg.TEST.LEVEL) > 0:
+                    logger.warning('Subset of levels selected for evaluation: {}'.format(cfg.TEST.LEVEL))
+                    levels = cfg.TEST.LEVEL
+            pred_boxes, probs = [], []
+            for level in levels:
+                suffix = '' if level is None else '_{}'.format(level)
+                cur_boxes = net.blobs['boxes' + suffix].data
+                cur_boxes = cur_boxes[:, 1:5] / im_scales[k]  # back to raw image space
+                cur_probs = net.blobs['cls_prob' + suffix].data
+                pred_boxes.append(np.tile(cur_boxes, (1, cur_probs.shape[1])))
+                probs.append(np.array(cur_probs))
+            out.append((probs, pred_boxes))
+    return out
+
+
+def _group_lanes(net, n):
+    """``n`` lanes for grouped forwards, cached on the net: the net itself, then clones made on first use and on demand."""
+    lanes = getattr(net, "_group_lanes", None)
+    if lanes is None:
+        lanes = net._group_lanes = [net]
+    while len(lanes) < n:
+        lanes.append(net.clone())
+    return lanes[:n]
+
+
 def _merge_class_dets(probs, boxes, thresh):
     """The per-class >thresh cut and box merging of detect() (test.py:161-176)."""
     cls_dets = [None] * (probs.shape[1] - 1)
@@ -183,7 +265,20 @@ def detect(net, im_path, thresh=0.05, timers=None, pyramid=False, im=None):
             im_blobs = _get_image_blob_device(im, pyramid_scales, on_device=True)
         else:
             im_blobs = _get_image_blob_device(im, pyramid_scales)
-        for i in range(len(pyramid_scales)):
+        grouped = os.environ.get("SHF_GROUPED_FORWARD") == "1"
+        if grouped:
+            # the same units in the same order, as one grouped pass per 16 (Net.forward_group) instead of one forward each:
+            # the same probs / boxes, so the same detections
+            chunks = group_units(len(pyramid_scales), bool(cfg.TEST.FLIP), GROUP_UNITS)
+            units = [u for ch in chunks for u in ch]
+            lanes = _group_lanes(net, min(len(units), GROUP_UNITS))
+            ublobs = [{'data': im_blobs[i]['data'][..., ::-1]} if f else im_blobs[i] for i, f in units]
+            res = forward_net_group(lanes, ublobs, [pyramid_scales[i] for i, _ in units], [f for _, f in units])
+            for probs, boxes in res:
+                for j in range(len(probs)):
+                    all_boxes.append(boxes[j][:, 0:4])
+                    all_probs.append(probs[j].copy())
+        for i in ([] if grouped else range(len(pyramid_scales))):
             probs, boxes = forward_net(net, im_blobs[i], pyramid_scales[i], pyramid=True)
             for j in range(len(probs)):
                 all_boxes.append(boxes[j][:, 0:4])

@@ -1,20 +1,24 @@
-"""The literal drop-in path with host levels and with device-resident levels, side by side.
+"""The literal drop-in path with host levels, with device-resident levels, and with the units of an image as one grouped
+forward, side by side.
 
-    python tools/bench_forward_path.py                       # -> profiles/forward_device_levels.json
-    python tools/bench_forward_path.py --parent-json P.json  # ... with the parent commit's figure merged in
+    python tools/bench_forward_path.py                       # -> profiles/forward_grouped.json
+    python tools/bench_forward_path.py --parent-json P.json  # ... with the parent commit's figures merged in
 
 Runs ``test.detect(net, im=...)`` -- lib/test.py:109-178: five pyramid levels, ten ``forward_net`` / ``Net.forward()`` calls,
 the > 0.05 cut and bbox_vote -- on bench.py's C5 image (1024 x 1024 uint8, seed 1000, the ``configs/smallhardface.toml``
 pyramid with flip, synthetic weights seed 1234, conv mode f16x3) with ``SHF_DEVICE_LEVELS`` unset ("switch_off": the levels
 come back to the host, are padded / flipped into the blob's pinned mirror and uploaded) and set to 1 ("switch_on": the levels
-stay in HBM as caffe.DeviceArray and Blob.load_device pads / flips them on the device).  After a warm-up each leg is timed
+stay in HBM as caffe.DeviceArray and Blob.load_device pads / flips them on the device), and with ``SHF_GROUPED_FORWARD=1`` on top
+of that ("grouped": one grouped load and ONE ``Net.forward_group`` over the ten units instead of ten loads and ten forwards).
+After a warm-up each leg is timed
 ``--repeats`` times over ``--images`` images, the legs alternating inside one process; a repeat is a host clock around
 whole detect() calls, each of which ends in synchronous read-backs.  Per leg: milliseconds per image of every repeat, their
-median and spread (max - min), and the ``Net.timing`` breakdown per image.
+median and spread (max - min), the ``Net.timing`` breakdown per image, and -- from one more, untimed image per leg with every
+launch bracketed -- the profiler's kernel / h2d / d2h milliseconds per image.
 
 With the switch off only interfaces older than the switch are used, so the same file runs on a tree without the feature
-(it then measures "switch_off" alone): run it there once and hand the result in with ``--parent-json``; it is recorded as
-"parent_commit" next to the two legs.
+(it then measures the legs that tree has): run it there once and hand the result in with ``--parent-json``; its legs are
+recorded under "parent_commit" next to this tree's.
 """
 import argparse
 import json
@@ -34,7 +38,7 @@ def main():
     ap.add_argument("--images", type=int, default=10, help="images per repeat (at least 10)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=3, help="untimed images per leg")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "forward_device_levels.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "forward_grouped.json"))
     ap.add_argument("--parent-json", default=None, help="this tool's output on the parent commit: merged in as parent_commit")
     args = ap.parse_args()
     n_img, n_rep = max(10, args.images), max(3, args.repeats)
@@ -54,14 +58,17 @@ def main():
     net.set_conv_mode("f16x3")
     im = np.random.default_rng(1000).integers(0, 256, (1024, 1024, 3)).astype(np.uint8)
 
-    legs = ["switch_off"] + (["switch_on"] if hasattr(caffe, "DeviceArray") else [])
+    legs = ["switch_off"] + (["switch_on"] if hasattr(caffe, "DeviceArray") else []) + \
+           (["grouped"] if hasattr(caffe.Net, "forward_group") else [])
     os.environ.pop("SHF_HOST_PREPROCESS", None)
+    n_units = len(cfg.TEST.SCALES) * (2 if cfg.TEST.FLIP else 1)
 
     def select(leg):
-        if leg == "switch_on":
-            os.environ["SHF_DEVICE_LEVELS"] = "1"
-        else:
-            os.environ.pop("SHF_DEVICE_LEVELS", None)
+        for k, on in (("SHF_DEVICE_LEVELS", leg in ("switch_on", "grouped")), ("SHF_GROUPED_FORWARD", leg == "grouped")):
+            if on:
+                os.environ[k] = "1"
+            else:
+                os.environ.pop(k, None)
 
     dets = {}
     for leg in legs:
@@ -81,8 +88,25 @@ def main():
             tm, net.timing = net.timing, None
             res[leg]["repeats_ms_per_image"].append(1000.0 * dt / n_img)
             res[leg]["timing_ms_per_image"].append({k[:-2] + "_ms": 1000.0 * v / n_img for k, v in tm.items() if k.endswith("_s")})
-            assert tm.get("calls", 0) == n_img * len(cfg.TEST.SCALES) * (2 if cfg.TEST.FLIP else 1)
-    os.environ.pop("SHF_DEVICE_LEVELS", None)
+            assert tm.get("units" if leg == "grouped" else "calls", 0) == n_img * n_units
+            res[leg]["forward_calls_per_image"] = tm.get("calls", 0) / float(n_img)
+    # the profiler's view of one more image per leg, outside the timed repeats (an event pair around every launch costs the
+    # stream a few microseconds each): what the GPU spends in kernels and in copies
+    for leg in legs:
+        select(leg)
+        net.prof_enable(True)
+        net.prof_reset()
+        T.detect(net, None, 0.05, pyramid=True, im=im)
+        pr = net.prof_read()
+        net.prof_enable(False)
+        net.prof_reset()
+        copies = {"h2d_copy": "h2d_ms", "d2h_copy": "d2h_ms"}
+        prof = {"kernel_ms": float(sum(v["ms"] for k, v in pr.items() if k not in copies)),
+                "kernel_launches": int(sum(v["launches"] for k, v in pr.items() if k not in copies))}
+        for k, name in copies.items():
+            prof[name] = float(pr[k]["ms"])
+        res[leg]["profiler_per_image"] = prof
+    select("switch_off")
     # forming the levels alone, outside the timed repeats (the call synchronises): switch off with their copy to the host
     from smallhardface_amd.test_utils import pyramid_scales
     level_blobs = T._get_image_blob_device    # (before the switch existed: test_utils' own, imported into test)
@@ -103,7 +127,7 @@ def main():
         r["timing_ms_per_image"] = {k: float(np.median([t[k] for t in r["timing_ms_per_image"]])) for k in keys}
         # what detect() spends outside Net.forward(): forming the levels (and, switch off, their D2H), the pad / flip on the host
         # or Blob.load_device, the box merge
-        r["outside_forward_ms"] = r["ms_per_image"] - sum(r["timing_ms_per_image"].values())
+        r["outside_forward_ms"] = r["ms_per_image"] - sum(v for k, v in r["timing_ms_per_image"].items() if k.endswith("_ms"))
         r["boxes"] = int(len(dets[leg]))
     out = {
         "workload": "test.detect(pyramid=True) on a 1024 x 1024 uint8 image (seed 1000), configs/smallhardface.toml pyramid "
@@ -119,12 +143,21 @@ def main():
                                            np.array_equal(dets["switch_on"], dets["switch_off"]))
         out["saving_ms"] = off["ms_per_image"] - on["ms_per_image"]
         out["saving_exceeds_spread"] = bool(out["saving_ms"] > max(off["spread_ms"], on["spread_ms"]))
+    if "grouped" in res:
+        on, gr = res["switch_on"], res["grouped"]
+        out["identical_detections"] = bool(out["identical_detections"] and dets["grouped"].shape == dets["switch_off"].shape and
+                                           np.array_equal(dets["grouped"], dets["switch_off"]))
+        out["grouped_saving_ms"] = on["ms_per_image"] - gr["ms_per_image"]       # against the ungrouped device-levels leg
+        out["grouped_saving_exceeds_spread"] = bool(out["grouped_saving_ms"] > max(on["spread_ms"], gr["spread_ms"]))
     if args.parent_json:
-        p = json.load(open(args.parent_json))["switch_off"]
-        out["parent_commit"] = p
-        d = abs(res["switch_off"]["ms_per_image"] - p["ms_per_image"])
-        out["switch_off_vs_parent_ms"] = res["switch_off"]["ms_per_image"] - p["ms_per_image"]
-        out["switch_off_within_spread_of_parent"] = bool(d <= max(res["switch_off"]["spread_ms"], p["spread_ms"]))
+        pj = json.load(open(args.parent_json))
+        out["parent_commit"] = {leg: pj[leg] for leg in ("switch_off", "switch_on") if leg in pj}
+        for leg, p in out["parent_commit"].items():
+            d = abs(res[leg]["ms_per_image"] - p["ms_per_image"])
+            out[leg + "_vs_parent_ms"] = res[leg]["ms_per_image"] - p["ms_per_image"]
+            out[leg + "_within_spread_of_parent"] = bool(d <= max(res[leg]["spread_ms"], p["spread_ms"]))
+        if "grouped" in res and "switch_on" in out["parent_commit"]:
+            out["grouped_vs_parent_switch_on_ms"] = res["grouped"]["ms_per_image"] - out["parent_commit"]["switch_on"]["ms_per_image"]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
