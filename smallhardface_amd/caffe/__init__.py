@@ -147,6 +147,25 @@ class DeviceArray(object):
         return "DeviceArray(ptr=0x%x, shape=%r%s)" % (self.ptr, self.shape, ", flipped" if self.flipped else "")
 
 
+def _resolve_source(blob, src, flip):
+    """What ``src`` -- a DeviceArray or anything it accepts -- means as a device load into ``blob``: None when it is the
+    blob's own device image (already in place), else (DeviceArray, the kernel's flip bit = ``flip`` XOR the source's own
+    ``flipped``, whether torch's stream must be waited for first)."""
+    a = src if isinstance(src, DeviceArray) else DeviceArray(src)
+    if a.ndim != 4:
+        raise ValueError("load_device needs a 4-D NCHW block, got shape %r" % (a.shape,))
+    if a._blob is not None and a._blob[0] is blob._net and a._blob[1] == blob._i:
+        if a.flipped != bool(flip):
+            raise ValueError("load_device cannot mirror blob '%s' into itself: copy its device image first" % blob.name)
+        return None
+    return a, (1 if bool(a.flipped) != bool(flip) else 0), not a._complete
+
+
+def _wait_for_torch():
+    import torch
+    torch.cuda.current_stream().synchronize()    # the producers' kernels: a source must be complete
+
+
 class Blob(object):
     def __init__(self, net, index, name):
         self._net = net
@@ -192,19 +211,14 @@ class Blob(object):
         shf_blob_load_device): ``src`` -- a DeviceArray or anything it accepts -- of shape (n, c, h <= H, w <= W) lands in
         this (n, c, H, W) blob, mirrored along x when ``flip`` XOR the source's own ``flipped``.  The net keeps ``src``
         alive until its next forward has returned."""
-        a = src if isinstance(src, DeviceArray) else DeviceArray(src)
-        if a.ndim != 4:
-            raise ValueError("load_device needs a 4-D NCHW block, got shape %r" % (a.shape,))
-        if a._blob is not None and a._blob[0] is self._net and a._blob[1] == self._i:
-            if a.flipped != bool(flip):
-                raise ValueError("load_device cannot mirror blob '%s' into itself: copy its device image first" % self.name)
-            return    # the blob's own device image: already in place
-        if not a._complete:
-            import torch
-            torch.cuda.current_stream().synchronize()    # the producer's kernels: the source must be complete
+        r = _resolve_source(self, src, flip)
+        if r is None:
+            return
+        a, f, wait = r
+        if wait:
+            _wait_for_torch()
         n, c, h, w = a.shape
-        _lib.check(self._net._lib.shf_blob_load_device(self._net._h, self._i, C.c_void_p(a.ptr), n, c, h, w,
-                                                       1 if bool(a.flipped) != bool(flip) else 0), "Blob.load_device")
+        _lib.check(self._net._lib.shf_blob_load_device(self._net._h, self._i, C.c_void_p(a.ptr), n, c, h, w, f), "Blob.load_device")
         self._net._dev_sources.append(a)
 
     @property
@@ -353,14 +367,6 @@ class Net(object):
             _lib.check(self._lib.shf_net_param_commit(self._h, li), "param_commit")
         self._dirty_layers.clear()
 
-    def _forward(self, start=0, end=None):
-        self.commit_params()
-        self._apply_cfg()
-        try:
-            _lib.check(self._lib.shf_net_forward(self._h), "Net.forward")
-        finally:
-            del self._dev_sources[:]    # (forward synchronises: the loads' kernels are done with their sources)
-
     def _stage_inputs(self, kwargs, deferred=None):
         """forward(**kwargs)'s checks and input copies (pycaffe.py:108-117).  ``deferred`` (forward_group): a device input is
         not loaded here but appended as (net, input name, DeviceArray), for one grouped load of all members."""
@@ -392,28 +398,55 @@ class Net(object):
                     and blob.strides == dst.strides):
                 dst[...] = blob
 
+    def _run_forward(self, members, inputs, names, group):
+        """forward() of ``members`` with ``self`` as the head: ``inputs[k]`` (None or forward's kwargs) staged into
+        ``members[k]``, one call, {name: Blob.data} of ``names(member)`` per member.  ``group``: the device inputs go in with
+        one grouped load per input name and the call is shf_net_forward_group; else Blob.load_device and shf_net_forward."""
+        tm = getattr(self, "timing", None)     # measurement only (bench.py net_forward_path): a dict collects host seconds
+        now = time.perf_counter if tm is not None else (lambda: 0.0)
+        t0 = now()
+        self.commit_params()
+        self._apply_cfg()
+        try:
+            deferred = [] if group else None
+            for m, kw in zip(members, inputs):
+                if kw:
+                    m._stage_inputs(kw, deferred)
+            for name in sorted(set(d[1] for d in deferred or ())):
+                sel = [d for d in deferred if d[1] == name]
+                _load_device_group(self, [d[0] for d in sel], name, [d[2] for d in sel], None)
+            t1 = now()
+            if group:
+                n = len(members)
+                mem = (C.c_void_p * max(n, 1))(*[getattr(m, "_h", None) for m in members])
+                _lib.check(self._lib.shf_net_forward_group(self._h, n, mem), "Net.forward_group")
+            else:
+                _lib.check(self._lib.shf_net_forward(self._h), "Net.forward")
+        finally:
+            for m in members:       # (the call synchronises: the loads' kernels are done with their sources)
+                if isinstance(m, Net):
+                    del m._dev_sources[:]
+        t2 = now()
+        out = [{o: m.blobs[o].data for o in names(m)} for m in members]
+        if tm is not None:
+            t3 = now()
+            tm["calls"] = tm.get("calls", 0) + 1
+            if group:
+                tm["units"] = tm.get("units", 0) + len(members)
+            tm["input_copy_s"] = tm.get("input_copy_s", 0.0) + (t1 - t0)     # host blob -> the pinned mirror (Blob.data[...] = x), or a DeviceArray's load
+            tm["forward_call_s"] = tm.get("forward_call_s", 0.0) + (t2 - t1)  # shf_net_forward(_group): H2D + kernels + the count read-back
+            tm["output_read_s"] = tm.get("output_read_s", 0.0) + (t3 - t2)   # Blob.data of the outputs: D2H
+        return out
+
     def forward(self, blobs=None, start=None, end=None, **kwargs):
         """pycaffe.py:88-134 (whole-net forward only: start/end are not supported)."""
         if start is not None or end is not None:
             raise NotImplementedError("partial forward (start/end) is outside the inference hot path")
-        if blobs is None:
-            blobs = []
-        outputs = set(self.outputs + blobs)
-        tm = getattr(self, "timing", None)     # measurement only (bench.py net_forward_path): a dict collects host seconds
-        t0 = time.perf_counter() if tm is not None else 0.0
-        if kwargs:
-            self._stage_inputs(kwargs)
-        t1 = time.perf_counter() if tm is not None else 0.0
-        self._forward()
-        t2 = time.perf_counter() if tm is not None else 0.0
-        out = {out: self.blobs[out].data for out in outputs}
-        if tm is not None:
-            t3 = time.perf_counter()
-            tm["calls"] = tm.get("calls", 0) + 1
-            tm["input_copy_s"] = tm.get("input_copy_s", 0.0) + (t1 - t0)     # host blob -> the pinned mirror (Blob.data[...] = x), or a DeviceArray's load
-            tm["forward_call_s"] = tm.get("forward_call_s", 0.0) + (t2 - t1)  # shf_net_forward: H2D + kernels + the count read-back
-            tm["output_read_s"] = tm.get("output_read_s", 0.0) + (t3 - t2)   # Blob.data of the outputs: D2H
-        return out
+        return self._run_forward([self], [kwargs], lambda m: set(m.outputs + (blobs or [])), False)[0]
+
+    def _forward(self):
+        """forward() on the blobs as they stand, no output read (tools/bench_conv.py, tools/bench_one.py)."""
+        self._run_forward([self], [None], lambda m: (), False)
 
     def forward_group(self, members, inputs=None):
         """``forward()`` of several nets as ONE grouped pass (C ABI shf_net_forward_group): every convolution, the
@@ -426,41 +459,10 @@ class Net(object):
         one per member.  Afterwards every member is an ordinary forwarded net: its results are bit for bit those of its
         own ``forward()``, and every blob of it reads as after one."""
         members = list(members)
-        n = len(members)
-        if inputs is None:
-            inputs = [None] * n
-        inputs = list(inputs)
-        if len(inputs) != n:
-            raise ValueError("forward_group: %d members but %d input dicts" % (n, len(inputs)))
-        tm = getattr(self, "timing", None)     # measurement only, as in forward()
-        t0 = time.perf_counter() if tm is not None else 0.0
-        self.commit_params()
-        self._apply_cfg()
-        try:
-            deferred = []
-            for m, kw in zip(members, inputs):
-                if kw:
-                    m._stage_inputs(kw, deferred)
-            for name in sorted(set(d[1] for d in deferred)):
-                sel = [d for d in deferred if d[1] == name]
-                _load_device_group(self, [d[0] for d in sel], name, [d[2] for d in sel], None)
-            t1 = time.perf_counter() if tm is not None else 0.0
-            mem = (C.c_void_p * max(n, 1))(*[getattr(m, "_h", None) for m in members])
-            _lib.check(self._lib.shf_net_forward_group(self._h, n, mem), "Net.forward_group")
-        finally:
-            for m in members:       # (forward_group synchronises: the loads' kernels are done with their sources)
-                if isinstance(m, Net):
-                    del m._dev_sources[:]
-        t2 = time.perf_counter() if tm is not None else 0.0
-        out = [{o: m.blobs[o].data for o in m.outputs} for m in members]
-        if tm is not None:
-            t3 = time.perf_counter()
-            tm["calls"] = tm.get("calls", 0) + 1
-            tm["units"] = tm.get("units", 0) + n
-            tm["input_copy_s"] = tm.get("input_copy_s", 0.0) + (t1 - t0)
-            tm["forward_call_s"] = tm.get("forward_call_s", 0.0) + (t2 - t1)
-            tm["output_read_s"] = tm.get("output_read_s", 0.0) + (t3 - t2)
-        return out
+        inputs = [None] * len(members) if inputs is None else list(inputs)
+        if len(inputs) != len(members):
+            raise ValueError("forward_group: %d members but %d input dicts" % (len(members), len(inputs)))
+        return self._run_forward(members, inputs, lambda m: m.outputs, True)
 
     # -- measurement helpers ------------------------------------------------------
     def sync(self):
@@ -625,26 +627,22 @@ def _load_device_group(head, nets, name, sources, flips):
     todo, wait = [], False
     for i, (net, src, flip) in enumerate(zip(nets, sources, flips)):
         b = net.blobs[name]
-        a = src if isinstance(src, DeviceArray) else DeviceArray(src)
-        if a.ndim != 4:
-            raise ValueError("load_device needs a 4-D NCHW block, got shape %r" % (a.shape,))
-        if a._blob is not None and a._blob[0] is net and a._blob[1] == b._i:
-            if a.flipped != bool(flip):
-                raise ValueError("load_device cannot mirror blob '%s' into itself: copy its device image first" % b.name)
-            continue    # the blob's own device image: already in place
+        r = _resolve_source(b, src, flip)
+        if r is None:
+            continue
+        a, f, w = r
         shp = b.shape
         if len(shp) == 4 and tuple(a.shape[:2]) != tuple(shp[:2]):    # (the C entry takes n and c from the blob itself)
             raise _lib.ShfError("load_device_group: member %d: blob_load_device: blob '%s' is (%d, %d, ...), the source (%d, %d, ...)"
                                 % (i, b.name, shp[0], shp[1], a.shape[0], a.shape[1]))
-        wait = wait or not a._complete
-        todo.append((net, b._i, a, 1 if bool(a.flipped) != bool(flip) else 0))
+        wait = wait or w
+        todo.append((net, b._i, a, f))
     if not todo:
         return
     if len(set(t[1] for t in todo)) != 1:
         raise ValueError("load_device_group: the nets do not hold blob '%s' at the same index (not lanes of one net)" % name)
     if wait:
-        import torch
-        torch.cuda.current_stream().synchronize()    # the producers' kernels: the sources must be complete
+        _wait_for_torch()
     n = len(todo)
     mem = (C.c_void_p * n)(*[t[0]._h for t in todo])
     src = (C.c_void_p * n)(*[t[2].ptr for t in todo])

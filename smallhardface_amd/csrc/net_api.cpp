@@ -52,6 +52,33 @@ int refuse_offsets(const int* off, int n_images, const char* name) {
   }
   return 0;
 }
+
+// the refusals of a device load into input blob `blob` of `net` (argument checks only): the messages of shf_blob_load_device
+// behind `prefix` ("member m: " in the grouped entry).  `nc`: the source's (n, c) where the entry receives them.
+Blob& check_load(shf_net* net, int blob, const std::string& prefix, const float* src_dev, const int* nc, int h, int w, int flip) {
+  Blob& b = net->blobs[blob];
+  const std::string what = prefix + "blob_load_device: blob '" + b.name + "' ";
+  if (!std::count(net->inputs.begin(), net->inputs.end(), blob) || b.shape.size() != 4)
+    throw std::runtime_error(what + "is not a 4-D net input");
+  if (!src_dev) throw std::runtime_error(what + "got a NULL source");
+  if (nc && (nc[0] != b.shape[0] || nc[1] != b.shape[1]))
+    throw std::runtime_error(what + "is (" + std::to_string(b.shape[0]) + ", " + std::to_string(b.shape[1]) +
+                             ", ...), the source (" + std::to_string(nc[0]) + ", " + std::to_string(nc[1]) + ", ...)");
+  if (h < 1 || w < 1 || h > b.shape[2] || w > b.shape[3])
+    throw std::runtime_error(what + "holds " + std::to_string(b.shape[2]) + " x " + std::to_string(b.shape[3]) +
+                             " planes, the source has " + std::to_string(h) + " x " + std::to_string(w));
+  if (flip != 0 && flip != 1) throw std::runtime_error(what + "flip must be 0 or 1");
+  if (b.count() == 0) throw std::runtime_error(what + "has zero elements");
+  return b;
+}
+
+// ... and what a load leaves behind: the device copy is the blob's head
+void mark_loaded(shf_net* net, Blob& b) {
+  b.host_newer = false;
+  b.dev_newer = true;
+  b.ext_dev = nullptr;
+  net->inputs_reshaped = true;   // (as after a reshape: the intermediates of the last forward no longer belong to this input)
+}
 }  // namespace
 
 extern "C" {
@@ -188,28 +215,14 @@ float* shf_blob_mutable_host_data(shf_net* net, int blob) {
 int shf_blob_load_device(shf_net* net, int blob, const float* src_dev, int n, int c, int h, int w, int flip) {
   API_BEGIN
   if (blob < 0 || blob >= (int)net->blobs.size()) throw std::runtime_error("bad blob index");
-  Blob& b = net->blobs[blob];
-  const std::string what = "blob_load_device: blob '" + b.name + "' ";
-  if (!std::count(net->inputs.begin(), net->inputs.end(), blob) || b.shape.size() != 4)
-    throw std::runtime_error(what + "is not a 4-D net input");
-  if (!src_dev) throw std::runtime_error(what + "got a NULL source");
-  if (n != b.shape[0] || c != b.shape[1])
-    throw std::runtime_error(what + "is (" + std::to_string(b.shape[0]) + ", " + std::to_string(b.shape[1]) +
-                             ", ...), the source (" + std::to_string(n) + ", " + std::to_string(c) + ", ...)");
-  if (h < 1 || w < 1 || h > b.shape[2] || w > b.shape[3])
-    throw std::runtime_error(what + "holds " + std::to_string(b.shape[2]) + " x " + std::to_string(b.shape[3]) +
-                             " planes, the source has " + std::to_string(h) + " x " + std::to_string(w));
-  if (flip != 0 && flip != 1) throw std::runtime_error(what + "flip must be 0 or 1");
-  if (b.count() == 0) throw std::runtime_error(what + "has zero elements");
+  const int nc[2] = {n, c};
+  Blob& b = check_load(net, blob, "", src_dev, nc, h, w, flip);
   b.dev.ensure(b.count() * 4);
   {
     ProfScope ps(net->prof, net->stream, PC_LAYOUT, 0, 4.0 * ((double)n * c * h * w + (double)b.count()));
     CHECK_RC(launch_pad_flip_nchw(src_dev, n, c, h, w, (float*)b.dev.p, b.shape[2], b.shape[3], flip, net->stream));
   }
-  b.host_newer = false;
-  b.dev_newer = true;
-  b.ext_dev = nullptr;
-  net->inputs_reshaped = true;   // (as after a reshape: the intermediates of the last forward no longer belong to this input)
+  mark_loaded(net, b);
   return 0;
   API_END(-1)
 }
@@ -222,19 +235,8 @@ int shf_blob_load_device_group(shf_net* net, int n, shf_net** members, int blob,
   check_group("blob_load_device_group", net, n, members);
   if (!src_dev || !h || !w || !flip) throw std::runtime_error("blob_load_device_group: NULL argument list");
   if (blob < 0 || blob >= (int)net->blobs.size()) throw std::runtime_error("bad blob index");
-  for (int m = 0; m < n; ++m) {
-    shf_net* ln = members[m];
-    Blob& b = ln->blobs[blob];
-    const std::string what = "member " + std::to_string(m) + ": blob_load_device: blob '" + b.name + "' ";
-    if (!std::count(ln->inputs.begin(), ln->inputs.end(), blob) || b.shape.size() != 4)
-      throw std::runtime_error(what + "is not a 4-D net input");
-    if (!src_dev[m]) throw std::runtime_error(what + "got a NULL source");
-    if (h[m] < 1 || w[m] < 1 || h[m] > b.shape[2] || w[m] > b.shape[3])
-      throw std::runtime_error(what + "holds " + std::to_string(b.shape[2]) + " x " + std::to_string(b.shape[3]) +
-                               " planes, the source has " + std::to_string(h[m]) + " x " + std::to_string(w[m]));
-    if (flip[m] != 0 && flip[m] != 1) throw std::runtime_error(what + "flip must be 0 or 1");
-    if (b.count() == 0) throw std::runtime_error(what + "has zero elements");
-  }
+  for (int m = 0; m < n; ++m)   // (n and c are the blob's own here: the entry does not receive them)
+    check_load(members[m], blob, "member " + std::to_string(m) + ": ", src_dev[m], nullptr, h[m], w[m], flip[m]);
   PadFlipUnit u[kMaxGroup];
   double bytes = 0;
   for (int m = 0; m < n; ++m) {
@@ -255,13 +257,7 @@ int shf_blob_load_device_group(shf_net* net, int n, shf_net** members, int blob,
   HIP_THROW(hipEventRecord(net->ev_group, net->stream));
   for (int m = 0; m < n; ++m)
     if (members[m]->stream != net->stream) HIP_THROW(hipStreamWaitEvent(members[m]->stream, net->ev_group, 0));
-  for (int m = 0; m < n; ++m) {
-    Blob& b = members[m]->blobs[blob];
-    b.host_newer = false;
-    b.dev_newer = true;
-    b.ext_dev = nullptr;
-    members[m]->inputs_reshaped = true;
-  }
+  for (int m = 0; m < n; ++m) mark_loaded(members[m], members[m]->blobs[blob]);
   return 0;
   API_END(-1)
 }
@@ -695,15 +691,9 @@ int shf_debug_append(shf_net* net, const float* boxes5, const float* probs2, int
   const int cnt[8] = {R, 0, R, 0, 0, 0, 0, 0};  // C candidates (all kept: topN is raised below), published R
   HIP_THROW(hipMemcpyAsync(net->tw.counters, cnt, sizeof(cnt), hipMemcpyHostToDevice, st));
   HIP_THROW(hipStreamSynchronize(st));
-  const int saved = net->pre_nms_topN;
+  Restore<int> topN(net->pre_nms_topN);
   net->pre_nms_topN = std::max(R, 1);  // append_unit sizes its launch and the list growth from it
-  try {
-    append_units(net, &net, 1, &im_w, &im_scale, &flip, thresh, false);
-  } catch (...) {
-    net->pre_nms_topN = saved;
-    throw;
-  }
-  net->pre_nms_topN = saved;
+  append_units(net, &net, 1, &im_w, &im_scale, &flip, thresh, false);
   return 0;
   API_END(-1)
 }

@@ -1,6 +1,7 @@
 // Net runtime, part 2: the layer walk (run_pass: one lane's unit, or one grouped pass over the units of several lanes),
-// Net.forward() with its fp32 redo, the same for a group of lanes (forward_group), Blob.data read-back, and the profiler's
-// kernel classes.
+// Net.forward() with its fp32 redo -- ONE function for 1..16 members (forward_members): shf_net::forward() is a group of
+// one, forward_group is check_group plus that function --, Blob.data / Blob.gpu_data() read-back, and the profiler's kernel
+// classes.
 #include "net_internal.h"
 
 namespace shf {
@@ -346,59 +347,38 @@ bool shf_net::forward_fast_eligible() const {
   return true;
 }
 
-void shf_net::forward() {
+// an input whose host copy is the newer one goes up on `st` (syncedmem.cpp:76-83 to_gpu); false: nothing to upload
+static bool upload_host_newer(Blob& b, hipStream_t st, Prof& pf) {
+  if (!b.host_newer || !b.host.p) return false;
+  b.dev.ensure(b.count() * 4);
+  ProfScope ps(pf, st, PC_H2D, 0, 4.0 * b.count());
+  HIP_THROW(hipMemcpyAsync(b.dev.p, b.host.p, b.count() * 4, hipMemcpyHostToDevice, st));
+  b.host_newer = false;
+  return true;
+}
+
+// this net as a member of a forward on `st`: shapes for the data blob's current shape, its inputs on the device, its unit's
+// im_info (from its own blob) in last_im_info
+void shf_net::stage_forward(hipStream_t st, Prof& pf) {
   if (data_blob >= 0 && blobs[data_blob].shape != last_data_shape) {
     infer_shapes();
     alloc_buffers();
   }
   for (int bi : inputs) {
-    Blob& b = blobs[bi];
-    b.ext_dev = nullptr;
-    if (b.host_newer && b.host.p) {
-      b.dev.ensure(b.count() * 4);
-      ProfScope ps(prof, stream, PC_H2D, 0, 4.0 * b.count());
-      HIP_THROW(hipMemcpyAsync(b.dev.p, b.host.p, b.count() * 4, hipMemcpyHostToDevice, stream));
-      b.host_newer = false;
-    }
+    blobs[bi].ext_dev = nullptr;
+    upload_host_newer(blobs[bi], st, pf);
   }
   float ii[3] = {0, 0, 1};
   if (im_info_blob >= 0 && blobs[im_info_blob].host.p && blobs[im_info_blob].count() >= 3)
     memcpy(ii, blobs[im_info_blob].host.p, 12);
   memcpy(last_im_info, ii, 12);
   inputs_reshaped = false;
-  const bool fast = forward_fast_eligible();
-  if (split_mode()) HIP_THROW(hipMemsetAsync(range_flag.p, 0, 4, stream));
-  reset_amax(stream);
-  run_unit(fast, ii, TAIL_LANE, true);
-  plain_stale = fast;
-  int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, flag = 0;
-  {
-    ProfScope ps(prof, stream, PC_D2H, 0, sizeof(cnt) + 4);
-    if (tail_layer >= 0) HIP_THROW(hipMemcpyAsync(cnt, tw.counters, sizeof(cnt), hipMemcpyDeviceToHost, stream));
-    if (split_mode()) HIP_THROW(hipMemcpyAsync(&flag, range_flag.p, 4, hipMemcpyDeviceToHost, stream));
-  }
-  HIP_THROW(hipStreamSynchronize(stream));
-  if (flag && split_mode()) {
-    const int mode_was = conv_mode;
-    // a convolution produced |x| > 65504: fp16(hi) of the split overflowed somewhere downstream.  The reference
-    // computes in fp32 (_caffe.cpp:46-48): redo THIS forward on the exact fp32 matrix-core kernels (per-layer path:
-    // every blob materialised).
-    ++sh->range_fallbacks;
-    conv_mode = 0;
-    try {
-      reset_amax(stream);
-      run_unit(false, ii, TAIL_LANE, true);
-      plain_stale = false;
-      if (tail_layer >= 0) HIP_THROW(hipMemcpyAsync(cnt, tw.counters, sizeof(cnt), hipMemcpyDeviceToHost, stream));
-      HIP_THROW(hipStreamSynchronize(stream));
-    } catch (...) {
-      conv_mode = mode_was;
-      throw;
-    }
-    conv_mode = mode_was;
-  }
+}
+
+// ... and what the forward left in it: `plain` -- the per-layer kernels ran, every blob is materialised; R proposal rows
+void shf_net::record_forward(bool plain, int R) {
+  plain_stale = !plain;
   if (tail_layer >= 0) {
-    const int R = cnt[2];
     blobs[boxes_blob].shape = {std::max(R, 1), 5};
     if (prob_blob >= 0) blobs[prob_blob].shape = {R, 2};
   }
@@ -406,6 +386,90 @@ void shf_net::forward() {
   for (size_t i = 0; i < blobs.size(); ++i)
     if (!std::count(inputs.begin(), inputs.end(), (int)i)) blobs[i].dev_newer = true;
   forwarded = true;
+}
+
+// Net.forward() of n members as ONE pass on the head's stream, with the head's range flag and profiler.  Its two callers
+// differ in the tail step, in whether the proposal outputs' host mirrors are filled here (`mirror_outputs`) or left to
+// Blob.data, and in check_group, which only the group goes through.
+static void forward_members(shf_net* head, int n, shf_net* const* members, TailStep tail, bool mirror_outputs) {
+  hipStream_t st = head->stream;
+  // a member's shf_blob_load_device was enqueued on its own stream: the pass is ordered after it
+  for (int m = 0; m < n; ++m)
+    if (members[m]->stream != st) HIP_THROW(hipStreamSynchronize(members[m]->stream));
+  Pass p;
+  p.head = head;
+  p.n = n;
+  p.s = st;
+  p.tail = tail;
+  p.materialize = true;
+  for (int m = 0; m < n; ++m) {
+    shf_net& ln = *members[m];
+    ln.stage_forward(st, head->prof);
+    p.u[m] = {&ln, ln.last_im_info[0], ln.last_im_info[1], ln.last_im_info[2]};
+  }
+  const bool fast = head->forward_fast_eligible(), has_tail = head->tail_layer >= 0, split = head->split_mode();
+  int cnt[kMaxGroup][8] = {{0}}, flag = 0;
+  auto run = [&](bool fused) {
+    for (int m = 0; m < n; ++m) members[m]->reset_amax(st);
+    p.fused = fused;
+    run_pass(p);
+  };
+  auto copy_counters = [&]() {
+    if (has_tail)
+      for (int m = 0; m < n; ++m)
+        HIP_THROW(hipMemcpyAsync(cnt[m], members[m]->tw.counters, sizeof(cnt[m]), hipMemcpyDeviceToHost, st));
+  };
+  if (split) HIP_THROW(hipMemsetAsync(head->range_flag.p, 0, 4, st));
+  run(fast);
+  {
+    ProfScope ps(head->prof, st, PC_D2H, 0, (double)n * sizeof(cnt[0]) + 4);
+    copy_counters();
+    if (split) HIP_THROW(hipMemcpyAsync(&flag, head->range_flag.p, 4, hipMemcpyDeviceToHost, st));
+  }
+  HIP_THROW(hipStreamSynchronize(st));
+  bool plain = !fast;
+  if (flag && split) {
+    // a convolution of SOME member produced |x| > 65504 (one flag per pass): fp16(hi) of the split overflowed somewhere
+    // downstream.  The reference computes in fp32 (_caffe.cpp:46-48): redo THIS forward, the whole group, on the exact fp32
+    // matrix-core kernels (per-layer path: every blob materialised).
+    ++head->sh->range_fallbacks;
+    Restore<int> mode(head->conv_mode);
+    head->conv_mode = 0;
+    run(false);
+    copy_counters();
+    HIP_THROW(hipStreamSynchronize(st));
+    plain = true;
+  }
+  for (int m = 0; m < n; ++m) members[m]->record_forward(plain, cnt[m][2]);
+  if (!mirror_outputs || !has_tail) return;
+  // the proposal outputs' host mirrors, now that the counts are known: every member's rows behind ONE synchronisation
+  // (Blob.data of each would copy and synchronise on its own: 2 n round trips)
+  {
+    ProfScope ps(head->prof, st, PC_D2H, 0, 0);
+    for (int m = 0; m < n; ++m) {
+      shf_net& ln = *members[m];
+      for (int bi : {ln.boxes_blob, ln.prob_blob}) {
+        if (bi < 0) continue;
+        Blob& b = ln.blobs[bi];
+        const size_t c = b.count();
+        b.host.ensure(std::max<size_t>(c, 1) * 4);
+        if (c > 0) HIP_THROW(hipMemcpyAsync(b.host.p, b.dev.p, c * 4, hipMemcpyDeviceToHost, st));
+      }
+    }
+  }
+  HIP_THROW(hipStreamSynchronize(st));
+  for (int m = 0; m < n; ++m) {
+    shf_net& ln = *members[m];
+    ln.blobs[ln.boxes_blob].dev_newer = false;
+    if (ln.prob_blob >= 0) ln.blobs[ln.prob_blob].dev_newer = false;
+  }
+}
+
+// a single forward is a group of one on its own stream: TAIL_LANE, so that a fused pass records this lane's ev_logits and
+// sets logits_done; no check_group, so a head with shf_net_set_pipeline enabled still runs
+void shf_net::forward() {
+  shf_net* self = this;
+  forward_members(this, 1, &self, TAIL_LANE, false);
 }
 
 // shf_net_forward_group's refusals: argument checks only, nothing is allocated or launched
@@ -428,113 +492,10 @@ void check_group(const char* who, shf_net* head, int n, shf_net* const* members)
     throw std::runtime_error(w + "the head has shf_net_set_pipeline enabled: its convolutions belong to the shared stream of the image pipeline");
 }
 
-// Net.forward() of every member as ONE grouped pass on the head's stream: shf_net::forward() step by step, the
-// per-member steps in loops and the pass, the read-backs and the range redo once for the group
+// the group: TAIL_GROUP (the tails as one launch per stage, no events) and the outputs' host mirrors filled eagerly
 void forward_group(shf_net* head, int n, shf_net* const* members) {
   check_group("forward_group", head, n, members);
-  hipStream_t st = head->stream;
-  // a member's shf_blob_load_device was enqueued on its own stream: the pass is ordered after it
-  for (int m = 0; m < n; ++m)
-    if (members[m]->stream != st) HIP_THROW(hipStreamSynchronize(members[m]->stream));
-  Pass p;
-  p.head = head;
-  p.n = n;
-  p.s = st;
-  p.tail = TAIL_GROUP;
-  p.materialize = true;
-  for (int m = 0; m < n; ++m) {
-    shf_net& ln = *members[m];
-    if (ln.data_blob >= 0 && ln.blobs[ln.data_blob].shape != ln.last_data_shape) {
-      ln.infer_shapes();
-      ln.alloc_buffers();
-    }
-    for (int bi : ln.inputs) {
-      Blob& b = ln.blobs[bi];
-      b.ext_dev = nullptr;
-      if (b.host_newer && b.host.p) {
-        b.dev.ensure(b.count() * 4);
-        ProfScope ps(head->prof, st, PC_H2D, 0, 4.0 * b.count());
-        HIP_THROW(hipMemcpyAsync(b.dev.p, b.host.p, b.count() * 4, hipMemcpyHostToDevice, st));
-        b.host_newer = false;
-      }
-    }
-    float ii[3] = {0, 0, 1};
-    if (ln.im_info_blob >= 0 && ln.blobs[ln.im_info_blob].host.p && ln.blobs[ln.im_info_blob].count() >= 3)
-      memcpy(ii, ln.blobs[ln.im_info_blob].host.p, 12);
-    memcpy(ln.last_im_info, ii, 12);
-    ln.inputs_reshaped = false;
-    p.u[m] = {&ln, ii[0], ii[1], ii[2]};
-  }
-  const bool fast = head->forward_fast_eligible();
-  const bool has_tail = head->tail_layer >= 0;
-  if (head->split_mode()) HIP_THROW(hipMemsetAsync(head->range_flag.p, 0, 4, st));
-  for (int m = 0; m < n; ++m) members[m]->reset_amax(st);
-  p.fused = fast;
-  run_pass(p);
-  int cnt[kMaxGroup][8] = {{0}}, flag = 0;
-  auto read_counters = [&]() {
-    ProfScope ps(head->prof, st, PC_D2H, 0, (double)n * sizeof(cnt[0]) + 4);
-    if (has_tail)
-      for (int m = 0; m < n; ++m)
-        HIP_THROW(hipMemcpyAsync(cnt[m], members[m]->tw.counters, sizeof(cnt[m]), hipMemcpyDeviceToHost, st));
-  };
-  read_counters();
-  if (head->split_mode()) HIP_THROW(hipMemcpyAsync(&flag, head->range_flag.p, 4, hipMemcpyDeviceToHost, st));
-  HIP_THROW(hipStreamSynchronize(st));
-  bool plain = !fast;
-  if (flag && head->split_mode()) {
-    // a convolution of SOME member left the fp16 range (one flag per pass): the whole group again on the exact fp32
-    // matrix-core kernels, per layer, every blob materialised -- as forward() redoes one net
-    const int mode_was = head->conv_mode;
-    ++head->sh->range_fallbacks;
-    head->conv_mode = 0;
-    try {
-      for (int m = 0; m < n; ++m) members[m]->reset_amax(st);
-      p.fused = false;
-      run_pass(p);
-      plain = true;
-      read_counters();
-      HIP_THROW(hipStreamSynchronize(st));
-    } catch (...) {
-      head->conv_mode = mode_was;
-      throw;
-    }
-    head->conv_mode = mode_was;
-  }
-  for (int m = 0; m < n; ++m) {
-    shf_net& ln = *members[m];
-    ln.plain_stale = !plain;
-    if (has_tail) {
-      const int R = cnt[m][2];
-      ln.blobs[ln.boxes_blob].shape = {std::max(R, 1), 5};
-      if (ln.prob_blob >= 0) ln.blobs[ln.prob_blob].shape = {R, 2};
-    }
-    for (size_t i = 0; i < ln.blobs.size(); ++i)
-      if (!std::count(ln.inputs.begin(), ln.inputs.end(), (int)i)) ln.blobs[i].dev_newer = true;
-    ln.forwarded = true;
-  }
-  if (!has_tail) return;
-  // the proposal outputs' host mirrors, now that the counts are known: every member's rows behind ONE synchronisation
-  // (Blob.data of each would copy and synchronise on its own: 2 n round trips)
-  {
-    ProfScope ps(head->prof, st, PC_D2H, 0, 0);
-    for (int m = 0; m < n; ++m) {
-      shf_net& ln = *members[m];
-      for (int bi : {ln.boxes_blob, ln.prob_blob}) {
-        if (bi < 0) continue;
-        Blob& b = ln.blobs[bi];
-        const size_t c = b.count();
-        b.host.ensure(std::max<size_t>(c, 1) * 4);
-        if (c > 0) HIP_THROW(hipMemcpyAsync(b.host.p, b.dev.p, c * 4, hipMemcpyDeviceToHost, st));
-      }
-    }
-  }
-  HIP_THROW(hipStreamSynchronize(st));
-  for (int m = 0; m < n; ++m) {
-    shf_net& ln = *members[m];
-    ln.blobs[ln.boxes_blob].dev_newer = false;
-    if (ln.prob_blob >= 0) ln.blobs[ln.prob_blob].dev_newer = false;
-  }
+  forward_members(head, n, members, TAIL_GROUP, true);
 }
 
 // the intermediate blobs after a fast forward (see net_internal.h `plain_stale`): run the per-layer kernels once, in the
@@ -611,6 +572,18 @@ void shf_net::materialize_fused(int bi) {
   b.dev_newer = false;
 }
 
+// an NHWC activation's fp32 NCHW image in the blob's staging buffer, enqueued on the stream (what Blob.data copies to the
+// host and Blob.gpu_data() hands out)
+const float* shf_net::stage_nchw(int bi, bool is_input) {
+  Blob& b = blobs[bi];
+  if (!is_input) ensure_plain();   // (after a fast forward: the activations are not plain fp32 tensors yet)
+  const size_t n = b.count();
+  b.stage.ensure(n * 4);
+  ProfScope ps(prof, stream, PC_LAYOUT, 0, 8.0 * n);
+  CHECK_RC(launch_nhwc_to_nchw(view_of(bi), (float*)b.stage.p, stream));
+  return (const float*)b.stage.p;
+}
+
 float* shf_net::host_data(int bi) {
   Blob& b = blobs[bi];
   if (b.kind == BK_FUSED) {
@@ -621,18 +594,10 @@ float* shf_net::host_data(int bi) {
   b.host.ensure(std::max<size_t>(n, 1) * 4);
   const bool is_input = std::count(inputs.begin(), inputs.end(), bi) > 0;
   if (b.dev_newer && n > 0) {
-    if (b.kind == BK_NHWC) {
-      if (!is_input) ensure_plain();   // (after a fast forward: the activations are not plain fp32 tensors yet)
-      b.stage.ensure(n * 4);
-      {
-        ProfScope ps(prof, stream, PC_LAYOUT, 0, 8.0 * n);
-        CHECK_RC(launch_nhwc_to_nchw(view_of(bi), (float*)b.stage.p, stream));
-      }
+    const void* src = b.kind == BK_NHWC ? stage_nchw(bi, is_input) : b.dev.p;
+    {
       ProfScope ps(prof, stream, PC_D2H, 0, 4.0 * n);
-      HIP_THROW(hipMemcpyAsync(b.host.p, b.stage.p, n * 4, hipMemcpyDeviceToHost, stream));
-    } else {
-      ProfScope ps(prof, stream, PC_D2H, 0, 4.0 * n);
-      HIP_THROW(hipMemcpyAsync(b.host.p, b.dev.p, n * 4, hipMemcpyDeviceToHost, stream));
+      HIP_THROW(hipMemcpyAsync(b.host.p, src, n * 4, hipMemcpyDeviceToHost, stream));
     }
     HIP_THROW(hipStreamSynchronize(stream));
     b.dev_newer = false;
@@ -654,24 +619,14 @@ const float* shf_net::device_data(int bi) {
   const bool is_input = std::count(inputs.begin(), inputs.end(), bi) > 0;
   const float* out = nullptr;
   if (is_input) {
-    if (b.host_newer && b.host.p) {
-      b.dev.ensure(n * 4);
-      ProfScope ps(prof, stream, PC_H2D, 0, 4.0 * n);
-      HIP_THROW(hipMemcpyAsync(b.dev.p, b.host.p, n * 4, hipMemcpyHostToDevice, stream));
-      b.host_newer = false;
-    } else if (!b.dev_newer && !forwarded) {
+    if (!upload_host_newer(b, stream, prof) && !b.dev_newer && !forwarded)
       throw std::runtime_error("blob '" + b.name + "' was never written: nothing to read on the device");
-    }
     out = (const float*)b.dev.p;
   } else {
     if (!forwarded) throw std::runtime_error("blob '" + b.name + "' was never forwarded: nothing to read on the device");
     if (b.kind == BK_NHWC) {
       if (b.shape.size() != 4) throw std::runtime_error("blob '" + b.name + "': an activation with " + std::to_string(b.shape.size()) + " axes has no NCHW image");
-      ensure_plain();   // (after a fast forward: the activations are not plain fp32 tensors yet)
-      b.stage.ensure(n * 4);
-      ProfScope ps(prof, stream, PC_LAYOUT, 0, 8.0 * n);
-      CHECK_RC(launch_nhwc_to_nchw(view_of(bi), (float*)b.stage.p, stream));
-      out = (const float*)b.stage.p;
+      out = stage_nchw(bi, false);
     } else {
       out = (const float*)b.dev.p;
     }

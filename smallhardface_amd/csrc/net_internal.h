@@ -344,6 +344,17 @@ struct NetShared {
   }
 };
 
+// a shared setting changed for the length of a scope (conv_mode during the fp32 redo, pre_nms_topN in shf_debug_append)
+template <typename T>
+struct Restore {
+  T& ref;
+  const T saved;
+  explicit Restore(T& r) : ref(r), saved(r) {}
+  ~Restore() { ref = saved; }
+  Restore(const Restore&) = delete;
+  Restore& operator=(const Restore&) = delete;
+};
+
 // what a pass of the layer walk does at the proposal layer: the one step its callers differ in
 enum TailStep {
   TAIL_NONE,      // nothing (ensure_plain: the intermediates only -- the tail's outputs stay the forward's own)
@@ -491,7 +502,12 @@ struct shf_net {
   void run_unit(bool fused, const float im_info[3], TailStep tail, bool materialize = false);
   void prepare_unit(const float* data, int data_on_device, int H, int W, hipStream_t st);
   void ensure_img_cap(int units_after);
+  // Net.forward(): a group of one (net_forward.cpp forward_members).  Per member of a forward: stage_forward before the
+  // pass (shapes, host-newer inputs up on the pass's stream, im_info -> last_im_info), record_forward after it
   void forward();
+  void stage_forward(hipStream_t st, Prof& pf);
+  void record_forward(bool plain, int R);
+  const float* stage_nchw(int bi, bool is_input);   // an NHWC activation's NCHW image in `stage` (host_data, device_data)
   float* host_data(int bi);
   const float* device_data(int bi);   // Blob.gpu_data(): the blob's fp32 NCHW image on the device (shf_blob_device_data)
   void materialize_fused(int bi);   // Blob.data of a tail-fused blob, re-ordered on the host from the tail workspace
@@ -515,7 +531,9 @@ struct Pass {
 void run_pass(const Pass& p);
 
 // net_forward.cpp: Net.forward() of n members (the head and / or lanes of its root) as ONE grouped pass on the head's
-// stream (shf_net_forward_group); check_group is its refusals, shared with shf_blob_load_device_group (net_api.cpp)
+// stream (shf_net_forward_group): check_group, then the function shf_net::forward() runs with itself as the only member.
+// The two differ in three things: the tail step (TAIL_LANE / TAIL_GROUP), the group filling the proposal outputs' host
+// mirrors itself, and check_group -- its refusals, shared with shf_blob_load_device_group (net_api.cpp).
 void check_group(const char* who, shf_net* head, int n, shf_net* const* members);
 void forward_group(shf_net* head, int n, shf_net* const* members);
 

@@ -78,8 +78,10 @@ def _get_image_blob_device(im, im_scales, on_device=False):
     return blobs
 
 
-def forward_net(net, blob, im_scale, pyramid=False, flip=False):
-    """Run one (scale, flip) unit; returns ([probs (R,2)], [pred_boxes (R,8)])."""
+def _stage_unit(net, blob, im_scale):
+    """forward_net's input staging for one unit: ``blob['im_info']``, the net's blobs reshaped to the level padded to
+    MAX_RESOLUTION and -- for a host level -- the level written into the data blob's host mirror.  Returns (w, data):
+    the level's width and that host view, or for a caffe.DeviceArray level the level itself, left for the caller to load."""
     blob['im_info'] = np.array([[blob['data'].shape[2], blob['data'].shape[3], im_scale]], dtype=np.float32)
 
     h, w = blob['data'].shape[2:]
@@ -88,48 +90,59 @@ def forward_net(net, blob, im_scale, pyramid=False, flip=False):
     n, c = blob['data'].shape[:2]
     net.blobs['data'].reshape(n, c, new_h, new_w)
     net.blobs['im_info'].reshape(*(blob['im_info'].shape))
+    if isinstance(blob['data'], caffe.DeviceArray):
+        return w, blob['data']
     # test.py:35-38 zero-pads with np.pad and hands the copy to forward(), which copies it again into the blob: here the
     # (possibly flipped, i.e. negatively strided) level is written ONCE, straight into the blob's host mirror, the pad rows /
     # columns zeroed around it -- the same (n, c, new_h, new_w) tensor, two 24-MB copies per 1408 x 1408 unit fewer
-    if isinstance(blob['data'], caffe.DeviceArray):
-        # a level that is already in HBM (SHF_DEVICE_LEVELS=1): padded -- and mirrored, for a [..., ::-1] view -- into the
-        # blob's device buffer by one kernel (Blob.load_device); forward() then finds the blob's own image and copies nothing
-        net.blobs['data'].load_device(blob['data'])
-        data = net.blobs['data'].device
-    else:
-        data = net.blobs['data'].data
-        data[:, :, :h, :w] = blob['data']
-        if new_h > h:
-            data[:, :, h:, :] = 0
-        if new_w > w:
-            data[:, :, :h, w:] = 0
-    net_args = {'data': data,
-                'im_info': blob['im_info'].astype(np.float32, copy=False)}
-    blobs_out = net.forward(**net_args)
+    data = net.blobs['data'].data
+    data[:, :, :h, :w] = blob['data']
+    if new_h > h:
+        data[:, :, h:, :] = 0
+    if new_w > w:
+        data[:, :, :h, w:] = 0
+    return w, data
 
+
+def _unit_results(net, blobs_out, w, im_scale, flip, copy=False):
+    """forward_net's ([probs (R,2)], [pred_boxes (R,8)]) of a forwarded net: the flip fix on its outputs, then per level
+    the boxes back in raw image space, tiled per class.  ``copy``: the probs as arrays of their own, not views of the blobs."""
     if flip:
         for i in [k for k in blobs_out.keys() if k.startswith('boxes')]:
             blobs_out[i][:, [1, 3]] = w - blobs_out[i][:, [3, 1]]
-
-    pred_boxes = []
-    probs = []
     if 'boxes' in net.blobs:
-        if not pyramid:
-            raise NotImplementedError("Please complete this part!")  # test.py:84-88
         levels = [None]
     else:
         levels = [k.split('_')[-1] for k in net.blobs.keys() if k.startswith('boxes')]
         if len(cfg.TEST.LEVEL) > 0:
             logger.warning('Subset of levels selected for evaluation: {}'.format(cfg.TEST.LEVEL))
             levels = cfg.TEST.LEVEL
+    pred_boxes = []
+    probs = []
     for level in levels:
         suffix = '' if level is None else '_{}'.format(level)
         cur_boxes = net.blobs['boxes' + suffix].data
         cur_boxes = cur_boxes[:, 1:5] / im_scale  # back to raw image space
         cur_probs = net.blobs['cls_prob' + suffix].data
         pred_boxes.append(np.tile(cur_boxes, (1, cur_probs.shape[1])))
-        probs.append(cur_probs)
+        probs.append(np.array(cur_probs) if copy else cur_probs)
     return probs, pred_boxes
+
+
+def forward_net(net, blob, im_scale, pyramid=False, flip=False):
+    """Run one (scale, flip) unit; returns ([probs (R,2)], [pred_boxes (R,8)])."""
+    w, data = _stage_unit(net, blob, im_scale)
+    if isinstance(data, caffe.DeviceArray):
+        # a level that is already in HBM (SHF_DEVICE_LEVELS=1): padded -- and mirrored, for a [..., ::-1] view -- into the
+        # blob's device buffer by one kernel (Blob.load_device); forward() then finds the blob's own image and copies nothing
+        net.blobs['data'].load_device(data)
+        data = net.blobs['data'].device
+    net_args = {'data': data,
+                'im_info': blob['im_info'].astype(np.float32, copy=False)}
+    blobs_out = net.forward(**net_args)
+    if 'boxes' in net.blobs and not pyramid:
+        raise NotImplementedError("Please complete this part!")  # test.py:84-88 (SURVEY.md F3)
+    return _unit_results(net, blobs_out, w, im_scale, flip)
 
 
 def group_units(n_levels, flip, max_group=16):
@@ -157,50 +170,18 @@ def forward_net_group(nets, blobs, im_scales, flips):
         lanes = [nets[k - a] for k in chunk]
         widths, dev = [], []
         for k, net in zip(chunk, lanes):
-            blob = blobs[k]
-            blob['im_info'] = np.array([[blob['data'].shape[2], blob['data'].shape[3], im_scales[k]]], dtype=np.float32)
-            h, w = blob['data'].shape[2:]
-            widths.append(w)
-            new_h = int(np.ceil(1.0 * h / cfg.MAX_RESOLUTION) * cfg.MAX_RESOLUTION)
-            new_w = int(np.ceil(1.0 * w / cfg.MAX_RESOLUTION) * cfg.MAX_RESOLUTION)
-            nn, c = blob['data'].shape[:2]
-            net.blobs['data'].reshape(nn, c, new_h, new_w)
-            net.blobs['im_info'].reshape(*(blob['im_info'].shape))
             # the inputs are written straight into the nets' blobs, as forward_net writes them, and forward_group runs on
             # the blobs as they stand
-            if isinstance(blob['data'], caffe.DeviceArray):
-                dev.append((net, blob['data']))
-            else:
-                data = net.blobs['data'].data
-                data[:, :, :h, :w] = blob['data']
-                if new_h > h:
-                    data[:, :, h:, :] = 0
-                if new_w > w:
-                    data[:, :, :h, w:] = 0
-            net.blobs['im_info'].data[...] = blob['im_info']
+            w, data = _stage_unit(net, blobs[k], im_scales[k])
+            widths.append(w)
+            if isinstance(data, caffe.DeviceArray):
+                dev.append((net, data))
+            net.blobs['im_info'].data[...] = blobs[k]['im_info']
         if dev:
             caffe._load_device_group(lanes[0], [d[0] for d in dev], 'data', [d[1] for d in dev], None)
         outs = lanes[0].forward_group(lanes)
         for k, net, w, blobs_out in zip(chunk, lanes, widths, outs):
-            if flips[k]:
-                for i in [key for key in blobs_out.keys() if key.startswith('boxes')]:
-                    blobs_out[i][:, [1, 3]] = w - blobs_out[i][:, [3, 1]]
-            if 'boxes' in net.blobs:
-                levels = [None]
-            else:
-                levels = [key.split('_')[-1] for key in net.blobs.keys() if key.startswith('boxes')]
-                if len(cfg.TEST.LEVEL) > 0:
-                    logger.warning('Subset of levels selected for evaluation: {}'.format(cfg.TEST.LEVEL))
-                    levels = cfg.TEST.LEVEL
-            pred_boxes, probs = [], []
-            for level in levels:
-                suffix = '' if level is None else '_{}'.format(level)
-                cur_boxes = net.blobs['boxes' + suffix].data
-                cur_boxes = cur_boxes[:, 1:5] / im_scales[k]  # back to raw image space
-                cur_probs = net.blobs['cls_prob' + suffix].data
-                pred_boxes.append(np.tile(cur_boxes, (1, cur_probs.shape[1])))
-                probs.append(np.array(cur_probs))
-            out.append((probs, pred_boxes))
+            out.append(_unit_results(net, blobs_out, w, im_scales[k], flips[k], copy=True))
     return out
 
 
@@ -265,8 +246,7 @@ def detect(net, im_path, thresh=0.05, timers=None, pyramid=False, im=None):
             im_blobs = _get_image_blob_device(im, pyramid_scales, on_device=True)
         else:
             im_blobs = _get_image_blob_device(im, pyramid_scales)
-        grouped = os.environ.get("SHF_GROUPED_FORWARD") == "1"
-        if grouped:
+        if os.environ.get("SHF_GROUPED_FORWARD") == "1":
             # the same units in the same order, as one grouped pass per 16 (Net.forward_group) instead of one forward each:
             # the same probs / boxes, so the same detections
             chunks = group_units(len(pyramid_scales), bool(cfg.TEST.FLIP), GROUP_UNITS)
@@ -274,21 +254,15 @@ def detect(net, im_path, thresh=0.05, timers=None, pyramid=False, im=None):
             lanes = _group_lanes(net, min(len(units), GROUP_UNITS))
             ublobs = [{'data': im_blobs[i]['data'][..., ::-1]} if f else im_blobs[i] for i, f in units]
             res = forward_net_group(lanes, ublobs, [pyramid_scales[i] for i, _ in units], [f for _, f in units])
-            for probs, boxes in res:
-                for j in range(len(probs)):
-                    all_boxes.append(boxes[j][:, 0:4])
-                    all_probs.append(probs[j].copy())
-        for i in ([] if grouped else range(len(pyramid_scales))):
-            probs, boxes = forward_net(net, im_blobs[i], pyramid_scales[i], pyramid=True)
+        else:
+            # one forward per unit, each consumed before the next overwrites the net's blobs: level i, then level i flipped
+            res = (forward_net(net, {'data': im_blobs[i]['data'][..., ::-1]} if f else im_blobs[i], pyramid_scales[i],
+                               pyramid=True, flip=f)
+                   for i in range(len(pyramid_scales)) for f in ([False, True] if cfg.TEST.FLIP else [False]))
+        for probs, boxes in res:
             for j in range(len(probs)):
                 all_boxes.append(boxes[j][:, 0:4])
                 all_probs.append(probs[j].copy())
-            if cfg.TEST.FLIP:
-                probs, boxes = forward_net(net, {'data': im_blobs[i]['data'][..., ::-1]}, pyramid_scales[i],
-                                           pyramid=True, flip=True)
-                for j in range(len(probs)):
-                    all_boxes.append(boxes[j][:, 0:4])
-                    all_probs.append(probs[j].copy())
         probs = np.concatenate(all_probs)
         boxes = np.concatenate(all_boxes)
     timers['detect'].toc()

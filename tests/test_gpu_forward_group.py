@@ -385,3 +385,56 @@ def test_detect_grouped_with_two_passes(driver_net, monkeypatch):
     im = np.random.default_rng(22).integers(0, 256, (96, 128, 3)).astype(np.uint8)
     _detect_all_ways(driver_net, im, monkeypatch)
     assert len(driver_net._group_lanes) == 16
+
+
+# ---- 9. one forward path: forward() is a group of one ------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["f16x3", "fp32"])
+def test_group_of_one_launches_what_forward_launches(lanes, mode):
+    """Per-class launch counts of forward() and of forward_group([root]) on the same host inputs, each after one warm call:
+    equal in every class but d2h_copy (only the group fills the proposal outputs' host mirrors itself, behind one
+    synchronisation; after forward() each Blob.data copies its own)."""
+    root = lanes[0]
+    root.set_conv_mode(mode)
+    data, info = _unit(2)
+    assert data.shape[2:] == (32, 48)
+    root.blobs["data"].reshape(*data.shape)
+    root.blobs["im_info"].reshape(1, 3)
+    inp = {"data": data, "im_info": info}
+
+    def counts(run):
+        run()
+        root.prof_reset()
+        run()
+        return {k: v["launches"] for k, v in root.prof_read().items() if k != "d2h_copy"}
+    root.prof_enable(True)
+    try:
+        one = counts(lambda: root.forward(**inp))
+        grouped = counts(lambda: root.forward_group([root], [inp]))
+    finally:
+        root.prof_enable(False)
+        root.prof_reset()
+    print("launches per class (%s): forward %r" % (mode, {k: v for k, v in one.items() if v}))
+    print("launches per class (%s): group of one %r" % (mode, {k: v for k, v in grouped.items() if v}))
+    assert sum(one.values()) > 10 and one["h2d_copy"] > 0
+    assert grouped == one
+
+
+def test_pipelined_head_forwards_alone_and_refuses_a_group(single):
+    """check_group is the group's alone: a head with shf_net_set_pipeline enabled still runs forward(), on its own stream."""
+    net = _new_net()                    # (not a lane of the module's: set_pipeline replaces the net's stream)
+    net.set_conv_mode("f16x3")
+    data, info = _unit(2)
+    want = single("f16x3", 2)
+    net.blobs["data"].reshape(*data.shape)
+    net.blobs["im_info"].reshape(1, 3)
+    net.set_pipeline(True)
+    out = net.forward(data=data, im_info=info)
+    for name in ("boxes", "cls_prob"):
+        np.testing.assert_array_equal(out[name], want[name], err_msg=name)
+    assert len(want["cls_prob"]) > 1
+    with pytest.raises(_lib.ShfError, match="shf_net_set_pipeline enabled"):
+        net.forward_group([net])
+    net.set_pipeline(False)
+    out = net.forward_group([net])[0]
+    for name in ("boxes", "cls_prob"):
+        np.testing.assert_array_equal(out[name], want[name], err_msg=name)

@@ -151,11 +151,13 @@ def main():
         out["grouped_saving_exceeds_spread"] = bool(out["grouped_saving_ms"] > max(on["spread_ms"], gr["spread_ms"]))
     if args.parent_json:
         pj = json.load(open(args.parent_json))
-        out["parent_commit"] = {leg: pj[leg] for leg in ("switch_off", "switch_on") if leg in pj}
+        out["parent_commit"] = {leg: pj[leg] for leg in ("switch_off", "switch_on", "grouped") if leg in pj}
         for leg, p in out["parent_commit"].items():
             d = abs(res[leg]["ms_per_image"] - p["ms_per_image"])
             out[leg + "_vs_parent_ms"] = res[leg]["ms_per_image"] - p["ms_per_image"]
             out[leg + "_within_spread_of_parent"] = bool(d <= max(res[leg]["spread_ms"], p["spread_ms"]))
+            out[leg + "_launches_equal_parent"] = bool(res[leg]["profiler_per_image"]["kernel_launches"] ==
+                                                       p.get("profiler_per_image", {}).get("kernel_launches"))
         if "grouped" in res and "switch_on" in out["parent_commit"]:
             out["grouped_vs_parent_switch_on_ms"] = res["grouped"]["ms_per_image"] - out["parent_commit"]["switch_on"]["ms_per_image"]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
