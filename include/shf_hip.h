@@ -277,6 +277,24 @@ int shf_wider_eval_counts(const double* pred5, const int* pred_off, const double
                           const uint8_t* counted, int n_images, int n_settings, double iou_thresh, int mimic_eval_bug,
                           const double* thresh, int n_thresh, long long* totals, int* hits_out, uint8_t* proposal_out);
 
+/* One matching round of the AFW / Pascal Faces evaluator, for all images in one call, on the current device:
+ * VOCprRecordOptim  external/marcopede-face-eval-f2870fd85d48/VOCpr.py:118-162 with the IoU of util.overlap
+ * (util.py:176-193: abs() extents + 1, a strict > intersection test, ia / (a1 + a2 - ia) in fp64, that operation order).
+ *   det4       (N,4) x1, y1, x2, y2; the rows of image i are det_off[i] .. det_off[i+1] (n_images + 1 offsets), in the
+ *              evaluator's global score-descending order (grouping by image keeps all the matching depends on)
+ *   gt4        (G,4) x1, y1, x2, y2 with gt_off alike; difficult (G): non-zero where the box is "difficult"
+ *   code_out   (N) 0 = neither (the best box is difficult), 1 = true positive, 2 = false positive
+ *   index_out  (N) the chosen box counted within its image, -1 for an image without boxes
+ * The chosen box is the LAST one holding the largest IoU (the reference compares covr >= maxovr, from maxovr = 0 and
+ * index 0).  True positive: IoU > ovr (strict) on a box that is not difficult and that no earlier detection of the call
+ * has taken; false positive: the box is taken, or IoU <= ovr, or the image has no boxes.  Integers only: translations,
+ * means, the refinement transform, the curve and the AP stay with the caller, one call per refinement round.
+ * All buffers are host memory.  Refused with a message, before anything is allocated or launched: negative or
+ * non-monotone offsets, ovr outside (0, 1], 2^31 rows or more of either kind.  Non-finite boxes are the caller's to keep
+ * away (Python's comparison chain on NaN is not reproduced). */
+int shf_face_eval_match(const double* det4, const long long* det_off, const double* gt4, const long long* gt_off,
+                        const uint8_t* difficult, int n_images, double ovr, int* code_out, int* index_out);
+
 /* Read parameter blob `idx` of layer `layer` from a binary .caffemodel (the reader behind
  * shf_net_create's weight loading; caffe.proto NetParameter.layer=100 / BlobProto data=5).
  * Returns the element count (out may be NULL to query), fills dims/ndim.  Needs no GPU. */

@@ -119,6 +119,8 @@ def _declare(lib):
         "shf_bbox_vote": (ci, [fp, ci, cf, dp, ci, ip]),
         "shf_wider_eval_counts": (ci, [dp, ip, dp, ip, C.POINTER(C.c_uint8), ci, ci, C.c_double, ci, dp, ci,
                                        C.POINTER(C.c_longlong), ip, C.POINTER(C.c_uint8)]),
+        "shf_face_eval_match": (ci, [dp, C.POINTER(C.c_longlong), dp, C.POINTER(C.c_longlong), C.POINTER(C.c_uint8), ci,
+                                     C.c_double, ip, ip]),
         "shf_generate_anchors": (ci, [ci, dp, ci, dp, ci, dp, ci, dp, dp, ci]),
         "shf_prof_enable": (ci, [vp, ci]),
         "shf_prof_only": (ci, [vp, ci]),

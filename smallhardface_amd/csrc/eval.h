@@ -1,4 +1,5 @@
-// Launchers of the WIDER evaluation kernels (eval.hip), called by shf_wider_eval_counts (net_api.cpp).
+// Launchers of the evaluation kernels (eval.hip): WIDER, called by shf_wider_eval_counts, and AFW / Pascal Faces, called by
+// shf_face_eval_match (net_api.cpp).
 #pragma once
 #include "shf_internal.h"
 
@@ -21,5 +22,12 @@ int launch_eval_counts(const int* pred_off, const int* match, const int* first, 
 int launch_eval_sweep(const double* pred5, const int* pred_off, const int* gt_off, const int* hits, const int* cum_prop,
                       int n_images, int n_settings, int N, const double* thresh, int T, unsigned long long* totals,
                       hipStream_t s);
+
+// the per-detection codes of shf_face_eval_match
+constexpr int kFaceNeither = 0, kFaceTruePositive = 1, kFaceFalsePositive = 2;
+// one wave per image: code[h], index[h] (box within the image, -1 without boxes) for the x1-y1-x2-y2 rows det4 / gt4;
+// taken (G) must be zero on entry
+int launch_face_match(const double* det4, const int* det_off, const double* gt4, const int* gt_off, const uint8_t* difficult,
+                      int n_images, double ovr, uint8_t* taken, int* code, int* index, hipStream_t s);
 
 }  // namespace shf

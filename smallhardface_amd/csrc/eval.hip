@@ -12,6 +12,10 @@
 //           vector atomic adds into the (S, T, 2) totals.  Integer sums: exact in any order.
 // All box arithmetic is fp64 in the operation order of _overlaps(); compiled with -ffp-contract=off, so every add, multiply
 // and divide rounds like numpy's.
+//
+// AFW / Pascal Faces evaluation: one matching round of
+//   VOCprRecordOptim    external/marcopede-face-eval-f2870fd85d48/VOCpr.py:118-162   (IoU: util.py:176-193)
+// face_match_kernel, at the end of this file (smallhardface_amd/face_eval.py: match_host is its numpy restatement).
 #include "eval.h"
 
 namespace shf {
@@ -169,6 +173,78 @@ int launch_eval_sweep(const double* pred5, const int* pred_off, const int* gt_of
   if (n_images == 0 || N == 0) return 0;
   hipLaunchKernelGGL(eval_sweep_kernel, dim3((unsigned)n_images, (unsigned)n_settings), dim3(256), 0, s, pred5, pred_off,
                      gt_off, hits, cum_prop, N, thresh, T, totals);
+  SHF_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// ---- AFW / Pascal Faces: one matching round (VOCpr.py:118-162) ---------------------------------------------------------------
+// One wave per image walks the image's detections in their (score-descending) order; the lanes stride over the image's boxes.
+//   IoU     util.overlap (util.py:176-193) on x1-y1-x2-y2 rows: abs() extents + 1, a strict > intersection test,
+//           ia / (a1 + a2 - ia), every operation in that order.
+//   choice  the reference keeps a box when covr >= maxovr, starting from maxovr = 0, gt = 0: it ends on the LAST index
+//           holding max(0, largest covr), or on (0, index 0) when no covr reaches 0.  A lane walks its boxes in rising index
+//           order with the same >=, the butterfly keeps the larger value and among equal values the larger index.
+//   verdict lane 0 alone: false positive unless maxovr > ovr; on a difficult box neither; else the box's taken flag decides
+//           and is set.  taken[] is a per-call scratch segment laid out like the boxes, zero on entry; only lane 0 of the
+//           image's own wave reads and writes the image's flags, in program order.
+// Latency-bound by construction: the detections of an image are a serial chain, the work per link is a handful of boxes.
+__global__ __launch_bounds__(64) void face_match_kernel(const double* __restrict__ det4, const int* __restrict__ det_off,
+                                                        const double* __restrict__ gt4, const int* __restrict__ gt_off,
+                                                        const uint8_t* __restrict__ difficult, double ovr,
+                                                        uint8_t* __restrict__ taken, int* __restrict__ code,
+                                                        int* __restrict__ index) {
+  const int img = blockIdx.x, lane = threadIdx.x;
+  const int h0 = det_off[img], h1 = det_off[img + 1];
+  const int g0 = gt_off[img], ng = gt_off[img + 1] - g0;
+  if (ng == 0) {   // no ground truth (an unknown image): every detection is a false positive
+    for (int h = h0 + lane; h < h1; h += 64) { code[h] = kFaceFalsePositive; index[h] = -1; }
+    return;
+  }
+  for (int h = h0; h < h1; ++h) {
+    const double* p = det4 + (size_t)h * 4;   // (wave-uniform: every lane reads the same detection)
+    const double dx1 = p[0], dy1 = p[1], dx2 = p[2], dy2 = p[3];
+    const double a1 = (fabs(dx1 - dx2) + 1) * (fabs(dy1 - dy2) + 1);
+    double best = -INFINITY;
+    int bi = -1;
+    for (int j = lane; j < ng; j += 64) {
+      const double* q = gt4 + (size_t)(g0 + j) * 4;
+      const double gx1 = q[0], gy1 = q[1], gx2 = q[2], gy2 = q[3];
+      const double a2 = (fabs(gx1 - gx2) + 1) * (fabs(gy1 - gy2) + 1);
+      double ia = 0;
+      if (dy2 > gy1 && gy2 > dy1 && dx2 > gx1 && gx2 > dx1) {
+        const double xx1 = gx1 > dx1 ? gx1 : dx1, yy1 = gy1 > dy1 ? gy1 : dy1;
+        const double xx2 = gx2 < dx2 ? gx2 : dx2, yy2 = gy2 < dy2 ? gy2 : dy2;
+        ia = (xx2 - xx1 + 1) * (yy2 - yy1 + 1);
+      }
+      const double c = ia / (a1 + a2 - ia);
+      if (c >= best) { best = c; bi = j; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double ob = __shfl_xor(best, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ob > best || (ob == best && oi > bi)) { best = ob; bi = oi; }
+    }
+    if (lane == 0) {
+      double maxovr = 0;
+      int gi = 0;
+      if (bi >= 0 && best >= 0.0) { maxovr = best; gi = bi; }
+      int c = kFaceFalsePositive;
+      if (maxovr > ovr) {
+        if (difficult[g0 + gi]) c = kFaceNeither;
+        else if (!taken[g0 + gi]) { taken[g0 + gi] = 1; c = kFaceTruePositive; }
+      }
+      code[h] = c;
+      index[h] = gi;
+    }
+  }
+}
+
+int launch_face_match(const double* det4, const int* det_off, const double* gt4, const int* gt_off, const uint8_t* difficult,
+                      int n_images, double ovr, uint8_t* taken, int* code, int* index, hipStream_t s) {
+  if (n_images == 0) return 0;
+  hipLaunchKernelGGL(face_match_kernel, dim3((unsigned)n_images), dim3(64), 0, s, det4, det_off, gt4, gt_off, difficult, ovr,
+                     taken, code, index);
   SHF_HIP_OK(hipGetLastError());
   return 0;
 }

@@ -27,7 +27,8 @@ static MergeCtx* g_box_ctx = nullptr;
 static hipStream_t g_box_stream = nullptr;
 static DevBuf* g_box_in = nullptr;
 
-// device memory and stream of ONE shf_wider_eval_counts call, on the device current at the call: nothing outlives it
+// device memory and stream of ONE shf_wider_eval_counts / shf_face_eval_match call, on the device current at the call:
+// nothing outlives it
 namespace {
 struct CallBuf {
   void* p = nullptr;
@@ -570,6 +571,56 @@ int shf_wider_eval_counts(const double* pred5, const int* pred_off, const double
   HIP_THROW(hipMemcpyAsync(totals, d_tot.p, S * T * 2 * 8, hipMemcpyDeviceToHost, st.s));
   if (hits_out) HIP_THROW(hipMemcpyAsync(hits_out, d_hits.p, S * (size_t)N * sizeof(int), hipMemcpyDeviceToHost, st.s));
   if (proposal_out) HIP_THROW(hipMemcpyAsync(proposal_out, d_prop.p, S * (size_t)N, hipMemcpyDeviceToHost, st.s));
+  HIP_THROW(hipStreamSynchronize(st.s));
+  return 0;
+  API_END(-1)
+}
+
+int shf_face_eval_match(const double* det4, const long long* det_off, const double* gt4, const long long* gt_off,
+                        const uint8_t* difficult, int n_images, double ovr, int* code_out, int* index_out) {
+  API_BEGIN
+  // ---- refusals: argument checks only, before anything is allocated or launched
+  if (!det_off || !gt_off || n_images < 0) throw std::runtime_error("face_eval_match: null offsets or negative n_images");
+  if (!(ovr > 0.0 && ovr <= 1.0)) throw std::runtime_error("face_eval_match: ovr must be in (0, 1]");
+  for (const auto& [off, name] : {std::pair<const long long*, const char*>{det_off, "det_off"}, {gt_off, "gt_off"}})
+    for (int i = 0; i <= n_images; ++i) {
+      if (off[i] < 0) throw std::runtime_error(std::string("face_eval_match: negative offset in ") + name);
+      if (i && off[i] < off[i - 1]) throw std::runtime_error(std::string("face_eval_match: non-monotone offsets in ") + name);
+    }
+  const long long N = det_off[n_images], G = gt_off[n_images];
+  if (N >= (1ll << 31) || G >= (1ll << 31))
+    throw std::runtime_error("face_eval_match: 2^31 rows or more (detections " + std::to_string(N) + ", ground-truth boxes " +
+                             std::to_string(G) + ")");
+  if ((N && (!det4 || !code_out || !index_out)) || (G && (!gt4 || !difficult)))
+    throw std::runtime_error("face_eval_match: null box or output array");
+  if (N == 0) return 0;
+  if (G == 0) {   // no image has ground truth: every detection is a false positive
+    std::fill(code_out, code_out + N, kFaceFalsePositive);
+    std::fill(index_out, index_out + N, -1);
+    return 0;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    throw std::runtime_error("no HIP device available: face_eval_match has no CPU fallback");
+
+  std::vector<int> off32(2 * ((size_t)n_images + 1));   // (the checked offsets fit 31 bits)
+  for (int i = 0; i <= n_images; ++i) { off32[i] = (int)det_off[i]; off32[(size_t)n_images + 1 + i] = (int)gt_off[i]; }
+  CallStream st;
+  st.create();
+  CallBuf d_det, d_off, d_gt, d_diff, d_taken, d_code, d_index;
+  const size_t offb = off32.size() * sizeof(int);
+  d_det.alloc((size_t)N * 4 * 8); d_off.alloc(offb); d_gt.alloc((size_t)G * 4 * 8); d_diff.alloc((size_t)G);
+  d_taken.alloc((size_t)G); d_code.alloc((size_t)N * sizeof(int)); d_index.alloc((size_t)N * sizeof(int));
+  HIP_THROW(hipMemcpyAsync(d_det.p, det4, (size_t)N * 4 * 8, hipMemcpyHostToDevice, st.s));
+  HIP_THROW(hipMemcpyAsync(d_off.p, off32.data(), offb, hipMemcpyHostToDevice, st.s));
+  HIP_THROW(hipMemcpyAsync(d_gt.p, gt4, (size_t)G * 4 * 8, hipMemcpyHostToDevice, st.s));
+  HIP_THROW(hipMemcpyAsync(d_diff.p, difficult, (size_t)G, hipMemcpyHostToDevice, st.s));
+  HIP_THROW(hipMemsetAsync(d_taken.p, 0, (size_t)G, st.s));
+  CHECK_RC(launch_face_match(d_det.as<double>(), d_off.as<int>(), d_gt.as<double>(), d_off.as<int>() + n_images + 1,
+                             d_diff.as<uint8_t>(), n_images, ovr, d_taken.as<uint8_t>(), d_code.as<int>(),
+                             d_index.as<int>(), st.s));
+  HIP_THROW(hipMemcpyAsync(code_out, d_code.p, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, st.s));
+  HIP_THROW(hipMemcpyAsync(index_out, d_index.p, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, st.s));
   HIP_THROW(hipStreamSynchronize(st.s));
   return 0;
   API_END(-1)

@@ -9,7 +9,8 @@
   writer_for(db)           imdb name (cfg.TEST.DB) -> writer, like lib/datasets/factory.py picks the class
 
 All four are pinned by tests/golden/writers.json (files written by the reference's own classes).  The WIDER
-evaluator is smallhardface_amd/wider_eval.py; ImageList runs it when a ground_truth directory is given.
+evaluator is smallhardface_amd/wider_eval.py, the AFW / Pascal Faces one smallhardface_amd/face_eval.py; ImageList runs
+them when a ground_truth directory holding the dataset's annotation files is given.
 """
 import os
 
@@ -82,7 +83,9 @@ class ImageList(object):
             except KeyError:
                 writer = write_detections_wider
         self._writer = writer
-        self._ground_truth = ground_truth   # WIDER: directory with wider_{face,easy,medium,hard}_val.mat
+        # WIDER: directory with wider_{face,easy,medium,hard}_val.mat; AFW: with new_annotations_AFW.mat; Pascal Faces: with
+        # Annotations_Face_PASCALLayout_large_fixed.mat
+        self._ground_truth = ground_truth
 
     def __len__(self):
         return len(self._image_paths)
@@ -107,4 +110,14 @@ class ImageList(object):
             ap, _ = wider_eval(out, self._ground_truth, mimic_eval_bug=cfg.MISC.MIMIC_EVAL_BUG,
                                IoU_thresh=cfg.TEST.IOU_THRESH, device=os.environ.get("SHF_DEVICE_EVAL") == "1")
             return 'Easy: {:.4f}, Medium: {:.4f}, Hard: {:.4f}'.format(*ap)
+        for writer, dataset, fname in ((write_detections_afw, 'AFW', 'afw_res.txt'),
+                                       (write_detections_pascal, 'PASCAL', 'pascal_res.txt')):
+            if self._writer is writer and self._ground_truth:
+                # what the reference's README leaves to external/marcopede-face-eval-f2870fd85d48/plot_AP.py
+                from .face_eval import ANNOTATION_FILES, face_eval
+                ann = os.path.join(self._ground_truth, ANNOTATION_FILES[dataset])
+                if os.path.exists(ann):
+                    ap = face_eval(os.path.join(out, fname), ann, dataset,
+                                   device=os.environ.get("SHF_DEVICE_EVAL") == "1")[0]
+                    return 'AP: {:.4f}'.format(ap)
         return 'detections written to {}'.format(out)
