@@ -309,13 +309,33 @@ class DevicePyramid(object):
     def window_units(self, ims, picks=None, scales=None, im_devs=None, net=None):
         """The units ``picks`` = [(image index in ``ims``, unit index)] (default: every unit of every image, image-major)
         of several images in ONE slot: what a rank of the pyramid-sharded schedule runs of a window
-        (pyramid.ShardedDetector) -- an image none of whose units is picked is not uploaded."""
+        (pyramid.ShardedDetector) -- an image none of whose units is picked is not uploaded.  ``ims[k]`` may be None
+        when ``im_devs[k]`` is a uint8 (h, w, 3) device TENSOR (not a bare pointer): the shape is then taken from the
+        tensor, so a rank needs no host copy of an image another rank decoded (pyramid.share_window_images)."""
         import torch
         net = net or self.net
-        geos = []
+        geos, hws = [], []
         for k, im in enumerate(ims):
-            sc = scales[k] if scales is not None and scales[k] is not None else pyramid_scales(im.shape)
-            im_h, im_w = im.shape[:2]
+            d = im_devs[k] if im_devs is not None else None
+            if im is None and d is None:
+                raise ValueError("DevicePyramid.window_units: image %d has neither a host array nor a device tensor" % k)
+            if isinstance(d, torch.Tensor):
+                # the kernel reads h * w * 3 bytes from this pointer: hold the tensor to exactly that before any launch
+                ok = d.dtype == torch.uint8 and d.is_cuda and d.is_contiguous()
+                if im is None:
+                    ok = ok and d.dim() == 3 and d.shape[2] == 3 and d.shape[0] >= 1 and d.shape[1] >= 1
+                else:
+                    ok = ok and d.numel() == int(np.prod(im.shape[:2])) * 3
+                if not ok:
+                    raise ValueError("DevicePyramid.window_units: image %d on the device must be a contiguous uint8 (h, w, 3) "
+                                     "tensor%s, got %s %s" % (k, "" if im is None else " of shape %s" % (tuple(im.shape),),
+                                                              d.dtype, tuple(d.shape)))
+            elif im is None:
+                raise ValueError("DevicePyramid.window_units: image %d without a host array needs a device TENSOR" % k)
+            shape = tuple(im.shape) if im is not None else tuple(int(v) for v in d.shape)
+            sc = scales[k] if scales is not None and scales[k] is not None else pyramid_scales(shape)
+            im_h, im_w = shape[:2]
+            hws.append((im_h, im_w))
             geo = []
             for s in sc:
                 lh, lw, H, W = caffe.pyramid_level_shape(im_h, im_w, s, cfg.MAX_RESOLUTION)
@@ -340,7 +360,7 @@ class DevicePyramid(object):
         out, off = [], 0
         for k, u in picks:
             lh, lw, H, W, s, flip = geos[k][u]
-            im_h, im_w = ims[k].shape[:2]
+            im_h, im_w = hws[k]
             ptr = slot[0].data_ptr() + 4 * off
             net.make_pyramid_level(devs[k].data_ptr(), im_h, im_w, s, flip, cfg.PIXEL_MEANS, ptr, H, W, lh, lw)
             out.append((ptr, H, W, lh, lw, s, flip))
@@ -736,16 +756,17 @@ def pyramid_sharded_inference(imdb, target_test, thresh=0.05, strict=False, prog
     """``TEST.SHARD = "pyramid"`` (or "pyramid_strict"): the north star's split of the work -- the PYRAMID of every image is
     sharded over the ranks of a torch.distributed job (one process per GPU, started by ``torch.distributed.run``), not the
     image list (lib/test.py:327-344, which ``TEST.SHARD = "images"`` keeps).  Windows of ``world`` images go through
-    pyramid.ShardedDetector: every rank decodes the window's images, builds ITS units on the device (DevicePyramid),
-    runs them as grouped passes, and the > thresh rows travel to the image's owner rank in ONE all_to_all per window
+    pyramid.ShardedDetector: every image is decoded by its owner rank alone and shared in one all-gather per window
+    (pyramid.WindowFeeder / share_window_images; ``SHF_SHARD_DECODE=all``: every rank decodes what its units need, no image
+    collective -- the same detections), every rank builds ITS units on the device (DevicePyramid), runs them as grouped
+    passes, and the > thresh rows travel to the image's owner rank in ONE all_to_all per window
     (RCCL; ``SHF_DIST_BACKEND=gloo`` for validation with several ranks on one GPU), which merges them.  At the end the
     owners' results are all-gathered so that every rank returns the full ``dets[class][image]`` lists.
 
     Device of rank r: ``TEST.GPU_ID[r]`` when the list has one entry per rank (``[0,0]``: two ranks on one GPU, gloo),
     LOCAL_RANK otherwise."""
     import torch
-    from concurrent.futures import ThreadPoolExecutor
-    from .pyramid import ShardedDetector
+    from .pyramid import ShardedDetector, WindowFeeder
     rank, world, local = dist_env()
     ids = cfg.TEST.GPU_ID if not isinstance(cfg.TEST.GPU_ID, int) else [cfg.TEST.GPU_ID]
     dev_id = int(ids[rank]) if len(ids) == world else local
@@ -784,37 +805,28 @@ def pyramid_sharded_inference(imdb, target_test, thresh=0.05, strict=False, prog
         n_windows = (n + world - 1) // world
         owned = {}
 
-        def window_plan(w):
-            base = w * world
-            n_valid = min(world, n - base)
-            picks = [(i, u) for (i, u) in sd.mine if i < n_valid]
-            need = sorted(set(i for i, _ in picks))
-            return base, n_valid, picks, need
-
         def read(i):
             im = _imread(imdb.image_path_at(i))
             if im is None:
                 raise IOError("cannot read image %s" % imdb.image_path_at(i))
             return im
 
-        pool = ThreadPoolExecutor(max_workers=max(1, min(4, world)))
+        # the input side: each image decoded ONCE, on its owner rank, and shared in one collective per window
+        # (SHF_SHARD_DECODE=all: the earlier path, every rank decodes the images its units need; read once, in the feeder)
+        feeder = WindowFeeder(read, n, rank, world, torch.device("cuda", dev_id),
+                              need=lambda n_valid: set(i for i, _ in sd.mine if i < n_valid))
+        prev_base = None
+        windows = iter(feeder)
         try:
-            ahead = None
-            prev_base = None
-            for w in range(n_windows):
-                base, n_valid, picks, need = window_plan(w)
-                futs = ahead if ahead is not None else {i: pool.submit(read, base + i) for i in need}
-                if w + 1 < n_windows:                       # the next window's decodes run under this window's GPU work
-                    nb, _, _, nneed = window_plan(w + 1)
-                    ahead = {i: pool.submit(read, nb + i) for i in nneed}
-                else:
-                    ahead = None
-                ims = [futs[i].result() for i in need]
+            for w, (base, n_valid, im_devs) in enumerate(windows):
+                picks = [(i, u) for (i, u) in sd.mine if i < n_valid]
+                need = sorted(set(i for i, _ in picks))
                 remap = {i: k for k, i in enumerate(need)}
                 ls = sd.lane_sets[sd._k & 1]                # the pass's head: its pre-processing runs in front of its convolutions
                 head = ls[0] if ls else net                 # (a rank without a share -- strict sharding, more ranks than levels)
-                units = dp.window_units(ims, [(remap[i], u) for (i, u) in picks], net=head)
-                done = sd.submit(units, picks=picks, n_valid=n_valid)
+                units = dp.window_units([None] * len(need), [(remap[i], u) for (i, u) in picks],
+                                        im_devs=[im_devs[i] for i in need], net=head)
+                done = sd.submit(units, picks=picks, n_valid=n_valid)   # (finishes window w - 1: the feeder's block order rests on it)
                 for i, d in done.items():
                     owned[prev_base + i] = d
                 prev_base = base
@@ -823,7 +835,9 @@ def pyramid_sharded_inference(imdb, target_test, thresh=0.05, strict=False, prog
             for i, d in sd.flush().items():
                 owned[prev_base + i] = d
         finally:
-            pool.shutdown(wait=True)
+            windows.close()                             # (stops the reader threads, also after a failure)
+        sd.host_seconds["images"] = feeder.stats()
+        logger.info("decoded %d of %d images, %d image collectives", feeder.reads, n, feeder.image_collectives)
         sd.sync()
         if dist is not None:
             parts = [None] * world
