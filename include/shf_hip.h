@@ -344,6 +344,12 @@ int shf_prof_reset(shf_net* net);
  * could reach.  Runs (reps + 1) / 2 settling launches, then times `reps` launches of `iters` x 24 MFMAs per wave on a
  * private stream; synchronises.  No counterpart in the reference (measurement only). */
 int shf_calib_matrix_pipe(int bf16, int zero_eighths, int constant_operands, int iters, int reps, double* tflops);
+/* Diagnostics (tests only): the launches the split-fp16 planner gives a 3x3 / pad 1 / dilation 1 convolution cin -> cout
+ * on one (1, h, w) unit -- in_split: its input is in the split activation format; pooled: a 2x2 max-pool is fused.
+ * Nothing is launched; no GPU is needed.  Per launch (at most two): the dynamic LDS it requests, its grid, and whether it
+ * runs the slim three-blocks-per-CU form of the 4-wave kernel.  Returns the number of launches, -1 with a message. */
+int shf_debug_conv_plan(int cin, int cout, int h, int w, int in_split, int pooled, long long* lds_bytes, long long* grid_blocks,
+                        int* slim);
 /* stream synchronise (end of a timed region) */
 int shf_net_sync(shf_net* net);
 

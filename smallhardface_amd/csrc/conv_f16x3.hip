@@ -145,6 +145,7 @@ const ConvKnobs& conv_knobs() {
     q.w4_mode = env_int("SHF_F16X3_W4", -1);
     q.w4_mt = env_int("SHF_F16X3_W4_MT", 0);
     q.w4d_ntile = env_int("SHF_F16X3_W4D_NTILE", 0);
+    q.w4_slim = env_int("SHF_F16X3_W4_SLIM", 1);
     q.heads3 = env_int("SHF_F16X3_HEADS3", 1);
     q.pc_tab = env_int("SHF_F16X3_PC_TAB", 1);
     q.pc = env_int("SHF_F16X3_PC", 1) != 0;
@@ -211,12 +212,20 @@ bool conv_f16x3_family_shape(int Cin, int Cout, int k, int pad, int dil, bool po
 // per CU; an 8-row block costs ~0.56 of a 16-row one (half the MFMAs, the same weight traffic per stage and the same
 // prologue / epilogue latencies).  SHF_F16X3_W4_MT = 2 / 4 forces the choice (experiments).
 // Short K loops (Cin <= 128: 24 stages) are the exception: there a block's prologue (first ~50 KB of weights and halo)
-// and epilogue (the output tile's store burst) are a third of its life, and the single-tile 8-row variant -- 66 KB of
-// LDS, 200 registers: TWO blocks per CU, one's epilogue under the other's K loop -- wins although it moves four times
-// the weight bytes per MFMA of a two-tile 16-row block.  Measured per layer on one box (tools/variant_layers.sh, us under
+// and epilogue (the output tile's store burst) are a third of its life, and the single-tile 8-row variant -- 81 152 B of
+// LDS (two halo buffers of 15 488 B, 2 x 3 weight slabs of 8 192 B, 512 B of biases), 200 registers: TWO blocks per CU
+// (162 304 of the 163 840 B), one's epilogue under the other's K loop -- wins although it moves four times the weight
+// bytes per MFMA of a two-tile 16-row block.  Measured per layer on one box (tools/variant_layers.sh, us under
 // rocprofv3): conv2_2 1212 vs 1278, conv3_1 625 vs 672, head_1 102 vs 109; from Cin 256 up it loses (conv3_2 1186 vs 1134,
 // conv4_2 1196 vs 1072).
 static bool w4_short_k(const ConvArgs* as) { return as[0].in.C <= 128; }
+constexpr size_t W4_SLIM_LDS_MAX = 163840 / 3 / 128 * 128;   // 54 528 B
+// The SLIM form of those single 8-row tiles (conv_mfma_f16x3_w4d_slim_kernel: one halo buffer, a ring of four tap slabs --
+// 48 768 B, at most 168 registers): THREE blocks per CU, so that a block's prologue and epilogue hide under two K loops.
+// Same bits.  Per layer on one box, us under rocprofv3, two against three per CU: conv2_1 714 vs 694, conv2_2 1181 vs 1142,
+// conv3_1 637 vs 629 (profiles/short_k_slim_ab.json): every short-K layer takes it.  SHF_F16X3_W4_SLIM = 0 keeps the
+// two-per-CU form (A/B, identity tests).
+static bool w4_slim(const ConvArgs* as) { return conv_knobs().w4_slim != 0 && w4_short_k(as) && as[0].in.C >= 64; }
 
 static int w4_pick_mt(const ConvArgs* as, int n, int nct) {
   if (conv_knobs().w4_mt == 2 || conv_knobs().w4_mt == 4) return conv_knobs().w4_mt;
@@ -247,6 +256,11 @@ static int w4_pick_mt(const ConvArgs* as, int n, int nct) {
    SHF_K(PC0, conv_mfma_f16x3_w4d_kernel<false, MT, NT, 1, false, DIL>), SHF_K(PC1, conv_mfma_f16x3_w4d_kernel<true, MT, NT, 3, false, DIL>),  \
    SHF_K(PC1, conv_mfma_f16x3_w4d_kernel<true, MT, NT, 2, false, DIL>), SHF_K(PC1, conv_mfma_f16x3_w4d_kernel<true, MT, NT, 1, false, DIL>),   \
    SHF_K(PC0, conv_mfma_f16x3_w4d_kernel<false, MT, NT, 1, true, DIL>)}
+#define SHF_W4S(PC0, PC1)                                                                                                  \
+  {SHF_K(PC0, conv_mfma_f16x3_w4d_slim_kernel<false, 3>), SHF_K(PC0, conv_mfma_f16x3_w4d_slim_kernel<false, 2>),             \
+   SHF_K(PC0, conv_mfma_f16x3_w4d_slim_kernel<false, 1>), SHF_K(PC1, conv_mfma_f16x3_w4d_slim_kernel<true, 3>),              \
+   SHF_K(PC1, conv_mfma_f16x3_w4d_slim_kernel<true, 2>), SHF_K(PC1, conv_mfma_f16x3_w4d_slim_kernel<true, 1>),               \
+   SHF_K(PC0, conv_mfma_f16x3_w4d_slim_kernel<false, 1, true>)}
 #define SHF_2NP3(PC, K)                                                                                                    \
   {SHF_K(PC, K<false, 3>), SHF_K(PC, K<false, 2>), SHF_K(PC, K<false, 1>), SHF_K(PC, K<true, 3>), SHF_K(PC, K<true, 2>),     \
    SHF_K(PC, K<true, 1>)}
@@ -257,6 +271,7 @@ struct F16x3Kernels {
   ConvKernel pc[2][4];       // conv_mfma_f16x3_pc_kernel: [PERSIST][NP]
   ConvKernel w4d[2][2][7];   // conv_mfma_f16x3_w4d_kernel, DIL 1: [MT 4, 2][NTILE 2, 1][IN_SPLIT x NP]
   ConvKernel w4d_dil[2][7];  // ... single 16-row tiles at DIL 2, 4: [DIL][IN_SPLIT x NP]
+  ConvKernel w4d_slim[7];    // ... the SLIM form of the single 8-row tiles, three blocks per CU: [IN_SPLIT x NP]
   ConvKernel k1[6];          // conv_mfma_f16x3_k1_kernel: [IN_SPLIT x NP]
   ConvKernel h3[6];          // conv_mfma_f16x3_heads3_kernel: [IN_SPLIT x NP]
 };
@@ -271,10 +286,12 @@ static const F16x3Kernels kK = {
     {{SHF_W4D(SHF_W4D_PC(0, 4, 2), SHF_W4D_PC(1, 4, 2), 4, 2, 1), SHF_W4D(SHF_W4D_PC(0, 4, 1), SHF_W4D_PC(1, 4, 1), 4, 1, 1)},
      {SHF_W4D(SHF_W4D_PC(0, 2, 2), SHF_W4D_PC(1, 2, 2), 2, 2, 1), SHF_W4D(SHF_W4D_PC(0, 2, 1), SHF_W4D_PC(1, 2, 1), 2, 1, 1)}},
     {SHF_W4D(PC_CONV_F16X3_W4D_D2, PC_CONV_F16X3_W4D_D2, 4, 1, 2), SHF_W4D(PC_CONV_F16X3_W4D_D4, PC_CONV_F16X3_W4D_D4, 4, 1, 4)},
+    SHF_W4S(SHF_W4D_PC(0, 2, 1), SHF_W4D_PC(1, 2, 1)),
     SHF_2NP3(PC_CONV_F16X3_K1G, conv_mfma_f16x3_k1_kernel),
     SHF_2NP3(PC_CONV_F16X3_H3, conv_mfma_f16x3_heads3_kernel)};
 #undef SHF_W4D_PC
 #undef SHF_2NP3
+#undef SHF_W4S
 #undef SHF_W4D
 #undef SHF_PC
 #undef SHF_8W
@@ -415,8 +432,14 @@ ConvPlan plan_conv_f16x3(const ConvArgs* as, int n) {
     const size_t as_b = 4 * ((size_t)(4 * mt + 2) * 24 * 16 + 32);
     const size_t lds1 = 2 * as_b + 2 * 3 * (size_t)BN * 64 + BN * sizeof(float), lds2 = lds1 + 2 * as_b;
     const auto& fam = kK.w4d[mt == 2];
+    // the slim single-tile form: one halo buffer, four tap slabs, biases -- a third of a CU's 163 840 B at the most
+    const bool slim = mt == 2 && n2 == 0 && w4_slim(as);
+    const size_t lds_slim = as_b + 4 * (size_t)BN * 64 + BN * sizeof(float);
+    if (slim && lds_slim > W4_SLIM_LDS_MAX) { pl.err = "conv f16x3: the slim form does not fit a third of the LDS"; return pl; }
     if (n2 > 0) add(fam[0][split_col(a)], ((n2 + 1) / 2) * nct, 256, lds2, 0, n2 * nct, (double)n2 / (double)tiles);
-    if (n2 < tiles) add(fam[1][split_col(a)], (tiles - n2) * nct, 256, lds1, n2, tiles * nct, (double)(tiles - n2) / (double)tiles);
+    if (n2 < tiles)
+      add(slim ? kK.w4d_slim[split_col(a)] : fam[1][split_col(a)], (tiles - n2) * nct, 256, slim ? lds_slim : lds1, n2, tiles * nct,
+          (double)(tiles - n2) / (double)tiles);
     return pl;
   }
   if (a.in_split) {
@@ -432,6 +455,27 @@ ConvPlan plan_conv_f16x3(const ConvArgs* as, int n) {
   const int dcol = a.k == 1 ? 3 : a.dil / 2;   // [DIL 1, 2, 4, then 1x1]
   add(a.img ? kK.w8_fuse1 : kK.w8[BN == 64][dcol][np_col(a)], tiles * nct, 512, lds, 0, 0, 1.0);
   return pl;
+}
+
+// diagnostics (shf_debug_conv_plan): the launches the planner gives a 3x3 / dilation-1 layer of the split-fp16 mode on one
+// (1, H, W) unit.  Nothing is launched and no device memory is touched: the views only have to look aligned.
+int conv_f16x3_plan_probe(int Cin, int Cout, int H, int W, int in_split, int pooled, long long* lds, long long* grid, int* slim) {
+  alignas(16) static float dummy[4];
+  ConvArgs a;
+  a.in = View{dummy, 1, H, W, Cin, Cin, 0};
+  a.out = View{dummy, 1, H, W, Cout, Cout, 0};
+  if (pooled) a.pool = View{dummy, 1, (H + 1) / 2, (W + 1) / 2, Cout, Cout, 0};
+  a.wsplit16 = dummy;
+  a.wsplit16h = dummy;
+  a.in_split = in_split ? 1 : 0;
+  const ConvPlan pl = plan_conv_f16x3(&a, 1);
+  if (pl.nl == 0) { set_error(pl.err.empty() ? "conv f16x3: no plan" : pl.err); return -1; }
+  for (int i = 0; i < pl.nl; ++i) {
+    lds[i] = (long long)pl.l[i].lds;
+    grid[i] = (long long)pl.l[i].grid.x;
+    slim[i] = pl.l[i].kern >= kK.w4d_slim && pl.l[i].kern < kK.w4d_slim + 7 ? 1 : 0;
+  }
+  return pl.nl;
 }
 
 // The three shared-weight dilated heads as ONE launch (conv_f16x3_h3.h): a1 / a2 / a4 = the dilation-1 / 2 / 4 layers'

@@ -804,6 +804,15 @@ int shf_calib_matrix_pipe(int bf16, int zero_eighths, int constant_operands, int
   return 0;
   API_END(-1)
 }
+int shf_debug_conv_plan(int cin, int cout, int h, int w, int in_split, int pooled, long long* lds_bytes, long long* grid_blocks,
+                        int* slim) {
+  API_BEGIN
+  if (!lds_bytes || !grid_blocks || !slim || cin < 1 || cout < 1 || h < 1 || w < 1) throw std::runtime_error("debug_conv_plan: bad arguments");
+  const int nl = conv_f16x3_plan_probe(cin, cout, h, w, in_split, pooled, lds_bytes, grid_blocks, slim);
+  if (nl < 0) return -1;
+  return nl;
+  API_END(-1)
+}
 int shf_net_sync(shf_net* net) {
   API_BEGIN
   HIP_THROW(hipStreamSynchronize(net->stream));

@@ -319,6 +319,7 @@ int conv_out(int n, int k, int pad, int stride, int dil);
 
 namespace shf {
 int calib_matrix_pipe(int bf16, int zero_eighths, int constant, int iters, int reps, double* tflops);   // calib.hip
+int conv_f16x3_plan_probe(int Cin, int Cout, int H, int W, int in_split, int pooled, long long* lds, long long* grid, int* slim);   // conv_f16x3.hip
 }
 using namespace shf;
 

@@ -82,6 +82,8 @@ struct ConvKnobs {
   int w4_mode;      // SHF_F16X3_W4: -1 auto (Cin >= 64), 0 never, 1 always -- which layers take the 4-wave dual-tile family
   int w4_mt;        // SHF_F16X3_W4_MT: 0 auto, 2 / 4 force 8- / 16-row tiles
   int w4d_ntile;    // SHF_F16X3_W4D_NTILE: 0 auto (hybrid launches), 1 / 2 force single- / two-tile blocks
+  int w4_slim;      // SHF_F16X3_W4_SLIM: 1 (default) = short-K single 8-row tiles take the slim form, three blocks per CU
+                    // (conv_mfma_f16x3_w4d_slim_kernel); 0 = the two-per-CU form; bit-identical
   int pc_tab;       // SHF_F16X3_PC_TAB: 0 = the persistent first pair decodes its tiles one by one (the path launches with more
                     // than 300 tiles per block take anyway); bit-identical
   int heads3;       // SHF_F16X3_HEADS3: 1 (default) = the three shared-weight dilated heads as ONE launch (conv_f16x3_h3.h),
