@@ -333,16 +333,35 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
     const int base_size = ps.count("base_size") ? (int)ps["base_size"][0] : 16;
     const bool subsampled = ps.count("subsampled") ? ps["subsampled"][0] != 0 : true;
     if (ps.count("num_feats") && ps["num_feats"][0] != 1) throw std::runtime_error("tail: num_feats != 1 unsupported");
+    // what the reference's layer cannot run is refused here with the layer's name, not answered: an empty list raises in its
+    // setup, a stride below 1 divides by zero in the subsampling map (proposal_layer.py:163-164)
+    if (fs.empty() || scales.empty() || ratios.empty() || shifts.empty())
+      throw std::runtime_error("ProposalLayer '" + T.name + "': feat_stride, scales, ratios and shifts need at least one entry");
+    for (double v : fs)
+      if (!(v >= 1 && v <= 4096))
+        throw std::runtime_error("ProposalLayer '" + T.name + "': feat_stride entries must be in 1 .. 4096");
     gen_anchors(base_size, ratios, scales, shifts, fs, anchors);
     tail_A = (int)anchors.size() / 4;
+    if (tail_A < 1) throw std::runtime_error("ProposalLayer '" + T.name + "': the param string yields no anchors");
+    if (tail_A > 8) throw std::runtime_error("tail: more than 8 anchors per cell unsupported");
     feat_stride = (int)fs[0];
     sub_stride.assign(tail_A, 1);
-    if (subsampled)
+    if (subsampled) {
+      // anchor i is kept on every (feat_stride[i // len(shifts)**2] // feat_stride[0])-th row and column
+      // (proposal_layer.py:160-165): with fewer feat_stride entries than that index reaches the reference raises IndexError
+      const size_t need = (size_t)(tail_A - 1) / (shifts.size() * shifts.size()) + 1;
+      if (fs.size() < need)
+        throw std::runtime_error("ProposalLayer '" + T.name + "': feat_stride has " + std::to_string(fs.size()) +
+                                 " entries, the anchor subsampling of " + std::to_string(tail_A) + " anchors indexes " +
+                                 std::to_string(need) + " (the reference raises IndexError); give one stride per anchor "
+                                 "group or 'subsampled': False");
       for (int i = 0; i < tail_A; ++i) {
         const size_t idx = (size_t)i / (shifts.size() * shifts.size());
-        sub_stride[i] = (int)fs[std::min(idx, fs.size() - 1)] / (int)fs[0];
+        sub_stride[i] = (int)fs[idx] / (int)fs[0];
+        if (sub_stride[i] < 1)   // (a slice step of zero: ValueError in the reference)
+          throw std::runtime_error("ProposalLayer '" + T.name + "': feat_stride entries must not be smaller than the first one");
       }
-    if (tail_A > 8) throw std::runtime_error("tail: more than 8 anchors per cell unsupported");
+    }
     if (tail_heads != 1 && tail_heads != tail_A) throw std::runtime_error("tail: heads must be 1 or == anchors");
     const int ncls = tail_heads == 1 ? 2 * tail_A : 2, nbox = tail_heads == 1 ? 4 * tail_A : 4;
     for (int i = 0; i < tail_heads; ++i)
@@ -385,6 +404,23 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
 
   // ---- params (shapes need channel counts: run shape inference once)
   infer_shapes();
+  // the per-head tail packs Cf weights per row from every head's predictors and reads Cf channels of every head blob at the
+  // first one's map size (build_tail_weights, tail_logits_kernel): heads of another shape would be read out of bounds
+  if (tail_layer >= 0) {
+    const std::vector<int>& s0 = blobs[tail_feat_blobs[0]].shape;
+    if (s0.size() != 4)
+      throw std::runtime_error("ProposalLayer '" + layers[tail_layer].name + "': head blob '" + blobs[tail_feat_blobs[0]].name + "' is not 4-D");
+    for (int fb : tail_feat_blobs) {
+      const std::vector<int>& s = blobs[fb].shape;
+      if (s.size() != 4 || s[1] != s0[1])
+        throw std::runtime_error("ProposalLayer '" + layers[tail_layer].name + "': head blobs '" + blobs[tail_feat_blobs[0]].name +
+                                 "' and '" + blobs[fb].name + "' differ in channel count (" + std::to_string(s0[1]) + " vs " +
+                                 std::to_string(s.size() == 4 ? s[1] : 0) + "): the per-head predictors must read heads of one width");
+      if (s[2] != s0[2] || s[3] != s0[3])
+        throw std::runtime_error("ProposalLayer '" + layers[tail_layer].name + "': head blobs '" + blobs[tail_feat_blobs[0]].name +
+                                 "' and '" + blobs[fb].name + "' differ in map size");
+    }
+  }
   for (size_t li = 0; li < layers.size(); ++li) {
     Layer& L = layers[li];
     if (L.type != "Convolution" && L.type != "Deconvolution") continue;

@@ -3,7 +3,10 @@
 
 Run in the authoring container only (needs /root/reference):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [OUTDIR]
+
+OUTDIR (default: this directory) receives every fixture; to add one fixture without touching the committed ones, write
+to a scratch directory, compare the arrays of the others and copy only the new file over.
 
 What it does (nothing from the reference is copied into this repo):
   * converts /root/reference/lib + configs to py3 in a scratch TEMP dir with
@@ -18,7 +21,8 @@ What it does (nothing from the reference is copied into this repo):
 
 Reference entry points exercised (file:line in /root/reference):
   lib/layers/generate_anchors.py:11   generate_anchors
-  lib/layers/proposal_layer.py:60     ProposalLayer.forward (TEST phase)
+  lib/layers/proposal_layer.py:60     ProposalLayer.forward (TEST phase), also under param strings with two / three
+                                      ratios, shifts, unequal strides, base sizes 8 / 12 and 'subsampled': False
   lib/utils/bbox_transform.py:33,80   bbox_transform_inv / clip_boxes
   lib/test.py:181                     bbox_vote
   lib/nms/py_cpu_nms.py:10            py_cpu_nms
@@ -42,7 +46,23 @@ import types
 import numpy as np
 
 REF = "/root/reference"
-OUT = os.path.dirname(os.path.abspath(__file__))
+HERE = os.path.dirname(os.path.abspath(__file__))
+OUT = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else HERE
+
+# ProposalLayer param strings beyond the templates' (proposal_geometry.npz); every anchor stays <= 64 px
+GEOMETRIES = [
+    # anchors 22x12, 33x18, 12x24, 18x36; zip(scales, strides) drops two strides; sub-strides 1, 2, 2, 2
+    ("two_ratios_mixed_strides", "{'feat_stride': [8,16,16,16], 'scales': [2,3], 'ratios': [0.5,2], 'base_size': 8}"),
+    # four shifted copies per scale, A = 8; sub-strides 1,1,1,1,2,2,2,2
+    ("shifts_two_strides", "{'feat_stride': [8,16], 'scales': [1,2], 'ratios': [1,], 'shifts': [0,0.5]}"),
+    # the unfiltered map, A = 6, anchors from 11x22 to 46x24
+    ("three_ratios_dense", "{'feat_stride': [8,8], 'scales': [1,2], 'ratios': [0.5,1,2], 'subsampled': False}"),
+    # feat_stride[0] != 8; sub-strides 1, 2, 4 on an odd map: ragged last row and column
+    ("strides_4_8_16", "{'feat_stride': [4,8,16], 'scales': [1,2,4], 'ratios': [2,], 'base_size': 12}"),
+]
+GEOMETRY_MAP = (7, 9)
+GEOMETRY_SCALE = 1.5
+GEOMETRY_MIN_SIZE = 6
 
 
 # --------------------------------------------------------------------------
@@ -229,7 +249,7 @@ def main():
     fake_cv2.INTER_LINEAR = 1
     fake_cv2._images = {}
     fake_cv2.imread = lambda p: fake_cv2._images[p].copy()
-    sys.path.insert(0, os.path.join(OUT, "..", ".."))
+    sys.path.insert(0, os.path.join(HERE, "..", ".."))
 
     def _resize(im, a, b, fx=None, fy=None, interpolation=None):
         from oracle.resize import cv_resize_linear_f64
@@ -362,6 +382,81 @@ def main():
     b, p = run_proposal(sc, dl, ii)
     prop.update(ties_scores=sc, ties_deltas=dl, ties_im_info=ii, ties_boxes=b, ties_probs=p)
     np.savez_compressed(os.path.join(OUT, "proposal.npz"), **prop)
+
+    # ---------------- ProposalLayer.forward under other param strings --------
+    # per geometry: TEST.ANCHOR_MIN_SIZE 0 and GEOMETRY_MIN_SIZE on the same inputs, an unpadded image a few pixels below
+    # h * feat_stride[0], im_info scale 1.5.  The seed is the first one for which no side of any box lies within 0.01 px
+    # of min_size * scale (judged with the oracle's restatement, which the CPU test then holds to these vectors): the
+    # kept set must not hinge on the last ulp of exp().
+    import ast
+    from oracle import oracle as O
+    geo = {}
+    gh, gw = GEOMETRY_MAP
+
+    def geometry_inputs(pstr, seed, dstd):
+        kw = ast.literal_eval(pstr)
+        A = O.generate_anchors(kw.get("base_size", 16), kw["ratios"], kw["scales"], kw.get("shifts", [0]),
+                               kw["feat_stride"]).shape[0]
+        r = np.random.default_rng(seed)
+        fg = r.uniform(0.001, 0.9, (A, gh, gw)).astype(np.float32)
+        sc = np.concatenate([1 - fg, fg], 0)[None].astype(np.float32)
+        dl = r.normal(0, dstd, (1, 4 * A, gh, gw)).astype(np.float32)
+        s0 = kw["feat_stride"][0]
+        ii = np.array([[gh * s0 - 3, gw * s0 - 5, GEOMETRY_SCALE]], dtype=np.float32)
+        return kw, A, sc, dl, ii
+
+    def sides_clear_of_cut(kw, sc, dl, ii):
+        b, _ = O.proposal_forward(sc, dl, ii, O.ProposalParams(min_size=0, score_thresh=-1.0, pre_nms_topN=0, **kw))
+        cut = GEOMETRY_MIN_SIZE * GEOMETRY_SCALE
+        sides = np.concatenate([b[:, 3] - b[:, 1] + 1, b[:, 4] - b[:, 2] + 1])
+        return np.abs(sides - cut).min() > 0.01
+
+    def record(case, pstr, sc, dl, ii, min_size):
+        old_ms = cfg.TEST.ANCHOR_MIN_SIZE
+        cfg.TEST.ANCHOR_MIN_SIZE = min_size
+        try:
+            b, p = run_proposal(sc, dl, ii, pstr)
+        finally:
+            cfg.TEST.ANCHOR_MIN_SIZE = old_ms
+        geo[case + "_scores"] = sc
+        geo[case + "_deltas"] = dl
+        geo[case + "_im_info"] = ii
+        geo[case + "_min_size"] = np.array([min_size], np.float32)
+        geo[case + "_boxes"] = b
+        geo[case + "_probs"] = p
+        geo[case + "_param_str"] = np.array(pstr)
+        geo_cases.append(case)
+        return b
+
+    geo_cases = []
+    for gi, (name, pstr) in enumerate(GEOMETRIES):
+        seed = 100 * (gi + 1)
+        while True:
+            kw, A, sc, dl, ii = geometry_inputs(pstr, seed, 0.3 + 0.05 * gi)
+            if sides_clear_of_cut(kw, sc, dl, ii):
+                break
+            seed += 1
+        total = gh * gw * A
+        n0 = len(record(name + "_ms0", pstr, sc, dl, ii, 0))
+        n6 = len(record(name + "_ms%d" % GEOMETRY_MIN_SIZE, pstr, sc, dl, ii, GEOMETRY_MIN_SIZE))
+        assert 0 < n6 < n0 <= total, (name, n6, n0, total)   # the cut removes some rows, not all
+        print("proposal_geometry %s: seed %d, A %d, rows %d / %d of %d" % (name, seed, A, n0, n6, total))
+    # the overflow / clamp branch on non-square anchors (np.seterr(over='raise'), bbox_transform.py:9,52-65):
+    #   _overflow          dw = 130 on the 22x12 anchor: exp() itself overflows fp32
+    #   _overflow_product  dw = 85.9 there: exp(85.9) is finite, times the WIDTH 22 it overflows, times the height 12 it
+    #                      would not (ln FLT_MAX = 88.72 < 85.9 + ln 22 = 88.99, > 85.9 + ln 12 = 88.38)
+    #   _big_finite        dh = 85.9 there: against the height 12 nothing overflows and nothing is clamped
+    # each with a second delta above 50 that is clamped only when the flag is raised, under an im_info of 6000 x 8000 px:
+    # a clamped side is exp(5) * 24 = 3562 px and ends inside that image, an unclamped one ends at its border
+    name, pstr = GEOMETRIES[0]
+    for tag, row, val in (("overflow", 2, 130.0), ("overflow_product", 2, 85.9), ("big_finite", 3, 85.9)):
+        kw, A, sc, dl, ii = geometry_inputs(pstr, 77, 0.3)
+        ii[0, :2] = (6000, 8000)
+        dl[0, row, 2, 4] = val          # anchor 0 (22 wide, 12 high), rows 4 a + (dx, dy, dw, dh)
+        dl[0, 4 * 2 + 3, 4, 2] = 60.0   # dh of anchor 2 at a cell its sub-stride 2 keeps
+        record(name + "_" + tag, pstr, sc, dl, ii, 0)
+    geo["cases"] = np.array(geo_cases)
+    np.savez_compressed(os.path.join(OUT, "proposal_geometry.npz"), **geo)
 
     # ---------------- bbox_vote / py_cpu_nms ---------------------------
     vn = {}

@@ -58,7 +58,7 @@ def _predictor(name, bottom, top, nout):
             'kernel_size: 1 pad: 0 stride: 1 } }\n' % (name, bottom, top, nout))
 
 
-def mini_detector(layers_txt, probe, feat_stride, cin=3, h=8, w=8):
+def mini_detector(layers_txt, probe, feat_stride, cin=3, h=8, w=8, param_str=None):
     """`single_layer_net(layers_txt)` + a proposal tail on the blob(s) `probe`, so that Net.forward() takes the fused
     path (a graph without a tail never does) and the tail's fp32 logits kernel can copy the probed blob out.
 
@@ -66,17 +66,19 @@ def mini_detector(layers_txt, probe, feat_stride, cin=3, h=8, w=8):
     Softmax, Reshape, ProposalLayer with ratios [1,], eight scales and eight equal feat_stride entries: A = 8 anchors.
     `probe` a list of 2 .. 8 names (blobs of one size): the dilated template's tail -- per blob i the predictors
     `cls_score_<i>` (2 channels) / `bbox_pred_<i>` (4), scores concatenated on axis 2, deltas on axis 1, one anchor per
-    blob.  Every probed blob needs C % 128 == 0 (the logits kernel's vector width)."""
+    blob.  Every probed blob needs C % 128 == 0 (the logits kernel's vector width).
+    `param_str` (A, text): the ProposalLayer's param string and the A anchors it yields, instead of the default's; the
+    single-blob tail then has 2A / 4A predictor outputs and the per-blob tail needs A blobs (`feat_stride` is unused)."""
     s = int(feat_stride)
     if isinstance(probe, str):
-        A = 8
+        A = 8 if param_str is None else int(param_str[0])
         tail = (_predictor("cls_score", probe, "cls_score_output", 2 * A) +
                 _predictor("bbox_pred", probe, "bbox_pred_output", 4 * A) +
                 'layer { name: "cls_reshape" type: "Reshape" bottom: "cls_score_output" top: "cls_score_reshape_output" '
                 'reshape_param { shape { dim: 0 dim: 2 dim: -1 dim: 0 } } }\n')
     else:
         A = len(probe)
-        assert 2 <= A <= 8
+        assert 2 <= A <= 8 and (param_str is None or A == int(param_str[0]))
         tail = "".join(_predictor("cls_score_%d" % i, p, "cls_score_%d_output" % i, 2) +
                        _predictor("bbox_pred_%d" % i, p, "bbox_pred_%d_output" % i, 4) for i, p in enumerate(probe))
         tail += ('layer { name: "cls_score_output_concat" type: "Concat" %s top: "cls_score_reshape_output" '
@@ -88,8 +90,9 @@ def mini_detector(layers_txt, probe, feat_stride, cin=3, h=8, w=8):
              'reshape_param { shape { dim: 0 dim: %d dim: -1 dim: 0 } } }\n' % (2 * A))
     tail += ('layer { name: "proposal" type: "Python" bottom: "cls_prob_reshape_output" bottom: "bbox_pred_output" '
              'bottom: "im_info" top: "boxes" top: "cls_prob" python_param { module: "lib.layers.proposal_layer" '
-             'layer: "ProposalLayer" param_str: "{\'feat_stride\': [%s],\'scales\': [%s], \'ratios\':[1,]}" } }\n'
-             % (",".join([str(s)] * A), ",".join(str(i + 1) for i in range(A))))
+             'layer: "ProposalLayer" param_str: "%s" } }\n'
+             % (param_str[1] if param_str is not None else "{'feat_stride': [%s],'scales': [%s], 'ratios':[1,]}"
+                % (",".join([str(s)] * A), ",".join(str(i + 1) for i in range(A)))))
     return single_layer_net(layers_txt + tail, cin, h, w)
 
 
