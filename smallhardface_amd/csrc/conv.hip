@@ -26,8 +26,7 @@ namespace shf {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int KC = 32;   // input channels per K chunk
-constexpr int LDK = 36;  // LDS row pitch in floats (32 + 4 pad: conflict-free ds_read_b128)
+constexpr int KC = 32;   // input channels per K chunk (LDK, the LDS row pitch: conv_lds_layout.h)
 
 // DIL is a template parameter (1/2/4 in the detector, 0 = "1x1, no halo") so the halo tile
 // size is a compile-time constant: its loads are fully unrolled, all issued back to back
@@ -41,13 +40,14 @@ __global__ __launch_bounds__(256, 1) void conv_mfma_f32_kernel(ConvK p) {
   constexpr int WN = BN / 64;  // waves along cout
   constexpr int WM = 4 / WN;   // waves along pixels
   static_assert(TH == 4 * WM && TW == 16, "tile shape");
-  constexpr int PAD = (KS == 3) ? DIL : 0;
-  constexpr int HTW = TW + 2 * PAD, HTH = TH + 2 * PAD;
-  constexpr int HP = HTH * HTW;
+  using L = F32Lds<KS, DIL, BN, TH>;
+  constexpr int PAD = L::PAD;
+  constexpr int HTW = TW + 2 * PAD;
+  constexpr int HP = L::HP;
   constexpr int ALD = (HP * 8 + 255) / 256;  // float4 halo pieces per thread
   constexpr int BLD = BN * 8 / 256;          // float4 weight pieces per thread
-  float* As = smem;              // [HP][LDK]
-  float* Bs = smem + HP * LDK;   // [2][BN][LDK]
+  float* As = smem + L::As;      // [HP][LDK]
+  float* Bs = smem + L::Bs;      // [2][BN][LDK]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wn = wave % WN, wm = wave / WN;
@@ -379,14 +379,10 @@ int conv_kernel_class(int Cin, int Cout, int k, int pad, int dil, bool in_nchw) 
   return 2;
 }
 
-static size_t mfma_lds_bytes(int k, int dil, int BN, int TH, int TW) {
-  const int pad = k == 3 ? dil : 0;
-  return ((size_t)(TH + 2 * pad) * (TW + 2 * pad) * LDK + 2 * (size_t)BN * LDK) * sizeof(float);
-}
-
 // Every instantiation of conv_mfma_f32_kernel, in the order of its profiler classes (PC_CONV_MFMA + index): 3x3 at dilation
 // 1, 2, 4, then 1x1, each as BN 128 (8-row tiles) and BN 64 (16-row tiles)
-#define SHF_F32(I, KS, DIL, BN, TH) {(const void*)conv_mfma_f32_kernel<KS, DIL, BN, TH, 16>, PC_CONV_MFMA + I}
+// (conv_lds: every entry's layout fits the 160 KiB the attribute set-up asks for, or the table does not compile)
+#define SHF_F32(I, KS, DIL, BN, TH) {(const void*)conv_mfma_f32_kernel<KS, DIL, BN, TH, 16>, PC_CONV_MFMA + I, conv_lds<F32Lds<KS, DIL, BN, TH>>()}
 static const ConvKernel kF32Kernels[8] = {SHF_F32(0, 3, 1, 128, 8), SHF_F32(1, 3, 2, 128, 8), SHF_F32(2, 3, 4, 128, 8),
                                           SHF_F32(3, 3, 1, 64, 16), SHF_F32(4, 3, 2, 64, 16), SHF_F32(5, 3, 4, 64, 16),
                                           SHF_F32(6, 1, 0, 128, 8), SHF_F32(7, 1, 0, 64, 16)};
@@ -426,7 +422,7 @@ static ConvPlan plan_conv_f32(const ConvArgs* as, int n) {
   pl.k.dbg = dbg_dev;
   pl.timing_report = f32_timing_report;
 #endif
-  pl.l[pl.nl++] = {&kern, dim3((unsigned)(tiles * pl.k.nct)), dim3(256), mfma_lds_bytes(a.k, a.dil, BN, TH, TW), 0, 0, 1.0};
+  pl.l[pl.nl++] = {&kern, dim3((unsigned)(tiles * pl.k.nct)), dim3(256), kern.lds, 0, 0, 1.0};
   return pl;
 }
 

@@ -1,5 +1,6 @@
 // Shared by the convolution translation units (conv.hip: exact fp32 MFMA; conv_f16x3.hip: split-fp16 MFMA).
 #pragma once
+#include "conv_lds_layout.h"
 #include "shf_internal.h"
 
 namespace shf {
@@ -131,7 +132,7 @@ __device__ __forceinline__ void conv_store_tile(GetV getv, float bv, int flags, 
 // channel axis: float4 per lane, 512 contiguous bytes per pixel, and the fused 2x2 pool becomes a max
 // over four float4 rows.  Needs 16-byte aligned channel views (the launcher checks and otherwise keeps
 // the scalar conv_store_tile path).
-constexpr int CS_PAD = 16;  // 2 x (BN + CS_PAD) words = 32 (mod 64 banks): the two half-waves of a staging ds_write_b32 (pixels x, x+2) never share a bank
+// (CS_PAD, the row padding: conv_lds_layout.h)
 
 // stage the 2x16-pixel x 32-cout MFMA tile of one lane: local rows ly0, ly0+1; `cl` = local cout
 template <int BN, typename GetV>
@@ -731,6 +732,7 @@ __device__ __forceinline__ void conv_epilogue_regs1(const cs_f32x16 acc, float s
 struct ConvKernel {   // one compiled instantiation: an entry of the kernel tables in conv.hip / conv_f16x3.hip
   const void* fn;
   int prof;           // ProfClass its launches are booked under
+  size_t lds;         // its dynamic LDS: the bytes of its layout (conv_lds_layout.h), from the template arguments that instantiate it
 };
 struct ConvLaunch {
   const ConvKernel* kern;

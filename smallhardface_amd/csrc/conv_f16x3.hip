@@ -20,6 +20,7 @@
 //   conv_f16x3_h3.h    conv_mfma_f16x3_heads3_kernel -- the three shared-weight dilated heads (dilation 1 / 2 / 4) in ONE launch
 //   conv_f16x3_8w.h    conv_mfma_f16x3_kernel     -- 8 waves: what the others cannot take (Cout 64, other 1x1s, unaligned views)
 //   conv_f16x3_types.h vector types, the hi / lo split, the MFMA wrapper, conv1_1's K-slot map
+//   conv_lds_layout.h  (through conv_common.h) every kernel's LDS regions and total, and the tile geometry they are made of
 // Common structure: tile 256 px (16x16) x BN couts; a STAGE is one kernel row (3 taps) of one channel chunk: its weight
 // slabs are double-buffered in LDS and arrive by LDS DMA; the halo tile is staged once per chunk and reused by all 9 taps.
 // 8-wave / first-pair LDS rows are [hi: 32 halfs][lo: 32 halfs][16 B pad] = 144 B (conflict-free ds_read_b128 over
@@ -212,16 +213,15 @@ bool conv_f16x3_family_shape(int Cin, int Cout, int k, int pad, int dil, bool po
 // per CU; an 8-row block costs ~0.56 of a 16-row one (half the MFMAs, the same weight traffic per stage and the same
 // prologue / epilogue latencies).  SHF_F16X3_W4_MT = 2 / 4 forces the choice (experiments).
 // Short K loops (Cin <= 128: 24 stages) are the exception: there a block's prologue (first ~50 KB of weights and halo)
-// and epilogue (the output tile's store burst) are a third of its life, and the single-tile 8-row variant -- 81 152 B of
+// and epilogue (the output tile's store burst) are a third of its life, and the single-tile 8-row variant -- 80 640 B of
 // LDS (two halo buffers of 15 488 B, 2 x 3 weight slabs of 8 192 B, 512 B of biases), 200 registers: TWO blocks per CU
-// (162 304 of the 163 840 B), one's epilogue under the other's K loop -- wins although it moves four times the weight
+// (161 280 of the 163 840 B), one's epilogue under the other's K loop -- wins although it moves four times the weight
 // bytes per MFMA of a two-tile 16-row block.  Measured per layer on one box (tools/variant_layers.sh, us under
 // rocprofv3): conv2_2 1212 vs 1278, conv3_1 625 vs 672, head_1 102 vs 109; from Cin 256 up it loses (conv3_2 1186 vs 1134,
 // conv4_2 1196 vs 1072).
 static bool w4_short_k(const ConvArgs* as) { return as[0].in.C <= 128; }
-constexpr size_t W4_SLIM_LDS_MAX = 163840 / 3 / 128 * 128;   // 54 528 B
 // The SLIM form of those single 8-row tiles (conv_mfma_f16x3_w4d_slim_kernel: one halo buffer, a ring of four tap slabs --
-// 48 768 B, at most 168 registers): THREE blocks per CU, so that a block's prologue and epilogue hide under two K loops.
+// 48 768 B, within W4_SLIM_LDS_MAX, at most 168 registers): THREE blocks per CU, so that a block's prologue and epilogue hide under two K loops.
 // Same bits.  Per layer on one box, us under rocprofv3, two against three per CU: conv2_1 714 vs 694, conv2_2 1181 vs 1142,
 // conv3_1 637 vs 629 (profiles/short_k_slim_ab.json): every short-K layer takes it.  SHF_F16X3_W4_SLIM = 0 keeps the
 // two-per-CU form (A/B, identity tests).
@@ -244,29 +244,31 @@ static int w4_pick_mt(const ConvArgs* as, int n, int nct) {
 // Every kernel instantiation of the split-fp16 modes, each with the profiler class its launches are booked under.  Columns:
 // NP = 3, 2, 1 fp16 products, then bf16 (one product on bf16 operands); [IN_SPLIT x NP] = the fp32-input forms, the split-input
 // forms, then bf16 (fp32 activations: no split input).
-#define SHF_K(PC, ...) {(const void*)__VA_ARGS__, PC}
-#define SHF_8W(PC, BN, DIL, KS)                                                                                            \
-  {SHF_K(PC, conv_mfma_f16x3_kernel<BN, false, DIL, KS, 3>), SHF_K(PC, conv_mfma_f16x3_kernel<BN, false, DIL, KS, 2>),       \
-   SHF_K(PC, conv_mfma_f16x3_kernel<BN, false, DIL, KS, 1>), SHF_K(PC, conv_mfma_f16x3_kernel<BN, false, DIL, KS, 1, true>)}
-#define SHF_PC(PC, PERSIST)                                                                                                \
-  {SHF_K(PC, conv_mfma_f16x3_pc_kernel<3, false, PERSIST>), SHF_K(PC, conv_mfma_f16x3_pc_kernel<2, false, PERSIST>),         \
-   SHF_K(PC, conv_mfma_f16x3_pc_kernel<1, false, PERSIST>), SHF_K(PC, conv_mfma_f16x3_pc_kernel<1, true, PERSIST>)}
+// An entry's LDS size is its layout's (conv_lds_layout.h), named by the same macro arguments as the kernel; conv_lds<>
+// refuses at compile time a layout beyond the 160 KiB conv_set_lds_attributes asks for.
+#define SHF_8W1(PC, BN, DIL, KS, FUSE1, ...) \
+  {(const void*)conv_mfma_f16x3_kernel<BN, FUSE1, DIL, KS, __VA_ARGS__>, PC, conv_lds<W8Lds<BN, DIL, KS, FUSE1>>()}
+#define SHF_8W(PC, BN, DIL, KS) \
+  {SHF_8W1(PC, BN, DIL, KS, false, 3), SHF_8W1(PC, BN, DIL, KS, false, 2), SHF_8W1(PC, BN, DIL, KS, false, 1), SHF_8W1(PC, BN, DIL, KS, false, 1, true)}
+#define SHF_PC1(PC, NP, BF, PERSIST) {(const void*)conv_mfma_f16x3_pc_kernel<NP, BF, PERSIST>, PC, conv_lds<PcLds>()}
+#define SHF_PC(PC, PERSIST) {SHF_PC1(PC, 3, false, PERSIST), SHF_PC1(PC, 2, false, PERSIST), SHF_PC1(PC, 1, false, PERSIST), SHF_PC1(PC, 1, true, PERSIST)}
+#define SHF_W4D1(PC, SPLIT, MT, NT, NP, BF, DIL) \
+  {(const void*)conv_mfma_f16x3_w4d_kernel<SPLIT, MT, NT, NP, BF, DIL>, PC, conv_lds<W4dLds<MT, NT, DIL, false>>()}
 #define SHF_W4D(PC0, PC1, MT, NT, DIL)                                                                                     \
-  {SHF_K(PC0, conv_mfma_f16x3_w4d_kernel<false, MT, NT, 3, false, DIL>), SHF_K(PC0, conv_mfma_f16x3_w4d_kernel<false, MT, NT, 2, false, DIL>), \
-   SHF_K(PC0, conv_mfma_f16x3_w4d_kernel<false, MT, NT, 1, false, DIL>), SHF_K(PC1, conv_mfma_f16x3_w4d_kernel<true, MT, NT, 3, false, DIL>),  \
-   SHF_K(PC1, conv_mfma_f16x3_w4d_kernel<true, MT, NT, 2, false, DIL>), SHF_K(PC1, conv_mfma_f16x3_w4d_kernel<true, MT, NT, 1, false, DIL>),   \
-   SHF_K(PC0, conv_mfma_f16x3_w4d_kernel<false, MT, NT, 1, true, DIL>)}
+  {SHF_W4D1(PC0, false, MT, NT, 3, false, DIL), SHF_W4D1(PC0, false, MT, NT, 2, false, DIL), SHF_W4D1(PC0, false, MT, NT, 1, false, DIL), \
+   SHF_W4D1(PC1, true, MT, NT, 3, false, DIL), SHF_W4D1(PC1, true, MT, NT, 2, false, DIL), SHF_W4D1(PC1, true, MT, NT, 1, false, DIL),    \
+   SHF_W4D1(PC0, false, MT, NT, 1, true, DIL)}
+#define SHF_W4S1(PC, ...) {(const void*)conv_mfma_f16x3_w4d_slim_kernel<__VA_ARGS__>, PC, conv_lds<W4dLds<2, 1, 1, true>>()}
 #define SHF_W4S(PC0, PC1)                                                                                                  \
-  {SHF_K(PC0, conv_mfma_f16x3_w4d_slim_kernel<false, 3>), SHF_K(PC0, conv_mfma_f16x3_w4d_slim_kernel<false, 2>),             \
-   SHF_K(PC0, conv_mfma_f16x3_w4d_slim_kernel<false, 1>), SHF_K(PC1, conv_mfma_f16x3_w4d_slim_kernel<true, 3>),              \
-   SHF_K(PC1, conv_mfma_f16x3_w4d_slim_kernel<true, 2>), SHF_K(PC1, conv_mfma_f16x3_w4d_slim_kernel<true, 1>),               \
-   SHF_K(PC0, conv_mfma_f16x3_w4d_slim_kernel<false, 1, true>)}
-#define SHF_2NP3(PC, K)                                                                                                    \
-  {SHF_K(PC, K<false, 3>), SHF_K(PC, K<false, 2>), SHF_K(PC, K<false, 1>), SHF_K(PC, K<true, 3>), SHF_K(PC, K<true, 2>),     \
-   SHF_K(PC, K<true, 1>)}
+  {SHF_W4S1(PC0, false, 3), SHF_W4S1(PC0, false, 2), SHF_W4S1(PC0, false, 1), SHF_W4S1(PC1, true, 3), SHF_W4S1(PC1, true, 2),  \
+   SHF_W4S1(PC1, true, 1), SHF_W4S1(PC0, false, 1, true)}
+#define SHF_2NP3(PC, K, L)                                                                                                 \
+  {{(const void*)K<false, 3>, PC, conv_lds<L>()}, {(const void*)K<false, 2>, PC, conv_lds<L>()}, {(const void*)K<false, 1>, PC, conv_lds<L>()}, \
+   {(const void*)K<true, 3>, PC, conv_lds<L>()}, {(const void*)K<true, 2>, PC, conv_lds<L>()}, {(const void*)K<true, 1>, PC, conv_lds<L>()}}
 struct F16x3Kernels {
-  ConvKernel w8[2][4][4];    // conv_mfma_f16x3_kernel: [BN 128, 64][DIL 1, 2, 4 (3x3), then 1x1][NP]; the BN 128 dilated rows
-                             // are never selected (those heads take the family's DIL form)
+  ConvKernel w8_128[2][4];   // conv_mfma_f16x3_kernel at BN 128: [3x3 DIL 1, 1x1][NP] (its dilated forms would need 168 / 194 KB
+                             // of LDS: dilated layers with Cout % 128 == 0 take BN 64 here, or the family's DIL form)
+  ConvKernel w8_64[4][4];    // ... at BN 64: [DIL 1, 2, 4 (3x3), then 1x1][NP]
   ConvKernel w8_fuse1;       // ... conv1_1 computed in the halo staging
   ConvKernel pc[2][4];       // conv_mfma_f16x3_pc_kernel: [PERSIST][NP]
   ConvKernel w4d[2][2][7];   // conv_mfma_f16x3_w4d_kernel, DIL 1: [MT 4, 2][NTILE 2, 1][IN_SPLIT x NP]
@@ -277,25 +279,27 @@ struct F16x3Kernels {
 };
 #define SHF_W4D_PC(SPLIT, MT, NT) (PC_CONV_F16X3_W4D_0 + 4 * SPLIT + (MT == 2 ? 2 : 0) + (NT == 1 ? 1 : 0))
 static const F16x3Kernels kK = {
-    {{SHF_8W(PC_CONV_F16X3_128, 128, 1, 3), SHF_8W(PC_CONV_F16X3_64_D2, 128, 2, 3), SHF_8W(PC_CONV_F16X3_64_D4, 128, 4, 3),
-      SHF_8W(PC_CONV_F16X3_128_K1, 128, 1, 1)},
-     {SHF_8W(PC_CONV_F16X3_64, 64, 1, 3), SHF_8W(PC_CONV_F16X3_64_D2, 64, 2, 3), SHF_8W(PC_CONV_F16X3_64_D4, 64, 4, 3),
-      SHF_8W(PC_CONV_F16X3_64_K1, 64, 1, 1)}},
-    SHF_K(PC_CONV_F16X3_64_FUSE1, conv_mfma_f16x3_kernel<64, true, 1, 3, 3>),
+    {SHF_8W(PC_CONV_F16X3_128, 128, 1, 3), SHF_8W(PC_CONV_F16X3_128_K1, 128, 1, 1)},
+    {SHF_8W(PC_CONV_F16X3_64, 64, 1, 3), SHF_8W(PC_CONV_F16X3_64_D2, 64, 2, 3), SHF_8W(PC_CONV_F16X3_64_D4, 64, 4, 3),
+     SHF_8W(PC_CONV_F16X3_64_K1, 64, 1, 1)},
+    SHF_8W1(PC_CONV_F16X3_64_FUSE1, 64, 1, 3, true, 3),
     {SHF_PC(PC_CONV_F16X3_PC, false), SHF_PC(PC_CONV_F16X3_PCP, true)},
     {{SHF_W4D(SHF_W4D_PC(0, 4, 2), SHF_W4D_PC(1, 4, 2), 4, 2, 1), SHF_W4D(SHF_W4D_PC(0, 4, 1), SHF_W4D_PC(1, 4, 1), 4, 1, 1)},
      {SHF_W4D(SHF_W4D_PC(0, 2, 2), SHF_W4D_PC(1, 2, 2), 2, 2, 1), SHF_W4D(SHF_W4D_PC(0, 2, 1), SHF_W4D_PC(1, 2, 1), 2, 1, 1)}},
     {SHF_W4D(PC_CONV_F16X3_W4D_D2, PC_CONV_F16X3_W4D_D2, 4, 1, 2), SHF_W4D(PC_CONV_F16X3_W4D_D4, PC_CONV_F16X3_W4D_D4, 4, 1, 4)},
     SHF_W4S(SHF_W4D_PC(0, 2, 1), SHF_W4D_PC(1, 2, 1)),
-    SHF_2NP3(PC_CONV_F16X3_K1G, conv_mfma_f16x3_k1_kernel),
-    SHF_2NP3(PC_CONV_F16X3_H3, conv_mfma_f16x3_heads3_kernel)};
+    SHF_2NP3(PC_CONV_F16X3_K1G, conv_mfma_f16x3_k1_kernel, K1Lds),
+    SHF_2NP3(PC_CONV_F16X3_H3, conv_mfma_f16x3_heads3_kernel, H3Lds)};
 #undef SHF_W4D_PC
 #undef SHF_2NP3
 #undef SHF_W4S
+#undef SHF_W4S1
 #undef SHF_W4D
+#undef SHF_W4D1
 #undef SHF_PC
+#undef SHF_PC1
 #undef SHF_8W
-#undef SHF_K
+#undef SHF_8W1
 static_assert(sizeof(F16x3Kernels) % sizeof(ConvKernel) == 0, "the attribute set-up walks the table as one array");
 
 int conv_f16x3_init_attributes() {
@@ -367,8 +371,8 @@ ConvPlan plan_conv_f16x3(const ConvArgs* as, int n) {
     if (!vec_ok) { pl.err = "conv f16x3: split-format output needs the aligned epilogue"; return pl; }
     p.flags |= (a.out_split ? CONV_MAIN_SPLIT : 0) | (a.pool_split ? CONV_POOL_SPLIT : 0);
   }
-  auto add = [&](const ConvKernel& kern, long long grid, int block, size_t lds, long long tile_base, long long ntile_blocks, double share) {
-    pl.l[pl.nl++] = {&kern, dim3((unsigned)grid), dim3(block), lds, (int)tile_base, (int)ntile_blocks, share};
+  auto add = [&](const ConvKernel& kern, long long grid, int block, long long tile_base, long long ntile_blocks, double share) {
+    pl.l[pl.nl++] = {&kern, dim3((unsigned)grid), dim3(block), kern.lds, (int)tile_base, (int)ntile_blocks, share};
   };
 #ifdef SHF_CONV_TIMING
   if (!(family && a.k == 1)) {
@@ -378,36 +382,28 @@ ConvPlan plan_conv_f16x3(const ConvArgs* as, int n) {
   }
 #endif
   if (family && a.k == 1) {   // blocks of 256 pixels of each member's flat pixel list x 256 couts
-    add(kK.k1[split_col(a)], tiles * nct, 256, 3 * 256 * 128 + 2 * 2 * 256 * 64, 0, 0, 1.0);   // (all 160 KiB: three activation
-    return pl;                                                                                  // chunks + two weight chunks)
+    add(kK.k1[split_col(a)], tiles * nct, 256, 0, 0, 1.0);
+    return pl;
   }
   if (a.img && kn.pc && vec_ok && a.out.C == 64 && a.w1f && a.wsplit16r) {
     p.wp = (const float*)a.wsplit16r;   // its own pack: 128-byte rotated rows (pack_conv_weights_split16r)
-    // two halo tiles (both channel chunks of conv1_1's output; rows of 18 pixels x 144 B + 96 B) + the weight double buffer
-    // (128-byte rows) + the image patch (+ conv1_1's weight fragments 8 KiB, its 64 biases, the row-tile counter)
-    constexpr size_t HPP = (HP + 31) / 32 * 32;
-    const size_t lds_pc = 2 * (size_t)(TH + 2) * ((TW + 2) * ROWB + 96) + 2 * 3 * (size_t)64 * 128 + (3 * (TH + 4) * (TW + 4) + 8) * sizeof(float) + HPP +
-                          64 * sizeof(float) + 8192 + 64 * sizeof(float) + 16 + 64 + 300 * 4;
-    if (lds_pc > 160 * 1024) { pl.err = "conv f16x3: the fused first pair does not fit the LDS"; return pl; }
     if (!kn.pc_persist) {
-      add(kK.pc[0][np_col(a)], tiles, 512, lds_pc, 0, 0, 1.0);
+      add(kK.pc[0][np_col(a)], tiles, 512, 0, 0, 1.0);
       return pl;
     }
     // one block per CU walks the tiles (tile = block, block + grid, ...)
     const long long grid = std::min<long long>(tiles, kn.cus);
-    // the per-block tile table: fits (300 tiles per block) and packs (image < 256, tile row / column < 1024)?
-    bool ok = kn.pc_tab != 0 && (tiles + grid - 1) / grid <= 300;
+    // the per-block tile table: fits (PC_TABN = 300 tiles per block) and packs (image < 256, tile row / column < 1024)?
+    bool ok = kn.pc_tab != 0 && (tiles + grid - 1) / grid <= PcLds::PC_TABN;
     for (int i = 0; i < n; ++i)
       ok = ok && as[i].in.B <= 255 && p.m[i].tiles_x <= 1023 && p.m[i].tiles_per_img / std::max(1, p.m[i].tiles_x) <= 1023;
     p.pc_tab = ok ? 1 : 0;
-    add(kK.pc[1][np_col(a)], grid, 512, lds_pc, 0, tiles, 1.0);
+    add(kK.pc[1][np_col(a)], grid, 512, 0, tiles, 1.0);
     return pl;
   }
   if (family && a.dil > 1) {
     // the dilated heads on the family's DIL form: single 16-row tiles (halo tiles of (16 + 2 DIL)^2 pixels, two buffer sets)
-    const size_t as_b = 4 * ((size_t)(16 + 2 * a.dil) * 24 * 16 + 32);
-    add(kK.w4d_dil[a.dil == 4][split_col(a)], tiles * nct, 256, 2 * as_b + 2 * 3 * (size_t)BN * 64 + BN * sizeof(float), 0,
-        tiles * nct, 1.0);
+    add(kK.w4d_dil[a.dil == 4][split_col(a)], tiles * nct, 256, 0, tiles * nct, 1.0);
     return pl;
   }
   if (dual) {
@@ -428,17 +424,12 @@ ConvPlan plan_conv_f16x3(const ConvArgs* as, int n) {
     if (w4_short_k(as) && kn.w4_mt == 0) n2 = 0;               // two single-tile blocks per CU (w4_pick_mt)
     if (kn.w4d_ntile == 1) n2 = 0;
     if (kn.w4d_ntile == 2) n2 = tiles;
-    // two buffer sets of halo tiles (4 planes of (rows + 2) x 24 pixels x 16 B, + 32 B), the weight double buffer, biases
-    const size_t as_b = 4 * ((size_t)(4 * mt + 2) * 24 * 16 + 32);
-    const size_t lds1 = 2 * as_b + 2 * 3 * (size_t)BN * 64 + BN * sizeof(float), lds2 = lds1 + 2 * as_b;
     const auto& fam = kK.w4d[mt == 2];
-    // the slim single-tile form: one halo buffer, four tap slabs, biases -- a third of a CU's 163 840 B at the most
+    // the slim single-tile form (a third of a CU's LDS at the most: W4_SLIM_LDS_MAX)
     const bool slim = mt == 2 && n2 == 0 && w4_slim(as);
-    const size_t lds_slim = as_b + 4 * (size_t)BN * 64 + BN * sizeof(float);
-    if (slim && lds_slim > W4_SLIM_LDS_MAX) { pl.err = "conv f16x3: the slim form does not fit a third of the LDS"; return pl; }
-    if (n2 > 0) add(fam[0][split_col(a)], ((n2 + 1) / 2) * nct, 256, lds2, 0, n2 * nct, (double)n2 / (double)tiles);
+    if (n2 > 0) add(fam[0][split_col(a)], ((n2 + 1) / 2) * nct, 256, 0, n2 * nct, (double)n2 / (double)tiles);
     if (n2 < tiles)
-      add(slim ? kK.w4d_slim[split_col(a)] : fam[1][split_col(a)], (tiles - n2) * nct, 256, slim ? lds_slim : lds1, n2, tiles * nct,
+      add(slim ? kK.w4d_slim[split_col(a)] : fam[1][split_col(a)], (tiles - n2) * nct, 256, n2, tiles * nct,
           (double)(tiles - n2) / (double)tiles);
     return pl;
   }
@@ -447,13 +438,9 @@ ConvPlan plan_conv_f16x3(const ConvArgs* as, int n) {
     return pl;
   }
   if (a.bf16 && a.img) { pl.err = "conv f16x3: bf16 mode runs the first pair on the producer/consumer kernel only"; return pl; }
-  // 8-wave kernel; (the transposed epilogue needs 256 x (BN + 4) floats: the 1x1 variant's K-loop buffers are smaller than that)
-  const int KS = a.k == 1 ? 1 : 3, padh = a.k == 1 ? 0 : a.dil;
-  const size_t hp = (size_t)(TH + 2 * padh) * (TW + 2 * padh);
-  const size_t lds = std::max(hp * ROWB + 2 * KS * (size_t)BN * ROWB, (size_t)256 * (BN + CS_PAD) * sizeof(float)) +
-                     (a.img ? (3 * (TH + 4) * (TW + 4) + 27 * 64 + 64) * sizeof(float) : 0);
+  // 8-wave kernel; BN is 128 only at dilation 1 and for 1x1 layers (above)
   const int dcol = a.k == 1 ? 3 : a.dil / 2;   // [DIL 1, 2, 4, then 1x1]
-  add(a.img ? kK.w8_fuse1 : kK.w8[BN == 64][dcol][np_col(a)], tiles * nct, 512, lds, 0, 0, 1.0);
+  add(a.img ? kK.w8_fuse1 : BN == 128 ? kK.w8_128[a.k == 1][np_col(a)] : kK.w8_64[dcol][np_col(a)], tiles * nct, 512, 0, 0, 1.0);
   return pl;
 }
 
@@ -518,9 +505,8 @@ ConvPlan plan_conv_heads3(const ConvArgs* a1, const ConvArgs* a2, const ConvArgs
     m.out2_amax = a2[i].out_amax;
     m.out3_amax = a4[i].out_amax;
   }
-  const size_t as_b = 4 * ((size_t)16 * 24 * 16 + 32);
-  pl.l[pl.nl++] = {&kK.h3[split_col(a)], dim3((unsigned)tiles), dim3(256), 2 * as_b + 2 * 3 * (size_t)128 * 64 + 128 * sizeof(float), 0,
-                   (int)tiles, 1.0};
+  const ConvKernel& kern = kK.h3[split_col(a)];
+  pl.l[pl.nl++] = {&kern, dim3((unsigned)tiles), dim3(256), kern.lds, 0, (int)tiles, 1.0};
   return pl;
 }
 

@@ -22,8 +22,9 @@ __global__ __launch_bounds__(512) void conv_mfma_f16x3_kernel(ConvK p) {
   // buffers would not fit the 160 KiB of LDS)
   // KS = 3: a stage is one kernel row (3 taps) of a 32-channel chunk; KS = 1 (1x1 convolutions): a stage is
   // the single tap of a chunk, no halo, and every stage hands the next chunk's tile over
-  constexpr int PADH = KS == 3 ? DIL : 0, KROWS = KS == 3 ? 3 : 1;
-  constexpr int HTW = TW + 2 * PADH, HTH = TH + 2 * PADH, HP = HTH * HTW;
+  using L = W8Lds<BN, DIL, KS, FUSE1>;
+  constexpr int PADH = L::PADH, KROWS = KS == 3 ? 3 : 1;
+  constexpr int HTW = TW + 2 * PADH, HP = L::HP;
   static_assert(KS == 3 || (KS == 1 && DIL == 1 && !FUSE1), "kernel sizes 3 (any dilation) and 1");
   static_assert(!FUSE1 || DIL == 1, "the fused first layer is a dilation-1 path");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -34,13 +35,13 @@ __global__ __launch_bounds__(512) void conv_mfma_f16x3_kernel(ConvK p) {
   constexpr int WM = 8 / WN;
   constexpr int MT = TH / (2 * WM);      // 2x16-pixel MFMA row tiles per wave: 2 (BN=128) or 1 (BN=64)
   constexpr int ALD = (HP * 8 + 511) / 512;  // float4 halo pieces per thread: 6
-  unsigned char* As = smem;                  // [HP][ROWB]
-  unsigned char* Bs = smem + HP * ROWB;      // [2][3][BN][ROWB]
+  unsigned char* As = smem + L::As;          // [HP][ROWB]
+  unsigned char* Bs = smem + L::Bs;          // [2][3][BN][ROWB]
   // FUSE1 extras behind the weight buffers
-  constexpr int PW = TW + 4, PH = TH + 4;    // image patch: halo of the halo
-  float* patch = (float*)(Bs + 2 * KS * BN * ROWB);  // [3][PH][PW]
-  float* w1s = patch + 3 * PH * PW;                 // [27][64]
-  float* b1s = w1s + 27 * 64;                       // [64]
+  constexpr int PW = L::PW, PH = L::PH;      // image patch: halo of the halo
+  float* patch = (float*)(smem + L::patch);  // [3][PH][PW]
+  float* w1s = (float*)(smem + L::w1s);      // [27][64]
+  float* b1s = (float*)(smem + L::b1s);      // [64]
   // first-layer weights [27][64]: read through the CONSTANT address space so that the wave-uniform accesses
   // become s_load_dwordx8/16 (scalar cache -> SGPRs), not per-lane memory instructions
   const __attribute__((address_space(4))) float* w1g = (const __attribute__((address_space(4))) float*)(unsigned long long)p.w1t;
@@ -341,7 +342,7 @@ __global__ __launch_bounds__(512) void conv_mfma_f16x3_kernel(ConvK p) {
   float amax = 0.f;  // fp16 range guard: largest |output| of this lane
   if (p.flags & CONV_VEC_EPI) {
     __syncthreads();  // the K loop's LDS buffers are dead: the output tile is transposed through them
-    float* Cs = (float*)smem;
+    float* Cs = (float*)(smem + L::Cs);
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn) {
       const int cl = wn * 64 + tn * 32 + i;

@@ -25,18 +25,16 @@ template <bool IN_SPLIT, int NP = 3>
 __global__ __launch_bounds__(256) void conv_mfma_f16x3_heads3_kernel(ConvK p) {
   constexpr int MT = 2, TH = 4 * MT, TW = 16, PADH = 4, HTW = TW + 2 * PADH, HTH = TH + 2 * PADH, HP = HTH * HTW;
   static_assert(HTW == 24, "the halo rows are exactly the 24-pixel plane rows");
-  constexpr int KC = 16, BN = 128, NT = 256;
-  constexpr int PROW = 24 * 16;
-  constexpr int PLANE = HTH * PROW + 32;
-  constexpr int AS_B = 4 * PLANE;                     // 24 704 B per halo tile
-  constexpr int WROWB = 64;
-  constexpr int SLAB_B = BN * WROWB;
+  using L = H3Lds;                                    // (the family's planes and slabs: conv_lds_layout.h)
+  static_assert(L::HTH == HTH, "the layout's planes hold this kernel's halo rows");
+  constexpr int KC = 16, BN = L::BN, NT = 256;
+  constexpr int PROW = L::PROW, PLANE = L::PLANE, AS_B = L::AS_B, WROWB = L::WROWB, SLAB_B = L::SLAB_B;   // 24 704 B per halo tile
   constexpr int ALD = HP * 4 / NT;                    // 6 sixteen-byte halo pieces per thread and chunk
   static_assert(HP * 4 == ALD * NT, "no ragged piece");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* As = smem;                           // [2 buffer sets][4 planes][HTH][24 px][16 B]
-  unsigned char* Bs = smem + 2 * AS_B;                // [2 buffers][3 taps][BN][64 B]
-  float* biasL = (float*)(Bs + 2 * 3 * SLAB_B);       // [BN]
+  unsigned char* As = smem + L::As;                   // [2 buffer sets][4 planes][HTH][24 px][16 B]
+  unsigned char* Bs = smem + L::Bs;                   // [2 buffers][3 taps][BN][64 B]
+  float* biasL = (float*)(smem + L::biasL);           // [BN]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wn = wave & 1, wm = wave >> 1;

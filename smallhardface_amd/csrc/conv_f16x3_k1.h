@@ -39,13 +39,12 @@ namespace shf {
 // epilogue.
 template <bool IN_SPLIT, int NP = 3>
 __global__ __launch_bounds__(256) void conv_mfma_f16x3_k1_kernel(ConvK p) {
-  constexpr int BN = 256, PXB = 256, NTN = BN / 32, WROWB = 64;
-  constexpr int SLAB_B = BN * WROWB;                 // 16 KiB: one 16-channel slab of the block's couts
-  constexpr int BUF_B = 2 * SLAB_B;                  // a 32-channel chunk of weights
-  constexpr int ABUF_B = PXB * 128;                  // a 32-channel chunk of the block's pixels
+  using L = K1Lds;                                   // (chunk buffers, epilogue rows: conv_lds_layout.h)
+  constexpr int BN = L::BN, PXB = L::PXB, NTN = BN / 32, WROWB = L::WROWB;
+  constexpr int SLAB_B = L::SLAB_B, BUF_B = L::BUF_B, ABUF_B = L::ABUF_B;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* As = smem;                          // [3 buffers][256 pixels][128 B]
-  unsigned char* Bs = smem + 3 * ABUF_B;             // [2 buffers][2 slabs][BN][64 B]
+  unsigned char* As = smem + L::As;                  // [3 buffers][256 pixels][128 B]
+  unsigned char* Bs = smem + L::Bs;                  // [2 buffers][2 slabs][BN][64 B]
 
 #ifdef SHF_K1_TIMING
   const unsigned long long t_entry = __builtin_amdgcn_s_memtime();
@@ -273,13 +272,13 @@ __global__ __launch_bounds__(256) void conv_mfma_f16x3_k1_kernel(ConvK p) {
       // exchange needed) --, then per pixel ONE 1-KiB store of 64 consecutive lanes; a lane's four couts are the same in every
       // row, so bias, ReLU (on the bit patterns) and the max |output| happen there, with one bias quad per lane.  Same
       // operations on the same values as the register form.
-      constexpr int EROW = BN * 4 + 16;
+      constexpr int EROW = L::EROW;
       const float4 bq = p.bias ? *(const float4*)(p.bias + ct * BN + lane * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
       __syncthreads();                                // every wave is done with the K loop's buffers
 #ifdef SHF_K1_TIMING
       tb = __builtin_amdgcn_s_memtime();
 #endif
-      unsigned char* Ew = smem + wave_u * (32 * EROW);
+      unsigned char* Ew = smem + L::Ew + wave_u * L::EW_B;
       unsigned tmax = 0u;
 #pragma unroll
       for (int tm = 0; tm < 2; ++tm) {

@@ -44,43 +44,28 @@ __global__ __launch_bounds__(512) void conv_mfma_f16x3_pc_kernel(ConvK p) {
 #define PC_T()
 #endif
   PC_T();
-  constexpr int BN = 64, MT = 2;
-  constexpr int PW = TW + 4, PH = TH + 4;
-  constexpr int HPP = (HP + 31) / 32 * 32;          // 352: tile rows padded to whole 32-row MFMA tiles
-  // HALO TILES (round 5): a pixel is ROWB = 144 B ([hi 32 | lo 32 | 16 B]: eight consecutive pixels of a row fall on eight
-  // different 16-byte bank groups), a halo ROW is 18 pixels + 96 B = 2 688 B = 128 mod 256: the 16 lanes of a
-  // ds_read_b128 group are 8 pixels of row y and 8 of row y + 1 (row_to_pixel), and with the plain 18 x 144 = 2 592 B rows
-  // (32 mod 256) the second row's groups fell two slots beside the first's -- a 2-way conflict on every A-fragment read
-  // (SQ_LDS_BANK_CONFLICT 0.32 of the kernel's LDS cycles in rounds 3-4, and the consumers' K loop is LDS-bound: 8 KiB of
-  // fragments per 12 MFMAs and wave).  The 3.4 KB the padding costs come from the weight rows (below).
-  constexpr int AROW = HTW * ROWB + 96;             // 2 688 B per halo row
-  constexpr int AT_B = HTH * AROW;                  // 48 384 B per halo tile
-  static_assert(AROW % 256 == 128, "consecutive halo rows on complementary halves of the bank row");
-  // WEIGHT ROWS are 128 B without padding (the 8-wave kernel's pack has 144-byte rows): the eight 16-byte pieces of cout
-  // row r -- hi k 0-7 .. 24-31, lo k 0-7 .. 24-31 -- are rotated by (r >> 1) mod 8 (pack_conv_weights_split16r), so the 16
-  // lanes of a B-fragment read (16 consecutive rows, one logical piece) still cover all 16 bank groups; a tap slab is
-  // 8 KiB = 8 DMA pieces, a stage 24 = six rounds of the four producer waves with no ragged one.
-  constexpr int WROWB = 128;
-  unsigned char* As0 = smem;                        // [HTH][AROW] channels  0..31 of conv1_1's output
-  unsigned char* As1 = smem + AT_B;                 // [HTH][AROW] channels 32..63
-  unsigned char* Bs = smem + 2 * AT_B;              // [2][3][BN][WROWB]
+  // (the halo tiles' padded rows, the unpadded rotated weight rows and every region below: PcLds, conv_lds_layout.h)
+  using L = PcLds;
+  constexpr int BN = L::BN, MT = 2;
+  constexpr int PW = L::PW, PH = L::PH, HPP = L::HPP, AROW = L::AROW, WROWB = L::WROWB;
+  unsigned char* As0 = smem + L::As0;               // [HTH][AROW] channels  0..31 of conv1_1's output
+  unsigned char* As1 = smem + L::As1;               // [HTH][AROW] channels 32..63
+  unsigned char* Bs = smem + L::Bs;                 // [2][3][BN][WROWB]
   // [3][PH][PW] image patch, already split: fp16 hi in the low half of a dword, fp16 lo (x 2^11) in the high half (bf16 mode:
   // the bf16 pattern | 0) -- conv1_1's fragments are then gathered with one byte permute per register, no conversion
   // (round 4; the conversions used to be redone for every fragment element: ~200 vector instructions per row tile).
   // (+ 8 dwords: half-wave 1's zero-weight slots read one element past a tap)
-  unsigned* patch = (unsigned*)(Bs + 2 * 3 * BN * WROWB);
-  constexpr int PATCH_DW = 3 * PH * PW + 8;
-  unsigned char* valid = (unsigned char*)(patch + PATCH_DW);  // [HPP] halo pixel inside the image? (0 in the padding)
-  float* bias2L = (float*)(valid + HPP);                          // [BN] conv1_2's biases (read by the register epilogue)
+  unsigned* patch = (unsigned*)(smem + L::patch);
+  unsigned char* valid = smem + L::valid;                         // [HPP] halo pixel inside the image? (0 in the padding)
+  float* bias2L = (float*)(smem + L::bias2L);                     // [BN] conv1_2's biases (read by the register epilogue)
   // conv1_1's operands live in LDS (round 4): its weight fragments [n][kk][hi/lo][lane][8 halfs] (8 KiB, the global pack
   // as it is) and biases -- read where a row tile needs them (ds_read latency, no registers held across anything), by
   // whichever wave has claimed the row tile
-  unsigned char* w1L = (unsigned char*)(bias2L + BN);             // 8192 B
-  float* b1L = (float*)(w1L + 8192);                              // [64]
-  unsigned* ctrL = (unsigned*)(b1L + 64);                         // [0] next row tile of the next tile's conv1_1 to claim, [1] its halo_inside
-  unsigned* geoL = ctrL + 4;                                      // [16] the next tile's geometry (TileGeo), decoded ONCE, by a producer
-  constexpr int PC_TABN = 300;
-  unsigned* tabL = geoL + 16;                                     // [PC_TABN] packed geometry of the tiles this block walks (ConvK::pc_tab)
+  unsigned char* w1L = smem + L::w1L;                             // 8192 B
+  float* b1L = (float*)(smem + L::b1L);                           // [64]
+  unsigned* ctrL = (unsigned*)(smem + L::ctrL);                   // [0] next row tile of the next tile's conv1_1 to claim, [1] its halo_inside
+  unsigned* geoL = (unsigned*)(smem + L::geoL);                   // [16] the next tile's geometry (TileGeo), decoded ONCE, by a producer
+  unsigned* tabL = (unsigned*)(smem + L::tabL);                   // [PC_TABN] packed geometry of the tiles this block walks (ConvK::pc_tab)
 
   int tid = threadIdx.x, lane = tid & 63;
   const int wave = tid >> 6;

@@ -19,10 +19,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define F16X3_CONV_MID 1   // 1: split the next halo tile to fp16 hi/lo in the middle of the last stage's MFMAs
 #endif
 
-namespace f16x3 {
-constexpr int KC = 32;      // input channels per chunk
-constexpr int ROWB = 144;   // bytes per LDS row (pixel or cout)
-constexpr int TH = 16, TW = 16, HTW = TW + 2, HTH = TH + 2, HP = HTH * HTW;
+namespace f16x3 {   // (KC, ROWB and the 16 x 16 tile with its halo: conv_lds_layout.h)
 constexpr float LO_SCALE = 2048.0f, LO_INV = 1.0f / 2048.0f;
 }  // namespace f16x3
 

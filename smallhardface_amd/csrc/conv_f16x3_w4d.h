@@ -33,7 +33,7 @@ namespace shf {
 // fragment address is lane offset + immediate: tap kx = +16 B, kernel row = +384 B, lo = +2 planes.
 // DIL (round 4): the dilated shared-weight heads (dilation 2 / 4, Cin = Cout = 128) run here too, as single 16-row tiles:
 // the halo tile is (16 + 2 DIL)^2 pixels -- 20 or 24 per row, inside the 24-pixel plane rows --, a tap is DIL pixels / DIL
-// plane rows further, nothing else changes (111 / 123 KB of LDS).  They used to take the 8-wave kernel's 64-cout form (a
+// plane rows further, nothing else changes (111 360 / 123 648 B of LDS).  They used to take the 8-wave kernel's 64-cout form (a
 // fragment read per MFMA: 0.29 issued).
 // SLIM (single 8-row tiles at dilation 1, the short-K layers): the same block in at most a third of a CU -- ONE halo
 // buffer and a RING of four tap slabs instead of two buffer sets and the 2 x 3 weight double buffer: 15 488 + 32 768 +

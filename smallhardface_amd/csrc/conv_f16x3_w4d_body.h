@@ -7,18 +7,15 @@
   static_assert(DIL == 1 || ((DIL == 2 || DIL == 4) && MT_ == 4 && NTILE == 1), "dilated layers: single 16-row tiles");
   constexpr int MT = MT_, TH = 4 * MT, TW = 16, HTW = TW + 2 * DIL, HTH = TH + 2 * DIL, HP = HTH * HTW;
   constexpr int UNUSED = 24 - HTW;                    // plane-row pixels no halo pixel uses (they take the ragged last piece)
-  constexpr int KC = 16, BN = 128, NT = 256;
-  constexpr int PROW = 24 * 16;                       // 384 B per halo-tile row of a plane (18 pixels used)
-  constexpr int PLANE = HTH * PROW + 32;              // 6 944 B (16-row tiles) / 3 872 B (8-row tiles)
-  constexpr int AS_B = 4 * PLANE;                     // 27 776 B / 15 488 B per halo tile
-  constexpr int NB_B = NTILE * AS_B;                  // one buffer set (the tiles of one chunk)
-  constexpr int WROWB = 64;                           // weight rows: no padding, the 16-byte pieces rotated by row / 4
-  constexpr int SLAB_B = BN * WROWB;                  // 8 192 B per tap slab
+  using L = W4dLds<MT_, NTILE, DIL, SLIM>;            // (planes, buffer sets, slabs: conv_lds_layout.h)
+  static_assert(L::HTH == HTH, "the layout's planes hold this kernel's halo rows");
+  constexpr int KC = 16, BN = L::BN, NT = 256;
+  constexpr int PROW = L::PROW, PLANE = L::PLANE, AS_B = L::AS_B, NB_B = L::NB_B, WROWB = L::WROWB, SLAB_B = L::SLAB_B;
   constexpr int ALD = (HP * 4 + NT - 1) / NT;         // 16-byte halo pieces per thread and tile: 6 (16 rows) or 3
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* As = smem;                           // [2 buffer sets][NTILE][4 planes][HTH][24 px][16 B]
-  unsigned char* Bs = smem + (SLIM ? 1 : 2) * NB_B;   // [2 buffers][3 taps][BN][64 B]; SLIM: a ring of [4 slabs][BN][64 B]
-  float* biasL = (float*)(Bs + (SLIM ? 4 : 2 * 3) * SLAB_B);   // [BN]
+  unsigned char* As = smem + L::As;                   // [2 buffer sets][NTILE][4 planes][HTH][24 px][16 B]
+  unsigned char* Bs = smem + L::Bs;                   // [2 buffers][3 taps][BN][64 B]; SLIM: a ring of [4 slabs][BN][64 B]
+  float* biasL = (float*)(smem + L::biasL);           // [BN]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wn = wave & 1, wm = wave >> 1;

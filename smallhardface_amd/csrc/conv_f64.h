@@ -121,8 +121,8 @@ __global__ __launch_bounds__(256) void conv_mfma_f64_kernel(ConvK p) {
   }
 }
 
-static const ConvKernel kF64Kernels[2] = {{(const void*)conv_mfma_f64_kernel<false>, PC_CONV_F64},
-                                          {(const void*)conv_mfma_f64_kernel<true>, PC_CONV_F64}};
+static const ConvKernel kF64Kernels[2] = {{(const void*)conv_mfma_f64_kernel<false>, PC_CONV_F64, 0},   // (static __shared__)
+                                          {(const void*)conv_mfma_f64_kernel<true>, PC_CONV_F64, 0}};
 
 static ConvPlan plan_conv_f64(const ConvArgs* as, int n) {
   ConvPlan pl;
