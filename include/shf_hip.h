@@ -295,6 +295,33 @@ int shf_wider_eval_counts(const double* pred5, const int* pred_off, const double
 int shf_face_eval_match(const double* det4, const long long* det_off, const double* gt4, const long long* gt_off,
                         const uint8_t* difficult, int n_images, double ovr, int* code_out, int* index_out);
 
+/* The pixel counts of the FDDB evaluator (smallhardface_amd/fddb_eval.py), for all images in one call, on the current
+ * device: per (annotation, detection) pair of an image the pixels inside both masks, and per annotation its area.
+ * Masks live on integer pixel coordinates (ix, iy):
+ *   rectangle  rint(x) <= ix <= rint(x + w), rint(y) <= iy <= rint(y + h), both corners inclusive, cut to the canvas
+ *              0 <= ix < W, 0 <= iy < H when the image size is known.  The CALLER rounds and cuts: rect4 holds integers.
+ *   ellipse    with c = cos(angle), s = sin(angle) SUPPLIED BY THE CALLER (computed once on the host; the device calls no
+ *              sin or cos), dx = ix - cx, dy = iy - cy, u = dx*c + dy*s, v = dy*c - dx*s the pixel is inside when
+ *              (u*u)*(rb*rb) + (v*v)*(ra*ra) <= (ra*ra)*(rb*rb): fp64 in exactly that operation order, no contraction.
+ *   ell6       (A,6) ra, rb, c, s, cx, cy; the rows of image i are ann_off[i] .. ann_off[i+1] (n_images + 1 offsets)
+ *   ell_box    (A,4) x0, y0, x1, y1: the inclusive integer scan box of each ellipse -- its bounding box, taken generously,
+ *              cut to the canvas; empty when x1 < x0 or y1 < y0.  Only pixels of the box are tested.
+ *   rect4      (D,4) x0, y0, x1, y1 inclusive, with det_off alike; empty when x1 < x0 or y1 < y0
+ *   inter_out  image i's (A_i, D_i) counts, row-major, at the sum of A_j * D_j over j < i: pixels of
+ *              rect n scan box that pass the ellipse test
+ *   area_out   (A) pixels of the scan box that pass the ellipse test
+ * Integers only: rectangle areas, the scores, the assignment and the curves stay with the caller.  All buffers are host
+ * memory.  Refused with a message, before anything is allocated or launched: null offsets, negative or non-monotone
+ * offsets, 2^31 rows or more of either kind, 2^26 (annotation, detection) pairs or more (one 64-lane block per pair, in one
+ * launch), null arrays with non-zero counts, a corner of 2^30 or more in magnitude, a scan
+ * box of more than 1 048 576 pixels (2^20: one wave sweeps a box 64 pixels at a time, the cap bounds how long it runs;
+ * FDDB's images are under 500 pixels a side, so any real face passes).  Non-finite parameters are the caller's to keep
+ * away.
+ *   phase_ms   NULL, or 3 doubles (measurement): the milliseconds the call's stream spent on the uploads, the kernels and
+ *              the read-back, from events on that stream; zeros when nothing was launched */
+int shf_fddb_pair_counts(const double* ell6, const int* ell_box, const long long* ann_off, const int* rect4,
+                         const long long* det_off, int n_images, int* inter_out, int* area_out, double* phase_ms);
+
 /* Read parameter blob `idx` of layer `layer` from a binary .caffemodel (the reader behind
  * shf_net_create's weight loading; caffe.proto NetParameter.layer=100 / BlobProto data=5).
  * Returns the element count (out may be NULL to query), fills dims/ndim.  Needs no GPU. */
@@ -302,6 +329,11 @@ int shf_caffemodel_read_blob(const char* path, const char* layer, int idx, float
                              int* dims, int* ndim);
 
 /* ---- diagnostics (tests) ------------------------------------------------------ */
+/* the hand-over event a later pass over `net` as a member lane would wait for (set by the fused passes): *waits = 1 when
+ * there is one, *holds = 1 when `net` itself keeps that event alive -- its own event, or a share of the head's whose
+ * grouped pass set it.  A lane that waits for an event it does not hold would wait on a destroyed one once that head is
+ * gone. */
+int shf_debug_handover_event(shf_net* net, int* waits, int* holds);
 /* runs the merge pipeline on host dets and returns its intermediates: the IoU bit matrix
  * (n x ceil(n/64) words, upper triangle), cluster head per box, kept heads, sorted dets, perm */
 int shf_debug_merge(const float* dets5, int n, float thresh, int ge_pred, unsigned long long* mask_out,

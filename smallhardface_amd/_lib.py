@@ -111,6 +111,7 @@ def _declare(lib):
         "shf_detect_export": (ci, [vp, vp, ci, ip]),
         "shf_detect_import": (ci, [vp, vp, ci]),
         "shf_detect_export_many": (ci, [vp, ci, C.POINTER(vp), C.POINTER(vp), ci, ip]),
+        "shf_debug_handover_event": (ci, [vp, ip, ip]),
         "shf_debug_merge": (ci, [vp, ci, cf, ci, vp, vp, vp, ip, vp, vp]),
         "shf_debug_proposal": (ci, [vp, fp, fp, ci, ci, fp, fp, fp, ci, ip, ip]),
         "shf_debug_append": (ci, [vp, fp, fp, ci, ci, cf, ci, cf]),
@@ -121,6 +122,7 @@ def _declare(lib):
                                        C.POINTER(C.c_longlong), ip, C.POINTER(C.c_uint8)]),
         "shf_face_eval_match": (ci, [dp, C.POINTER(C.c_longlong), dp, C.POINTER(C.c_longlong), C.POINTER(C.c_uint8), ci,
                                      C.c_double, ip, ip]),
+        "shf_fddb_pair_counts": (ci, [dp, ip, C.POINTER(C.c_longlong), ip, C.POINTER(C.c_longlong), ci, ip, ip, dp]),
         "shf_generate_anchors": (ci, [ci, dp, ci, dp, ci, dp, ci, dp, dp, ci]),
         "shf_prof_enable": (ci, [vp, ci]),
         "shf_prof_only": (ci, [vp, ci]),

@@ -464,6 +464,13 @@ class Net(object):
             raise ValueError("forward_group: %d members but %d input dicts" % (len(members), len(inputs)))
         return self._run_forward(members, inputs, lambda m: m.outputs, True)
 
+    def handover_event(self):
+        """(waits, holds) of C ABI shf_debug_handover_event: whether a later grouped pass over this net as a member lane
+        waits for an event, and whether this net keeps that event alive (tests)."""
+        w, h = C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.shf_debug_handover_event(self._h, C.byref(w), C.byref(h)), "debug_handover_event")
+        return bool(w.value), bool(h.value)
+
     # -- measurement helpers ------------------------------------------------------
     def sync(self):
         _lib.check(self._lib.shf_net_sync(self._h), "sync")

@@ -1,5 +1,5 @@
-// Launchers of the evaluation kernels (eval.hip): WIDER, called by shf_wider_eval_counts, and AFW / Pascal Faces, called by
-// shf_face_eval_match (net_api.cpp).
+// Launchers of the evaluation kernels (eval.hip): WIDER, called by shf_wider_eval_counts, AFW / Pascal Faces, called by
+// shf_face_eval_match, and FDDB, called by shf_fddb_pair_counts (net_api.cpp).
 #pragma once
 #include "shf_internal.h"
 
@@ -29,5 +29,19 @@ constexpr int kFaceNeither = 0, kFaceTruePositive = 1, kFaceFalsePositive = 2;
 // taken (G) must be zero on entry
 int launch_face_match(const double* det4, const int* det_off, const double* gt4, const int* gt_off, const uint8_t* difficult,
                       int n_images, double ovr, uint8_t* taken, int* code, int* index, hipStream_t s);
+
+// One wave sweeps an ellipse's scan box (or its part inside a rectangle) 64 pixels at a time: the cap bounds how long it can
+// run.  2^20 pixels = 16 384 steps; FDDB's images are under 500 pixels a side, so any real face passes.
+constexpr long long kFddbMaxScanBox = 1ll << 20;
+// one 64-lane block per pair: a launch holds at most 2^32 - 1 threads, so 2^26 pairs or more cannot be one launch
+constexpr long long kFddbMaxPairs = 1ll << 26;
+// every integer corner stays below this in magnitude, so extents and pixel indices fit an int
+constexpr int kFddbMaxCoord = 1 << 30;
+// one wave per (annotation, detection) pair: pair p belongs to the annotation a with pair_off[a] <= p < pair_off[a + 1]
+// (A + 1 offsets) and to detection det0[a] + p - pair_off[a]; inter[p] = pixels of rect n scan box inside the ellipse
+int launch_fddb_pairs(const double* ell6, const int* ell_box, const int* rect4, const int* pair_off, const int* det0, int A,
+                      int n_pairs, int* inter, hipStream_t s);
+// one wave per annotation: area[a] = pixels of the scan box inside the ellipse
+int launch_fddb_areas(const double* ell6, const int* ell_box, int A, int* area, hipStream_t s);
 
 }  // namespace shf

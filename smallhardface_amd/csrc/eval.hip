@@ -15,7 +15,10 @@
 //
 // AFW / Pascal Faces evaluation: one matching round of
 //   VOCprRecordOptim    external/marcopede-face-eval-f2870fd85d48/VOCpr.py:118-162   (IoU: util.py:176-193)
-// face_match_kernel, at the end of this file (smallhardface_amd/face_eval.py: match_host is its numpy restatement).
+// face_match_kernel, below (smallhardface_amd/face_eval.py: match_host is its numpy restatement).
+//
+// FDDB evaluation: the pixel counts of ellipse and rectangle masks, fddb_pairs_kernel / fddb_areas_kernel at the end of this
+// file (smallhardface_amd/fddb_eval.py: pair_counts_host is their numpy restatement).
 #include "eval.h"
 
 namespace shf {
@@ -245,6 +248,81 @@ int launch_face_match(const double* det4, const int* det_off, const double* gt4,
   if (n_images == 0) return 0;
   hipLaunchKernelGGL(face_match_kernel, dim3((unsigned)n_images), dim3(64), 0, s, det4, det_off, gt4, gt_off, difficult, ovr,
                      taken, code, index);
+  SHF_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// ---- FDDB: pixel counts of ellipse and rectangle masks (smallhardface_amd/fddb_eval.py: pair_counts_host) -----------------------
+// A pixel (ix, iy) is inside the ellipse row ra, rb, c, s, cx, cy when, with dx = ix - cx, dy = iy - cy, u = dx*c + dy*s,
+// v = dy*c - dx*s,   (u*u)*(rb*rb) + (v*v)*(ra*ra) <= (ra*ra)*(rb*rb)   -- fp64 adds, multiplies and one compare in that order
+// (c = cos(angle), s = sin(angle) come from the host).  The 64 lanes sweep the inclusive box x0..x1 x y0..y1 row-major, 64
+// pixels a step; every lane tests its pixel, the wave adds popcount(ballot) to a wave-uniform counter.  The box is at most
+// kFddbMaxScanBox pixels and every corner below kFddbMaxCoord in magnitude (checked by the caller), so w * h fits an int.
+// No atomics, no LDS, no floating-point output: one wave owns one count.
+__device__ __forceinline__ int fddb_sweep(const double* __restrict__ e, int x0, int y0, int x1, int y1, int lane) {
+  const int w = x1 - x0 + 1, h = y1 - y0 + 1;
+  if (w <= 0 || h <= 0) return 0;   // (wave-uniform: an empty pair costs its wave these few instructions)
+  const int n = w * h;
+  const double ra = e[0], rb = e[1], c = e[2], s = e[3], cx = e[4], cy = e[5];
+  const double ra2 = ra * ra, rb2 = rb * rb, rhs = ra2 * rb2;
+  // lane's pixel of the step, kept without a division per step: 64 pixels on are step_y rows down and step_x columns right
+  const int step_y = 64 / w, step_x = 64 % w;
+  int x = lane % w, y = lane / w, total = 0;
+  for (int base = 0; base < n; base += 64) {
+    bool in = false;
+    if (base + lane < n) {
+      const double dx = (double)(x0 + x) - cx, dy = (double)(y0 + y) - cy;
+      const double u = dx * c + dy * s, v = dy * c - dx * s;
+      in = (u * u) * rb2 + (v * v) * ra2 <= rhs;
+    }
+    total += __popcll(__ballot(in));
+    x += step_x;
+    y += step_y;
+    if (x >= w) { x -= w; ++y; }
+  }
+  return total;
+}
+
+__global__ __launch_bounds__(64) void fddb_pairs_kernel(const double* __restrict__ ell6, const int* __restrict__ ell_box,
+                                                        const int* __restrict__ rect4, const int* __restrict__ pair_off,
+                                                        const int* __restrict__ det0, int A, int* __restrict__ inter) {
+  const int p = blockIdx.x, lane = threadIdx.x;
+  // the annotation owning pair p: the last a with pair_off[a] <= p (pair_off[0] = 0 <= p < pair_off[A]; an annotation
+  // without detections has an empty range and is never the last)
+  int lo = 0, hi = A;
+  while (hi - lo > 1) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (pair_off[mid] <= p) lo = mid; else hi = mid;
+  }
+  const int a = lo, d = det0[a] + (p - pair_off[a]);
+  const int* b = ell_box + (size_t)a * 4;
+  const int* r = rect4 + (size_t)d * 4;
+  const int x0 = b[0] > r[0] ? b[0] : r[0], y0 = b[1] > r[1] ? b[1] : r[1];
+  const int x1 = b[2] < r[2] ? b[2] : r[2], y1 = b[3] < r[3] ? b[3] : r[3];
+  const int total = fddb_sweep(ell6 + (size_t)a * 6, x0, y0, x1, y1, lane);
+  if (lane == 0) inter[p] = total;
+}
+
+__global__ __launch_bounds__(64) void fddb_areas_kernel(const double* __restrict__ ell6, const int* __restrict__ ell_box,
+                                                        int* __restrict__ area) {
+  const int a = blockIdx.x, lane = threadIdx.x;
+  const int* b = ell_box + (size_t)a * 4;
+  const int total = fddb_sweep(ell6 + (size_t)a * 6, b[0], b[1], b[2], b[3], lane);
+  if (lane == 0) area[a] = total;
+}
+
+int launch_fddb_pairs(const double* ell6, const int* ell_box, const int* rect4, const int* pair_off, const int* det0, int A,
+                      int n_pairs, int* inter, hipStream_t s) {
+  if (n_pairs == 0) return 0;
+  hipLaunchKernelGGL(fddb_pairs_kernel, dim3((unsigned)n_pairs), dim3(64), 0, s, ell6, ell_box, rect4, pair_off, det0, A,
+                     inter);
+  SHF_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int launch_fddb_areas(const double* ell6, const int* ell_box, int A, int* area, hipStream_t s) {
+  if (A == 0) return 0;
+  hipLaunchKernelGGL(fddb_areas_kernel, dim3((unsigned)A), dim3(64), 0, s, ell6, ell_box, area);
   SHF_HIP_OK(hipGetLastError());
   return 0;
 }

@@ -27,7 +27,8 @@ static MergeCtx* g_box_ctx = nullptr;
 static hipStream_t g_box_stream = nullptr;
 static DevBuf* g_box_in = nullptr;
 
-// device memory and stream of ONE shf_wider_eval_counts / shf_face_eval_match call, on the device current at the call:
+// device memory, stream and events of ONE shf_wider_eval_counts / shf_face_eval_match / shf_fddb_pair_counts call, on the
+// device current at the call:
 // nothing outlives it
 namespace {
 struct CallBuf {
@@ -38,6 +39,11 @@ struct CallBuf {
   CallBuf() = default;
   CallBuf(const CallBuf&) = delete;
   CallBuf& operator=(const CallBuf&) = delete;
+};
+struct CallEvents {
+  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  void create() { for (auto& x : e) HIP_THROW(hipEventCreate(&x)); }
+  ~CallEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
 };
 struct CallStream {
   hipStream_t s = nullptr;
@@ -626,6 +632,91 @@ int shf_face_eval_match(const double* det4, const long long* det_off, const doub
   API_END(-1)
 }
 
+int shf_fddb_pair_counts(const double* ell6, const int* ell_box, const long long* ann_off, const int* rect4,
+                         const long long* det_off, int n_images, int* inter_out, int* area_out, double* phase_ms) {
+  API_BEGIN
+  // ---- refusals: argument checks only, before anything is allocated or launched
+  if (!ann_off || !det_off || n_images < 0) throw std::runtime_error("fddb_pair_counts: null offsets or negative n_images");
+  for (const auto& [off, name] : {std::pair<const long long*, const char*>{ann_off, "ann_off"}, {det_off, "det_off"}})
+    for (int i = 0; i <= n_images; ++i) {
+      if (off[i] < 0) throw std::runtime_error(std::string("fddb_pair_counts: negative offset in ") + name);
+      if (i && off[i] < off[i - 1]) throw std::runtime_error(std::string("fddb_pair_counts: non-monotone offsets in ") + name);
+    }
+  const long long A = ann_off[n_images] - ann_off[0], D = det_off[n_images] - det_off[0];
+  if (ann_off[0] != 0 || det_off[0] != 0) throw std::runtime_error("fddb_pair_counts: offsets must start at 0");
+  if (A >= (1ll << 31) || D >= (1ll << 31))
+    throw std::runtime_error("fddb_pair_counts: 2^31 rows or more (annotations " + std::to_string(A) + ", detections " +
+                             std::to_string(D) + ")");
+  long long P = 0;
+  for (int i = 0; i < n_images; ++i) {
+    P += (ann_off[i + 1] - ann_off[i]) * (det_off[i + 1] - det_off[i]);   // (each factor is below 2^31, P below 2^26 so far)
+    if (P >= kFddbMaxPairs)
+      throw std::runtime_error("fddb_pair_counts: 2^26 (annotation, detection) pairs or more (one wave per pair in one launch)");
+  }
+  if ((A && (!ell6 || !ell_box || !area_out)) || (D && !rect4) || (P && !inter_out))
+    throw std::runtime_error("fddb_pair_counts: null shape or output array");
+  for (const auto& [box, rows, name] : {std::tuple<const int*, long long, const char*>{ell_box, A, "scan box"},
+                                        {rect4, D, "rectangle"}})
+    for (long long k = 0; k < rows * 4; ++k)
+      if (box[k] >= kFddbMaxCoord || box[k] <= -kFddbMaxCoord)
+        throw std::runtime_error(std::string("fddb_pair_counts: a ") + name + " corner of 2^30 or more in magnitude (row " +
+                                 std::to_string(k / 4) + ")");
+  for (long long a = 0; a < A; ++a) {
+    const long long w = (long long)ell_box[a * 4 + 2] - ell_box[a * 4 + 0] + 1, h = (long long)ell_box[a * 4 + 3] - ell_box[a * 4 + 1] + 1;
+    if (w > 0 && h > 0 && w * h > kFddbMaxScanBox)
+      throw std::runtime_error("fddb_pair_counts: annotation " + std::to_string(a) + " has a scan box of " + std::to_string(w) +
+                               " x " + std::to_string(h) + " pixels, the cap is " + std::to_string(kFddbMaxScanBox));
+  }
+  if (phase_ms) phase_ms[0] = phase_ms[1] = phase_ms[2] = 0.0;
+  if (A == 0) return 0;   // (no annotations: no pairs either)
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    throw std::runtime_error("no HIP device available: fddb_pair_counts has no CPU fallback");
+
+  // per annotation: where its pairs start (A + 1 offsets) and its image's first detection
+  std::vector<int> pair_off((size_t)A + 1), det0((size_t)A);
+  long long p = 0;
+  for (int i = 0; i < n_images; ++i)
+    for (long long a = ann_off[i]; a < ann_off[i + 1]; ++a) {
+      pair_off[(size_t)a] = (int)p;
+      det0[(size_t)a] = (int)det_off[i];
+      p += det_off[i + 1] - det_off[i];
+    }
+  pair_off[(size_t)A] = (int)p;
+  CallStream st;
+  st.create();
+  CallBuf d_ell, d_box, d_rect, d_poff, d_det0, d_inter, d_area;
+  CallEvents ev;   // (only with phase_ms: start, uploads done, kernels done, read-back done)
+  if (phase_ms) ev.create();
+  auto mark = [&](int k) { if (phase_ms) HIP_THROW(hipEventRecord(ev.e[k], st.s)); };
+  d_ell.alloc((size_t)A * 6 * 8); d_box.alloc((size_t)A * 4 * sizeof(int)); d_rect.alloc((size_t)D * 4 * sizeof(int));
+  d_poff.alloc(((size_t)A + 1) * sizeof(int)); d_det0.alloc((size_t)A * sizeof(int));
+  d_inter.alloc((size_t)P * sizeof(int)); d_area.alloc((size_t)A * sizeof(int));
+  mark(0);
+  HIP_THROW(hipMemcpyAsync(d_ell.p, ell6, (size_t)A * 6 * 8, hipMemcpyHostToDevice, st.s));
+  HIP_THROW(hipMemcpyAsync(d_box.p, ell_box, (size_t)A * 4 * sizeof(int), hipMemcpyHostToDevice, st.s));
+  if (D) HIP_THROW(hipMemcpyAsync(d_rect.p, rect4, (size_t)D * 4 * sizeof(int), hipMemcpyHostToDevice, st.s));
+  HIP_THROW(hipMemcpyAsync(d_poff.p, pair_off.data(), ((size_t)A + 1) * sizeof(int), hipMemcpyHostToDevice, st.s));
+  HIP_THROW(hipMemcpyAsync(d_det0.p, det0.data(), (size_t)A * sizeof(int), hipMemcpyHostToDevice, st.s));
+  mark(1);
+  CHECK_RC(launch_fddb_pairs(d_ell.as<double>(), d_box.as<int>(), d_rect.as<int>(), d_poff.as<int>(), d_det0.as<int>(), (int)A,
+                             (int)P, d_inter.as<int>(), st.s));
+  CHECK_RC(launch_fddb_areas(d_ell.as<double>(), d_box.as<int>(), (int)A, d_area.as<int>(), st.s));
+  mark(2);
+  if (P) HIP_THROW(hipMemcpyAsync(inter_out, d_inter.p, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, st.s));
+  HIP_THROW(hipMemcpyAsync(area_out, d_area.p, (size_t)A * sizeof(int), hipMemcpyDeviceToHost, st.s));
+  mark(3);
+  HIP_THROW(hipStreamSynchronize(st.s));
+  if (phase_ms)
+    for (int k = 0; k < 3; ++k) {
+      float ms = 0;
+      HIP_THROW(hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
+      phase_ms[k] = ms;
+    }
+  return 0;
+  API_END(-1)
+}
+
 int shf_caffemodel_read_blob(const char* path, const char* layer, int idx, float* out, int cap, int* dims,
                              int* ndim) {
   API_BEGIN
@@ -640,6 +731,16 @@ int shf_caffemodel_read_blob(const char* path, const char* layer, int idx, float
     return (int)b.data.size();
   }
   throw std::runtime_error(std::string("caffemodel: no layer named '") + layer + "'");
+  API_END(-1)
+}
+
+int shf_debug_handover_event(shf_net* net, int* waits, int* holds) {
+  API_BEGIN
+  if (!net || !waits || !holds) throw std::runtime_error("debug_handover_event: null argument");
+  *waits = net->logits_done != nullptr;
+  *holds = net->logits_done && (net->logits_done == net->ev_logits ||
+                                (net->logits_keep && net->logits_keep->e == net->logits_done));
+  return 0;
   API_END(-1)
 }
 

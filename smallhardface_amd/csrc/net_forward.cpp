@@ -278,7 +278,7 @@ void run_pass(const Pass& p) {
             ProfScope ps(h.prof, p.s, PC_TAIL, c.first, c.second);
             if (p.fused && !ln.ev_logits) HIP_THROW(hipEventCreateWithFlags(&ln.ev_logits, hipEventDisableTiming));
             CHECK_RC(launch_tail(t[m], ln.tw, boxes[m], probs[m], p.s, p.fused ? ln.ev_logits : nullptr, 0));
-            if (p.fused) ln.logits_done = ln.ev_logits;
+            if (p.fused) { ln.logits_done = ln.ev_logits; ln.logits_keep.reset(); }
           }
           break;
         }
@@ -293,7 +293,11 @@ void run_pass(const Pass& p) {
         // gather): ~15 launches per image instead of ~100.  Phase 1 (reset + logits) is what reads the feature maps and
         // runs on the layers' stream; phase 2 works on the lanes' tail workspaces only and runs on the head's stream.
         for (int m = 1; m < p.n; ++m) t[m].wcls[0] = t[0].wcls[0], t[m].bcls[0] = t[0].bcls[0];  // lanes hold identical copies
-        if (!h.ev_convs) HIP_THROW(hipEventCreateWithFlags(&h.ev_convs, hipEventDisableTiming));
+        if (!h.ev_convs) {
+          h.ev_convs_own = std::make_shared<SharedEvent>();
+          HIP_THROW(hipEventCreateWithFlags(&h.ev_convs_own->e, hipEventDisableTiming));
+          h.ev_convs = h.ev_convs_own->e;
+        }
         // the lanes' tail workspaces were last used by the predecessor head's tails (its own stream)
         if (h.pred && h.pred->ev_mark) HIP_THROW(hipStreamWaitEvent(p.s, h.pred->ev_mark, 0));
         {
@@ -315,6 +319,7 @@ void run_pass(const Pass& p) {
             HIP_THROW(hipEventRecord(ln.ev_logits, h.stream));
           }
           ln.logits_done = shared ? h.ev_convs : ln.ev_logits;
+          ln.logits_keep = shared ? h.ev_convs_own : nullptr;
         }
         {
           ProfScope ps(h.prof, h.stream, PC_TAIL, 0, 0);

@@ -364,6 +364,13 @@ enum TailStep {
   TAIL_GROUP      // both phases of the group as one launch per stage on the pass's stream, no events (shf_net_forward_group)
 };
 
+// a HIP event that lives as long as anyone holds it: a head's ev_convs is also what the lanes of its pass wait for later
+// (shf_net::logits_done), and a head may go before the lanes that lent it their buffers
+struct SharedEvent {
+  hipEvent_t e = nullptr;
+  ~SharedEvent() { if (e) (void)hipEventDestroy(e); }
+};
+
 struct shf_net {
   std::shared_ptr<NetShared> sh;
   int& conv_mode;
@@ -399,10 +406,12 @@ struct shf_net {
   int tail_gen = -1;
   hipEvent_t ev_mark = nullptr;
   hipEvent_t ev_logits = nullptr;  // recorded by every fused tail pass right after its logits kernel
-  hipEvent_t logits_done = nullptr;  // (not owned) what a later pass over this member waits for: its own ev_logits, or --
+  hipEvent_t logits_done = nullptr;  // what a later pass over this member waits for: its own ev_logits, or --
                                      // after a pipelined grouped pass -- the head's ev_convs (ONE record for the group:
                                      // ten event records in a row were ~90 us of idle conv stream per image)
+  std::shared_ptr<SharedEvent> logits_keep;   // holds the head's ev_convs while logits_done is that event, else empty
   hipEvent_t ev_convs = nullptr;   // group pass: recorded on the head's stream after the last layer before the tails
+  std::shared_ptr<SharedEvent> ev_convs_own;  // ... and its owner, shared with the lanes that wait for it
   hipEvent_t ev_group = nullptr;   // head of shf_blob_load_device_group: recorded behind the copy, awaited by the members' streams
   shf_net* pred = nullptr;         // shf_net_set_predecessor: the head lane whose image precedes this one's
   bool pipelined = false;   // shf_net_set_pipeline: convolutions go to sh->conv_stream, the rest stays on `stream`
@@ -450,7 +459,6 @@ struct shf_net {
 
   ~shf_net() {
     if (ev_logits) (void)hipEventDestroy(ev_logits);
-    if (ev_convs) (void)hipEventDestroy(ev_convs);
     if (ev_group) (void)hipEventDestroy(ev_group);
     if (ev_mark) (void)hipEventDestroy(ev_mark);
     if (stream) {

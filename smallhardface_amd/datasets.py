@@ -9,8 +9,9 @@
   writer_for(db)           imdb name (cfg.TEST.DB) -> writer, like lib/datasets/factory.py picks the class
 
 All four are pinned by tests/golden/writers.json (files written by the reference's own classes).  The WIDER
-evaluator is smallhardface_amd/wider_eval.py, the AFW / Pascal Faces one smallhardface_amd/face_eval.py; ImageList runs
-them when a ground_truth directory holding the dataset's annotation files is given.
+evaluator is smallhardface_amd/wider_eval.py, the AFW / Pascal Faces one smallhardface_amd/face_eval.py, the FDDB one
+smallhardface_amd/fddb_eval.py; ImageList runs them when a ground_truth directory holding the dataset's annotation files
+is given.
 """
 import os
 
@@ -84,7 +85,7 @@ class ImageList(object):
                 writer = write_detections_wider
         self._writer = writer
         # WIDER: directory with wider_{face,easy,medium,hard}_val.mat; AFW: with new_annotations_AFW.mat; Pascal Faces: with
-        # Annotations_Face_PASCALLayout_large_fixed.mat
+        # Annotations_Face_PASCALLayout_large_fixed.mat; FDDB: with val_gt.txt or FDDB-folds/val_gt.txt
         self._ground_truth = ground_truth
 
     def __len__(self):
@@ -120,4 +121,19 @@ class ImageList(object):
                     ap = face_eval(os.path.join(out, fname), ann, dataset,
                                    device=os.environ.get("SHF_DEVICE_EVAL") == "1")[0]
                     return 'AP: {:.4f}'.format(ap)
+        if self._writer is write_detections_fddb and self._ground_truth:
+            # lib/datasets/fddb.py:75-105, with the in-tree evaluator in the place of FDDB's external binary
+            from . import fddb_eval
+            ann = [p for p in (os.path.join(self._ground_truth, fddb_eval.ANNOTATION_FILE),
+                               os.path.join(self._ground_truth, 'FDDB-folds', fddb_eval.ANNOTATION_FILE))
+                   if os.path.exists(p)]
+            if ann:
+                gt = fddb_eval.load_annotations(ann[0])
+                dets = fddb_eval.load_detections(os.path.join(out, 'detection_rect.txt'))
+                # image sizes from the headers of the files the list names, where they exist
+                path_of = {os.path.splitext(p)[0]: self.image_path_at(i) for i, p in enumerate(self._image_paths)}
+                sizes = fddb_eval.sizes_of([path_of.get(n) for n in gt.names])
+                res = fddb_eval.evaluate(dets, gt, sizes=sizes, device=os.environ.get("SHF_DEVICE_EVAL") == "1")
+                fddb_eval.write_roc(res, out, prefix='rect_')
+                return fddb_eval.result_string(res)
         return 'detections written to {}'.format(out)
