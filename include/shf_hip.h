@@ -51,6 +51,9 @@ int shf_net_num_outputs(shf_net* net);
 int shf_net_output_blob(shf_net* net, int i);
 /* Net._layer_names / Layer.type / Layer.blobs           _caffe.cpp:434,483-487 */
 int shf_net_num_layers(shf_net* net);
+/* classes of the net's proposal layer, background first (proposal_layer.py:118: scores.shape[1] / A): 2 .. 8, taken from
+ * the class predictors' output counts; 0 for a net without a proposal layer */
+int shf_net_num_classes(shf_net* net);
 const char* shf_net_layer_name(shf_net* net, int i);
 const char* shf_net_layer_type(shf_net* net, int i);
 int shf_net_layer_num_params(shf_net* net, int layer);
@@ -342,15 +345,18 @@ int shf_debug_merge(const float* dets5, int n, float thresh, int ge_pred, unsign
 /* The proposal stage alone -- tail decode -> candidate select -> sort -> gather -- on INJECTED blobs, so the
  * reference's own ProposalLayer.forward vectors (lib/layers/proposal_layer.py:60-220, incl. the
  * np.seterr(over='raise') clamp branch of lib/utils/bbox_transform.py:52-65) reach the HIP kernels: scores =
- * cls_prob_reshape_output (1,2A,h,w), deltas = bbox_pred_output (1,4A,h,w), im_info3 = (h, w, scale), all host
- * fp32.  Anchors and cfg.TEST.* come from `net` (any net holding the proposal layer).  out_boxes5 (cap,5) /
- * out_probs2 (cap,2) receive the layer's tops: *n_out = R rows (when R == 0 out_boxes5 holds the dummy roi);
- * *overflow != 0 when the clamp branch was taken. */
+ * cls_prob_reshape_output (1,C*A,h,w) with channel c*A + a, deltas = bbox_pred_output (1,4A,h,w), im_info3 =
+ * (h, w, scale), all host fp32.  Anchors, the class count C (shf_net_num_classes) and cfg.TEST.* come from `net` (any
+ * net holding the proposal layer).  out_boxes5 (cap,5) / out_probs2 (cap,C) receive the layer's tops: *n_out = R rows,
+ * ranked by the best foreground class (when R == 0 out_boxes5 holds the dummy roi); *overflow != 0 when the clamp branch
+ * was taken. */
 int shf_debug_proposal(shf_net* net, const float* scores, const float* deltas, int h, int w, const float* im_info3,
                        float* out_boxes5, float* out_probs2, int cap, int* n_out, int* overflow);
 /* forward_net's flip fix + unscale (lib/test.py:52-54,59-66) and detect()'s > thresh cut (:163-167) on injected
  * proposals boxes5 (R,5) / probs2 (R,2) (host, score-descending like the layer emits them): appended to the
- * current image's device list as one more unit (after shf_detect_begin; read back with shf_detect_export). */
+ * current image's device list as one more unit (after shf_detect_begin; read back with shf_detect_export).
+ * The per-image lists (this call, shf_detect_begin, shf_detect_add_level(s)) hold one foreground class: a net with
+ * more than two classes is refused, with the class count in the message, before anything is launched. */
 int shf_debug_append(shf_net* net, const float* boxes5, const float* probs2, int R, int im_w, float im_scale,
                      int flip, float thresh);
 

@@ -273,6 +273,11 @@ class Net(object):
         self._dev_sources = []    # device sources of Blob.load_device, kept alive until the next forward has returned
         self._apply_cfg()
 
+    @property
+    def num_classes(self):
+        """Classes of the proposal layer, background first (C ABI shf_net_num_classes); 0 without a proposal layer."""
+        return int(self._lib.shf_net_num_classes(self._h))
+
     def clone(self):
         """A lane: same parameter tensors, own activations / workspace / HIP stream
         (cf. Net::ShareTrainedLayersWith).  Keep ``self`` alive while the lane is used."""
@@ -586,16 +591,18 @@ class Net(object):
     # -- diagnostics (tests) -----------------------------------------------------------
     def debug_proposal(self, scores, deltas, im_info):
         """ProposalLayer.forward on injected blobs through the HIP tail (C ABI shf_debug_proposal):
-        scores (1,2A,h,w), deltas (1,4A,h,w), im_info (1,3) -> (boxes (max(R,1),5), probs (R,2), overflow flag)."""
+        scores (1,C*A,h,w), deltas (1,4A,h,w), im_info (1,3) -> (boxes (max(R,1),5), probs (R,C), overflow flag),
+        C = ``self.num_classes``."""
         sc = np.ascontiguousarray(scores, dtype=np.float32)
         dl = np.ascontiguousarray(deltas, dtype=np.float32)
         ii = np.ascontiguousarray(im_info, dtype=np.float32).reshape(-1)
         h, w = sc.shape[2:]
-        A = sc.shape[1] // 2
-        assert dl.shape == (1, 4 * A, h, w), dl.shape
+        nc = self.num_classes
+        A = sc.shape[1] // nc
+        assert sc.shape[1] == nc * A and dl.shape == (1, 4 * A, h, w), (sc.shape, dl.shape, nc)
         cap = h * w * A
         boxes = np.zeros((cap, 5), np.float32)
-        probs = np.zeros((cap, 2), np.float32)
+        probs = np.zeros((cap, nc), np.float32)
         n, of = C.c_int(0), C.c_int(0)
         F = C.POINTER(C.c_float)
         _lib.check(self._lib.shf_debug_proposal(self._h, sc.ctypes.data_as(F), dl.ctypes.data_as(F), h, w,

@@ -154,6 +154,7 @@ int shf_net_input_blob(shf_net* net, int i) { return net->inputs[i]; }
 int shf_net_num_outputs(shf_net* net) { return (int)net->outputs.size(); }
 int shf_net_output_blob(shf_net* net, int i) { return net->outputs[i]; }
 int shf_net_num_layers(shf_net* net) { return (int)net->layers.size(); }
+int shf_net_num_classes(shf_net* net) { return net->tail_layer >= 0 ? net->tail_C : 0; }
 const char* shf_net_layer_name(shf_net* net, int i) { return net->layers[i].name.c_str(); }
 const char* shf_net_layer_type(shf_net* net, int i) { return net->layers[i].type.c_str(); }
 int shf_net_layer_num_params(shf_net* net, int layer) { return (int)net->layers[layer].params.size(); }
@@ -773,22 +774,22 @@ int shf_debug_merge(const float* dets5, int n, float thresh, int ge_pred, unsign
 
 // diagnostics: the proposal stage alone on injected blobs (tests only)
 int shf_debug_proposal(shf_net* net, const float* scores, const float* deltas, int h, int w, const float* im_info3,
-                       float* out_boxes5, float* out_probs2, int cap, int* n_out, int* overflow) {
+                       float* out_boxes5, float* out_probs, int cap, int* n_out, int* overflow) {
   API_BEGIN
   if (net->tail_layer < 0) throw std::runtime_error("net has no proposal layer");
   if (h < 1 || w < 1) throw std::runtime_error("debug_proposal: bad map size");
   // (any (h, w): the layer itself does not care that the real graph only produces even head maps)
-  const int A = net->tail_A;
+  const int A = net->tail_A, NC = net->tail_C;
   const size_t K = (size_t)h * w;
   net->ensure_tail_workspace(K * A);
   DevBuf ds, dd;
-  ds.ensure(K * 2 * A * 4);
+  ds.ensure(K * NC * A * 4);
   dd.ensure(K * 4 * A * 4);
   hipStream_t st = net->stream;
-  HIP_THROW(hipMemcpyAsync(ds.p, scores, K * 2 * A * 4, hipMemcpyHostToDevice, st));
+  HIP_THROW(hipMemcpyAsync(ds.p, scores, K * NC * A * 4, hipMemcpyHostToDevice, st));
   HIP_THROW(hipMemcpyAsync(dd.p, deltas, K * 4 * A * 4, hipMemcpyHostToDevice, st));
   TailArgs t;
-  t.A = A; t.heads = net->tail_heads; t.Cf = net->tail_Cf;
+  t.A = A; t.C = NC; t.heads = net->tail_heads; t.Cf = net->tail_Cf;
   t.h = h; t.w = w;
   for (int i = 0; i < A * 4; ++i) t.anchors[i] = (float)net->anchors[i];
   for (int i = 0; i < A; ++i) t.sub_stride[i] = net->sub_stride[i];
@@ -805,13 +806,13 @@ int shf_debug_proposal(shf_net* net, const float* scores, const float* deltas, i
   HIP_THROW(hipStreamSynchronize(st));
   const int R = cnt[2];
   if (overflow) *overflow = cnt[1];
-  // ProposalLayer's tops: (max(R,1), 5) with the dummy roi when R == 0, and (R, 2)   proposal_layer.py:207-220
+  // ProposalLayer's tops: (max(R,1), 5) with the dummy roi when R == 0, and (R, C)   proposal_layer.py:207-220
   const int rows_b = std::max(R, 1);
   if (n_out) *n_out = R;
   HIP_THROW(hipMemcpy(out_boxes5, boxes, (size_t)std::min(rows_b, cap) * 5 * 4, hipMemcpyDeviceToHost));
-  if (R > 0) HIP_THROW(hipMemcpy(out_probs2, probs, (size_t)std::min(R, cap) * 2 * 4, hipMemcpyDeviceToHost));
+  if (R > 0) HIP_THROW(hipMemcpy(out_probs, probs, (size_t)std::min(R, cap) * NC * 4, hipMemcpyDeviceToHost));
   net->blobs[net->boxes_blob].shape = {rows_b, 5};
-  if (net->prob_blob >= 0) net->blobs[net->prob_blob].shape = {R, 2};
+  if (net->prob_blob >= 0) net->blobs[net->prob_blob].shape = {R, NC};
   return 0;
   API_END(-1)
 }
@@ -822,6 +823,7 @@ int shf_debug_append(shf_net* net, const float* boxes5, const float* probs2, int
                      int flip, float thresh) {
   API_BEGIN
   if (net->tail_layer < 0) throw std::runtime_error("net has no proposal layer");
+  refuse_multiclass_lists("debug_append", net);
   if (R < 0) throw std::runtime_error("debug_append: R < 0");
   net->tw_counters.ensure(64);
   net->tw.counters = (int*)net->tw_counters.p;

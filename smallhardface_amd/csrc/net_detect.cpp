@@ -16,9 +16,24 @@ static void throw_if_out_of_range(shf_net* net) {
   if (flag) throw std::runtime_error(kRangeMsg);
 }
 
+}  // extern "C"
+
+// the per-image device lists hold one foreground class (rows of x1, y1, x2, y2, score, cut on the (R, 2) score rows): a net
+// with more classes is refused before anything is staged or launched -- its units go through Net.forward and the caller's
+// class loop
+void refuse_multiclass_lists(const char* who, const shf_net* net) {
+  if (net->tail_layer >= 0 && net->tail_C > 2)
+    throw std::runtime_error(std::string(who) + ": the net has " + std::to_string(net->tail_C) +
+                             " classes; the fused per-image path keeps one detection list per image and supports 2 "
+                             "(use Net.forward / forward_group and merge per class)");
+}
+
+extern "C" {
+
 int shf_detect_begin(shf_net* net) {
   API_BEGIN
   if (net->tail_layer < 0) throw std::runtime_error("net has no proposal layer");
+  refuse_multiclass_lists("detect_begin", net);
   if (!net->pipelined) HIP_THROW(hipMemsetAsync(net->range_flag.p, 0, 4, net->stream));
   net->img_count.ensure(64);
   HIP_THROW(hipMemsetAsync(net->img_count.p, 0, 64, net->stream));
@@ -138,6 +153,7 @@ int shf_make_pyramid_level(shf_net* net, const uint8_t* im_bgr_dev, int im_h, in
 int shf_detect_add_level(shf_net* net, const float* data, int data_on_device, int H, int W, int im_h, int im_w,
                          float im_scale, int flip, float thresh) {
   API_BEGIN
+  refuse_multiclass_lists("detect_add_level", net);
   net->prepare_unit(data, data_on_device, H, W, net->stream);
   const float im_info[3] = {(float)im_h, (float)im_w, im_scale};
   net->run_unit(true, im_info, TAIL_LANE);
@@ -151,6 +167,7 @@ int shf_detect_add_levels(shf_net* net, int n, shf_net** members, const float* c
                           const int* H, const int* W, const int* im_h, const int* im_w, const float* im_scale,
                           const int* flip, float thresh, int per_member_lists) {
   API_BEGIN
+  refuse_multiclass_lists("detect_add_levels", net);
   if (n < 1 || n > kMaxGroup) throw std::runtime_error("detect_add_levels: 1..16 units per group");
   for (int m = 0; m < n; ++m) {
     for (int q = 0; q < m; ++q)

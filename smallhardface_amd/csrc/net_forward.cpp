@@ -51,7 +51,7 @@ static double conv_flops(const Layer& L, const std::vector<int>& in, const std::
 TailArgs shf_net::tail_args(float im_h, float im_w, float im_scale, bool materialize) {
   if (tail_w_dirty || tail_gen != *wgen) build_tail_weights();
   TailArgs t;
-  t.A = tail_A; t.heads = tail_heads; t.Cf = tail_Cf;
+  t.A = tail_A; t.C = tail_C; t.heads = tail_heads; t.Cf = tail_Cf;
   for (int i = 0; i < tail_heads; ++i) t.feat[i] = view_of(tail_feat_blobs[i]);
   t.wcls[0] = (const float*)tail_W.p;
   t.bcls[0] = (const float*)tail_b.p;
@@ -144,8 +144,8 @@ void shf_net::add_cost(int li, bool fused, int heads, double& flops, double& byt
   if (L.op == OP_TAIL) {
     const Blob& f = blobs[tail_feat_blobs[0]];
     const double K = (double)f.shape[2] * f.shape[3];
-    flops += 2.0 * K * tail_A * 6 * tail_Cf;
-    bytes += 4.0 * K * (tail_heads * tail_Cf + tail_A * 18);
+    flops += 2.0 * K * tail_A * (tail_C + 4) * tail_Cf;
+    bytes += 4.0 * K * (tail_heads * tail_Cf + tail_A * 3 * (tail_C + 4));
     return;
   }
   const Blob& ib = blobs[L.bottoms[0]];
@@ -385,7 +385,7 @@ void shf_net::record_forward(bool plain, int R) {
   plain_stale = !plain;
   if (tail_layer >= 0) {
     blobs[boxes_blob].shape = {std::max(R, 1), 5};
-    if (prob_blob >= 0) blobs[prob_blob].shape = {R, 2};
+    if (prob_blob >= 0) blobs[prob_blob].shape = {R, tail_C};
   }
   // (tail-fused blobs too: "newer" for them means the tail workspace holds this forward's logits -- read on demand)
   for (size_t i = 0; i < blobs.size(); ++i)
@@ -519,37 +519,37 @@ void shf_net::ensure_plain() {
 // Blob.data of a blob whose producer was folded into the detection tail (the cls / bbox 1x1 convs, the score concat /
 // reshape, the softmax): pycaffe exposes every blob after forward() (pycaffe.py:24-32, _caffe.cpp:222-242), and someone
 // debugging through the shim reads them.  Nothing extra is computed in forward(): the logits kernel leaves
-// [K][A][cls0, cls1, dx, dy, dw, dh] in the tail workspace and the tail writes the softmax as the (1, 2A, h, w) blob the
+// [K][A][cls0 .. cls(C-1), dx, dy, dw, dh] in the tail workspace and the tail writes the softmax as the (1, C*A, h, w) blob the
 // proposal layer reads; the read-back re-orders those on the host into the blob's own NCHW shape.
 void shf_net::materialize_fused(int bi) {
   Blob& b = blobs[bi];
   const size_t n = b.count();
   b.host.ensure(std::max<size_t>(n, 1) * 4);
   if (!b.dev_newer || n == 0) return;          // (never forwarded: zeros, like a Caffe blob before its first forward)
-  const int A = tail_A;
+  const int A = tail_A, NC = tail_C, NO = tail_C + 4;
   const int h = blobs[tail_feat_blobs[0]].shape[2], w = blobs[tail_feat_blobs[0]].shape[3];
   const size_t K = (size_t)h * w;
   float* out = b.host.p;
   if (b.fused_role == FR_PROB_PLANES) {
-    if (n != K * A * 2) throw std::runtime_error("blob '" + b.name + "': unexpected shape for the softmax output");
+    if (n != K * A * NC) throw std::runtime_error("blob '" + b.name + "': unexpected shape for the softmax output");
     HIP_THROW(hipMemcpyAsync(out, blobs[tail_cls_blob].dev.p, n * 4, hipMemcpyDeviceToHost, stream));
     HIP_THROW(hipStreamSynchronize(stream));
     b.dev_newer = false;
     return;
   }
-  std::vector<float> lg(K * A * 6);
+  std::vector<float> lg(K * A * NO);
   HIP_THROW(hipMemcpyAsync(lg.data(), tw.logits, lg.size() * 4, hipMemcpyDeviceToHost, stream));
   HIP_THROW(hipStreamSynchronize(stream));
-  auto L = [&](size_t k, int a, int o) { return lg[(k * A + a) * 6 + o]; };
+  auto L = [&](size_t k, int a, int o) { return lg[(k * A + a) * NO + o]; };
   const bool per_head = tail_heads != 1;
   switch (b.fused_role) {
     case FR_CLS_CONV:
-      if (n != (per_head ? 2 : 2 * (size_t)A) * K) throw std::runtime_error("blob '" + b.name + "': unexpected shape");
+      if (n != (per_head ? NC : NC * (size_t)A) * K) throw std::runtime_error("blob '" + b.name + "': unexpected shape");
       if (per_head) {
-        for (int c = 0; c < 2; ++c)
+        for (int c = 0; c < NC; ++c)
           for (size_t k = 0; k < K; ++k) out[c * K + k] = L(k, b.fused_head, c);
       } else {
-        for (int c = 0; c < 2; ++c)
+        for (int c = 0; c < NC; ++c)
           for (int a = 0; a < A; ++a)
             for (size_t k = 0; k < K; ++k) out[((size_t)c * A + a) * K + k] = L(k, a, c);
       }
@@ -558,16 +558,16 @@ void shf_net::materialize_fused(int bi) {
       if (n != (per_head ? 4 : 4 * (size_t)A) * K) throw std::runtime_error("blob '" + b.name + "': unexpected shape");
       if (per_head) {
         for (int j = 0; j < 4; ++j)
-          for (size_t k = 0; k < K; ++k) out[j * K + k] = L(k, b.fused_head, 2 + j);
+          for (size_t k = 0; k < K; ++k) out[j * K + k] = L(k, b.fused_head, NC + j);
       } else {
         for (int a = 0; a < A; ++a)
           for (int j = 0; j < 4; ++j)
-            for (size_t k = 0; k < K; ++k) out[((size_t)a * 4 + j) * K + k] = L(k, a, 2 + j);
+            for (size_t k = 0; k < K; ++k) out[((size_t)a * 4 + j) * K + k] = L(k, a, NC + j);
       }
       break;
-    case FR_CLS_PLANES:   // (1, 2, A*h, w): plane c, rows a*h .. a*h + h - 1 = head / anchor a
-      if (n != 2 * (size_t)A * K) throw std::runtime_error("blob '" + b.name + "': unexpected shape");
-      for (int c = 0; c < 2; ++c)
+    case FR_CLS_PLANES:   // (1, C, A*h, w): plane c, rows a*h .. a*h + h - 1 = head / anchor a
+      if (n != NC * (size_t)A * K) throw std::runtime_error("blob '" + b.name + "': unexpected shape");
+      for (int c = 0; c < NC; ++c)
         for (int a = 0; a < A; ++a)
           for (size_t k = 0; k < K; ++k) out[((size_t)c * A + a) * K + k] = L(k, a, c);
       break;

@@ -284,7 +284,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
     const int l_sm = prod(layers[l_rs].bottoms[0], "Softmax");
     fused_layers.insert(l_rs);
     fused_layers.insert(l_sm);
-    int pre = layers[l_sm].bottoms[0];
+    int pre = layers[l_sm].bottoms[0], l_pre_rs = -1;
     auto pit = producer.find(pre);
     if (pit == producer.end()) throw std::runtime_error("tail: dangling softmax input");
     if (layers[pit->second].type == "Concat") {
@@ -294,6 +294,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
       fused_layers.insert(l_cc);
       for (int b : layers[l_cc].bottoms) tail_cls_layers.push_back(prod(b, "Convolution"));
     } else if (layers[pit->second].type == "Reshape") {
+      l_pre_rs = pit->second;
       fused_layers.insert(pit->second);
       tail_cls_layers.push_back(prod(layers[pit->second].bottoms[0], "Convolution"));
     } else {
@@ -363,10 +364,41 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
       }
     }
     if (tail_heads != 1 && tail_heads != tail_A) throw std::runtime_error("tail: heads must be 1 or == anchors");
-    const int ncls = tail_heads == 1 ? 2 * tail_A : 2, nbox = tail_heads == 1 ? 4 * tail_A : 4;
-    for (int i = 0; i < tail_heads; ++i)
-      if (layers[tail_cls_layers[i]].nout != ncls || layers[tail_box_layers[i]].nout != nbox)
-        throw std::runtime_error("tail: predictor channel counts do not match the anchors");
+    // the class count (proposal_layer.py:118: scores.shape[1] / A): every per-head predictor has C outputs, the single-blob
+    // one C * A with channel c * A + a; the Reshapes around the softmax must say the same
+    const std::string who = "ProposalLayer '" + T.name + "': ";
+    const bool per_head = tail_heads != 1;
+    int C = -1;
+    for (int i = 0; i < tail_heads; ++i) {
+      const Layer& c = layers[tail_cls_layers[i]];
+      if (!per_head && c.nout % tail_A)
+        throw std::runtime_error(who + "class predictor '" + c.name + "' has " + std::to_string(c.nout) + " outputs, not a multiple of the " +
+                                 std::to_string(tail_A) + " anchors");
+      const int ci = per_head ? c.nout : c.nout / tail_A;
+      if (C >= 0 && ci != C)
+        throw std::runtime_error(who + "class predictors '" + layers[tail_cls_layers[0]].name + "' and '" + c.name +
+                                 "' disagree on the class count (" + std::to_string(C) + " vs " + std::to_string(ci) + ")");
+      C = ci;
+      if (layers[tail_box_layers[i]].nout != (per_head ? 4 : 4 * tail_A))
+        throw std::runtime_error(who + "bbox predictor '" + layers[tail_box_layers[i]].name + "' channel count does not match the anchors");
+    }
+    auto reshape_dim1 = [&](int li2) {
+      const PMsg* rp = layers[li2].msg->sub("reshape_param");
+      std::vector<int> dims;
+      if (rp && rp->sub("shape"))
+        for (auto d : rp->sub("shape")->all("dim")) dims.push_back(atoi(d->scalar.c_str()));
+      return dims.size() > 1 ? dims[1] : 0;
+    };
+    if (l_pre_rs >= 0 && reshape_dim1(l_pre_rs) != C)
+      throw std::runtime_error(who + "Reshape '" + layers[l_pre_rs].name + "' makes " + std::to_string(reshape_dim1(l_pre_rs)) +
+                               " class planes, the predictor has " + std::to_string(C) + " classes per anchor");
+    if (reshape_dim1(l_rs) != C * tail_A)
+      throw std::runtime_error(who + "Reshape '" + layers[l_rs].name + "' makes " + std::to_string(reshape_dim1(l_rs)) +
+                               " channels, the predictors give " + std::to_string(C) + " classes x " + std::to_string(tail_A) + " anchors");
+    if (C < 2) throw std::runtime_error(who + "at least 2 classes (background and one foreground class) are needed, the predictors have " + std::to_string(C));
+    if (C > kTailMaxClasses)
+      throw std::runtime_error(who + std::to_string(C) + " classes: the tail supports at most " + std::to_string(kTailMaxClasses));
+    tail_C = C;
     for (int li2 : fused_layers) {
       layers[li2].op = OP_SKIP;
       // what the top holds, for the on-demand read-back (shf_net::materialize_fused)
@@ -650,7 +682,7 @@ void shf_net::infer_shapes() {
       blobs[L.tops[0]].shape = out;
     } else if (L.type == "Python") {
       if (blobs[L.tops[0]].shape.size() != 2) blobs[L.tops[0]].shape = {1, 5};
-      if (L.tops.size() > 1 && blobs[L.tops[1]].shape.size() != 2) blobs[L.tops[1]].shape = {1, 2};
+      if (L.tops.size() > 1 && blobs[L.tops[1]].shape.size() != 2) blobs[L.tops[1]].shape = {1, tail_C};
     }
   }
   if (data_blob >= 0) last_data_shape = blobs[data_blob].shape;
@@ -674,8 +706,9 @@ void shf_net::alloc_buffers() {
 void shf_net::ensure_tail_workspace(size_t total) {
   size_t npad = 1;
   while (npad < total) npad <<= 1;
-  tw_logits.ensure(total * 6 * 4);
-  tw_rec.ensure(total * 6 * 4);
+  const size_t rec = (size_t)tail_C + 4;   // floats per anchor: the class scores and four box values
+  tw_logits.ensure(total * rec * 4);
+  tw_rec.ensure(total * rec * 4);
   tw_keys.ensure(std::max<size_t>(npad, 16384) * 8);
   tw_counters.ensure(64);
   tw.logits = (float*)tw_logits.p;
@@ -688,14 +721,14 @@ void shf_net::ensure_tail_workspace(size_t total) {
   tw.cap_keys = npad;
   const size_t rmax = (pre_nms_topN > 0) ? std::min<size_t>(total, (size_t)pre_nms_topN) : total;
   blobs[boxes_blob].dev.ensure(std::max<size_t>(rmax, 1) * 5 * 4);
-  if (prob_blob >= 0) blobs[prob_blob].dev.ensure(std::max<size_t>(rmax, 1) * 2 * 4);
+  if (prob_blob >= 0) blobs[prob_blob].dev.ensure(std::max<size_t>(rmax, 1) * tail_C * 4);
 }
 
 void shf_net::build_tail_weights() {
   if (tail_layer < 0) return;
   tail_Cf = blobs[tail_feat_blobs[0]].shape[1];
-  const int A = tail_A, Cf = tail_Cf;
-  std::vector<float> W((size_t)A * 6 * Cf, 0.f), B((size_t)A * 6, 0.f);
+  const int A = tail_A, Cf = tail_Cf, NC = tail_C, NO = tail_C + 4;
+  std::vector<float> W((size_t)A * NO * Cf, 0.f), B((size_t)A * NO, 0.f);
   for (int a = 0; a < A; ++a) {
     const int h = tail_heads == 1 ? 0 : a;
     Layer& c = layers[tail_cls_layers[h]];
@@ -704,16 +737,16 @@ void shf_net::build_tail_weights() {
     const float* bw = b.params[0]->host.data();
     const float* cb = c.params.size() > 1 ? c.params[1]->host.data() : nullptr;
     const float* bb = b.params.size() > 1 ? b.params[1]->host.data() : nullptr;
-    for (int cls = 0; cls < 2; ++cls) {
-      // plain template: cls_score channel = cls*A + a (Reshape (0,2,-1,0)); dilation template: channel = cls
+    for (int cls = 0; cls < NC; ++cls) {
+      // plain template: cls_score channel = cls*A + a (Reshape (0,C,-1,0)); dilation template: channel = cls
       const int row = tail_heads == 1 ? cls * A + a : cls;
-      memcpy(&W[((size_t)a * 6 + cls) * Cf], cw + (size_t)row * Cf, Cf * sizeof(float));
-      B[a * 6 + cls] = cb ? cb[row] : 0.f;
+      memcpy(&W[((size_t)a * NO + cls) * Cf], cw + (size_t)row * Cf, Cf * sizeof(float));
+      B[a * NO + cls] = cb ? cb[row] : 0.f;
     }
     for (int j = 0; j < 4; ++j) {
       const int row = tail_heads == 1 ? a * 4 + j : j;
-      memcpy(&W[((size_t)a * 6 + 2 + j) * Cf], bw + (size_t)row * Cf, Cf * sizeof(float));
-      B[a * 6 + 2 + j] = bb ? bb[row] : 0.f;
+      memcpy(&W[((size_t)a * NO + NC + j) * Cf], bw + (size_t)row * Cf, Cf * sizeof(float));
+      B[a * NO + NC + j] = bb ? bb[row] : 0.f;
     }
   }
   tail_W.ensure(W.size() * 4);

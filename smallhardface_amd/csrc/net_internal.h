@@ -144,10 +144,10 @@ struct Blob {
 // what a tail-fused blob holds (pycaffe exposes every blob after forward(), pycaffe.py:24-32 / _caffe.cpp:222-242)
 enum FusedRole {
   FR_NONE = 0,
-  FR_CLS_CONV,     // top of a class-score 1x1 conv: (1, 2, h, w) per head, or (1, 2A, h, w) channel = cls * A + a (plain template)
+  FR_CLS_CONV,     // top of a class-score 1x1 conv: (1, C, h, w) per head, or (1, C*A, h, w) channel = cls * A + a (plain template)
   FR_BOX_CONV,     // top of a bbox 1x1 conv: (1, 4, h, w) per head, or (1, 4A, h, w) channel = 4a + j
-  FR_CLS_PLANES,   // the pre-softmax (1, 2, A*h, w) tensor: axis-2 Concat of the heads' scores, or the plain template's Reshape
-  FR_PROB_PLANES   // the Softmax's top, (1, 2, A*h, w): the memory of the materialised (1, 2A, h, w) cls_prob blob
+  FR_CLS_PLANES,   // the pre-softmax (1, C, A*h, w) tensor: axis-2 Concat of the heads' scores, or the plain template's Reshape
+  FR_PROB_PLANES   // the Softmax's top, (1, C, A*h, w): the memory of the materialised (1, C*A, h, w) cls_prob blob
 };
 
 void check_blob_dims(const std::vector<int>& shp, const std::string& name);   // net_graph.cpp: Blob::Reshape's limits
@@ -394,6 +394,7 @@ struct shf_net {
   std::vector<int> tail_cls_layers, tail_box_layers;  // per head (or single)
   std::vector<int> tail_feat_blobs;
   int tail_A = 0, tail_heads = 0, tail_Cf = 0;
+  int tail_C = 2;   // classes (background first), 2 .. kTailMaxClasses: from the predictors' output counts
   int tail_cls_blob = -1, tail_box_blob = -1, im_info_blob = -1, boxes_blob = -1, prob_blob = -1, data_blob = -1;
   std::vector<double> anchors;
   std::vector<int> sub_stride;
@@ -549,6 +550,8 @@ void forward_group(shf_net* head, int n, shf_net* const* members);
 // net_detect.cpp: append a group of finished units to `net`'s image list (or, per_member, to each member's own) in ONE launch
 void append_units(shf_net* net, shf_net* const* srcs, int n, const int* im_w, const float* im_scale, const int* flip,
                   float thresh, bool per_member, hipStream_t st = nullptr, Prof* pf = nullptr);
+// ... whose rows carry ONE foreground score: throws, naming the class count, for a net with more than two classes
+void refuse_multiclass_lists(const char* who, const shf_net* net);
 
 // ---------------------------------------------------------------------------
 // C ABI

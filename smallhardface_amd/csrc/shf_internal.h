@@ -133,12 +133,14 @@ int launch_pyramid_level(const uint8_t* im, int im_h, int im_w, double scale, in
                          float* out, int H, int W, int lvl_h, int lvl_w, hipStream_t s);
 
 // ---- detection tail ------------------------------------------------------------
+constexpr int kTailMaxClasses = 8;   // class counts the tail kernels are instantiated for: 2 .. 8 (background + 1 .. 7)
 struct TailArgs {
   // per-anchor-set (dilation head) features and 1x1 weights
   int A = 3;                 // anchors per cell (== number of heads, or 1 head with A outputs)
+  int C = 2;                 // classes, background first (proposal_layer.py:118)
   int heads = 3;             // number of distinct feature maps (3: one per dilation; 1: plain template)
   View feat[8];              // head feature maps (h,w,Cf)
-  const float* wcls[8];      // heads==A: (2,Cf) per head ; heads==1: (2A,Cf)
+  const float* wcls[8];      // heads==A: (C,Cf) per head ; heads==1: (C*A,Cf)
   const float* bcls[8];
   const float* wbox[8];      // heads==A: (4,Cf) per head ; heads==1: (4A,Cf)
   const float* bbox[8];
@@ -151,14 +153,14 @@ struct TailArgs {
   float score_thresh = 0.002f;
   int pre_nms_topN = 10000;
   // optional materialised Caffe blobs (NCHW), may be null
-  float* cls_prob_reshape_nchw = nullptr;  // (1,2A,h,w)
+  float* cls_prob_reshape_nchw = nullptr;  // (1,C*A,h,w)
   float* bbox_pred_nchw = nullptr;         // (1,4A,h,w)
   int f64 = 0;               // conv mode "f64": the predictors' dot products accumulate in binary64, one rounding to fp32
-  int probs_given = 0;       // diagnostics: the logits workspace already holds bg/fg probabilities (launch_tail_inject)
+  int probs_given = 0;       // diagnostics: the logits workspace already holds the class probabilities (launch_tail_inject)
 };
 struct TailWork {  // device workspace owned by the net, sized for the largest level seen
-  float* logits = nullptr;           // [K][A][6]
-  float* rec = nullptr;              // [K*A][6] = bg, fg, x1,y1,x2,y2
+  float* logits = nullptr;           // [K][A][C + 4]
+  float* rec = nullptr;              // [K*A][C + 4] = the C class probabilities, x1,y1,x2,y2
   unsigned long long* keys = nullptr;  // [pow2 >= K*A]
   int* counters = nullptr;           // [8]: 0 = n candidates, 1 = overflow flag, 2 = R, 3 = argmax idx
   size_t cap_anchors = 0, cap_keys = 0;
@@ -167,10 +169,10 @@ struct TailWork {  // device workspace owned by the net, sized for the largest l
   unsigned* amax = nullptr;
   int n_amax = 0;
 };
-// runs logits -> decode -> select -> sort; leaves R (device counters[2]) rows in out_boxes/out_probs
-int launch_tail(const TailArgs& a, TailWork& ws, float* out_boxes5, float* out_probs2, hipStream_t s,
+// runs logits -> decode -> select -> sort; leaves R (device counters[2]) rows in out_boxes (R, 5) / out_probs (R, C)
+int launch_tail(const TailArgs& a, TailWork& ws, float* out_boxes5, float* out_probs, hipStream_t s,
                 hipEvent_t after_logits = nullptr, int phase = 0);
-// diagnostics (shf_debug_proposal): fill the logits workspace from injected (1,2A,h,w) probabilities and
+// diagnostics (shf_debug_proposal): fill the logits workspace from injected (1,C*A,h,w) probabilities and
 // (1,4A,h,w) deltas (device pointers, NCHW) and raise the overflow flag; follow with launch_tail(phase 2, probs_given)
 int launch_tail_inject(const TailArgs& a, TailWork& ws, const float* scores_nchw, const float* deltas_nchw,
                        hipStream_t s);
@@ -178,7 +180,7 @@ int launch_tail_inject(const TailArgs& a, TailWork& ws, const float* scores_nchw
 
 // the same for a GROUP of independent units (the units of an image's pyramid): ONE launch per stage.  phase 0:
 // everything; 1: counters reset + logits kernel (after_logits recorded behind it); 2: decode -> sort -> gather
-int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* out_boxes5, float* const* out_probs2,
+int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* out_boxes5, float* const* out_probs,
                       int n, hipStream_t s, hipEvent_t after_logits = nullptr, int phase = 0);
 
 // generic device sort of u64 keys, descending; n_dev points at the element count on the device,
@@ -189,7 +191,8 @@ int launch_sort_desc_u64_group(unsigned long long* const* keys, const int* const
 
 // append the >thresh detections of a group of finished units to an image list (test.py:52-66,163-167): flip fix,
 // unscale, threshold cut.  count[pass & 1] = list length before the pass, count[(pass + 1) & 1] after it; with
-// per_member != 0 every unit has its own (reset) list and count[1] receives its length.
+// per_member != 0 every unit has its own (reset) list and count[1] receives its length.  Two-class units only: the list
+// holds the one foreground class's score (probs2 = (R, 2) rows).
 struct AppendUnit {
   const float* boxes5;
   const float* probs2;

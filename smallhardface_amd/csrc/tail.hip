@@ -60,13 +60,13 @@ __global__ void tail_reset_kernel(TailResetK p) {
 struct TailGM {  // per member
   const float* feat[8];
   int fstride[8];
-  float* logits;    // [K][A][6]
+  float* logits;    // [K][A][C + 4]
   int* counters;    // [1] = overflow flag
   int K, w;
 };
 struct TailGK {
-  const float* Wt;  // [A][6][Cf]  rows: cls0, cls1, dx, dy, dw, dh
-  const float* bt;  // [A][6]
+  const float* Wt;  // [A][C + 4][Cf]  rows: cls0 .. cls(C-1), dx, dy, dw, dh
+  const float* bt;  // [A][C + 4]
   int A, Cf;
   float aw[8], ah[8];  // base anchor widths / heights (x2-x1+1)
   int blk_start[TG + 1];
@@ -76,8 +76,10 @@ struct TailGK {
 // ---- 1x1 cls/reg convs: wave handles two pixels, 32 lanes x float4 per pixel -------------
 // F64 (conv mode "f64"): the products and the sum in binary64 (a product of two fp32 values is exact there), the bias added
 // in binary64, ONE rounding to fp32
-template <bool F64>
+// NC: the class count (2 .. 8); a record is NC class scores and four box deltas, NC + 4 floats at 4-byte alignment
+template <bool F64, int NC>
 __global__ __launch_bounds__(256) void tail_logits_kernel(TailGK g) {
+  constexpr int NO = NC + 4;
   typedef typename std::conditional<F64, double, float>::type acc_t;
   const int mi = tail_find_member(g.blk_start, blockIdx.x);
   const TailGM& p = g.m[mi];
@@ -92,13 +94,13 @@ __global__ __launch_bounds__(256) void tail_logits_kernel(TailGK g) {
     const int fs = p.fstride[a];
     for (long long pr = wave; pr < npairs; pr += nwaves) {
       const long long k = pr * 2 + sub;
-      acc_t part[6] = {0, 0, 0, 0, 0, 0};
+      acc_t part[NO] = {};
       if (k < p.K) {
         for (int c0 = 0; c0 < g.Cf; c0 += 128) {
           const float4 x = *(const float4*)(f + (size_t)k * fs + c0 + q * 4);
 #pragma unroll
-          for (int o = 0; o < 6; ++o) {
-            const float4 wv = *(const float4*)(g.Wt + ((size_t)a * 6 + o) * g.Cf + c0 + q * 4);
+          for (int o = 0; o < NO; ++o) {
+            const float4 wv = *(const float4*)(g.Wt + ((size_t)a * NO + o) * g.Cf + c0 + q * 4);
             if constexpr (F64)
               part[o] += (double)x.x * (double)wv.x + (double)x.y * (double)wv.y + (double)x.z * (double)wv.z + (double)x.w * (double)wv.w;
             else
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(256) void tail_logits_kernel(TailGK g) {
       // step m the lanes i and i ^ m hold the same bits (a + b == b + a), so the partner of step 8 / 4 may as well be the
       // lane 8 / 4 places round the 16-lane row (DPP row_ror), and steps 2 / 1 are quad permutes: the same tree, the same bits
 #pragma unroll
-      for (int o = 0; o < 6; ++o) {
+      for (int o = 0; o < NO; ++o) {
         if constexpr (F64) {
           double v = part[o];
 #pragma unroll
@@ -127,13 +129,13 @@ __global__ __launch_bounds__(256) void tail_logits_kernel(TailGK g) {
         }
       }
       if (q == 0 && k < p.K) {
-        float* L = p.logits + ((size_t)k * g.A + a) * 6;
+        float* L = p.logits + ((size_t)k * g.A + a) * NO;
         bool of = false;
 #pragma unroll
-        for (int o = 0; o < 6; ++o) {
-          const float v = (float)(part[o] + (acc_t)g.bt[a * 6 + o]);
+        for (int o = 0; o < NO; ++o) {
+          const float v = (float)(part[o] + (acc_t)g.bt[a * NO + o]);
           L[o] = v;
-          if (o >= 4) of |= delta_overflows(v, o == 4 ? g.aw[a] : g.ah[a]);
+          if (o >= NC + 2) of |= delta_overflows(v, o == NC + 2 ? g.aw[a] : g.ah[a]);
         }
         if (of) atomicOr(&p.counters[1], 1);
       }
@@ -141,23 +143,22 @@ __global__ __launch_bounds__(256) void tail_logits_kernel(TailGK g) {
   }
 }
 
-// diagnostics: (1,2A,h,w) probabilities + (1,4A,h,w) deltas in the blobs' NCHW layout -> the tail's
-// [K][A][6] records, raising the same overflow flag the logits kernel raises
+// diagnostics: (1,C*A,h,w) probabilities (channel c*A + a) + (1,4A,h,w) deltas in the blobs' NCHW layout -> the tail's
+// [K][A][C + 4] records, raising the same overflow flag the logits kernel raises
 __global__ void tail_inject_kernel(const float* __restrict__ scores, const float* __restrict__ deltas,
-                                   float* __restrict__ logits, int K, int A, TailGK g, int* counters) {
+                                   float* __restrict__ logits, int K, int A, int NC, TailGK g, int* counters) {
   const long long total = (long long)K * A;
   for (long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x; n < total;
        n += (long long)gridDim.x * blockDim.x) {
     const int a = (int)(n % A);
     const long long k = n / A;
-    float* L = logits + n * 6;
-    L[0] = scores[(size_t)a * K + k];
-    L[1] = scores[(size_t)(A + a) * K + k];
+    float* L = logits + n * (NC + 4);
+    for (int c = 0; c < NC; ++c) L[c] = scores[(size_t)(c * A + a) * K + k];
     bool of = false;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float v = deltas[(size_t)(a * 4 + j) * K + k];
-      L[2 + j] = v;
+      L[NC + j] = v;
       if (j >= 2) of |= delta_overflows(v, j == 2 ? g.aw[a] : g.ah[a]);
     }
     if (of) atomicOr(&counters[1], 1);
@@ -165,13 +166,13 @@ __global__ void tail_inject_kernel(const float* __restrict__ scores, const float
 }
 
 struct DecodeGM {  // per member
-  const float* logits;  // [K][A][6]
-  float* rec;           // [K*A][6] bg, fg, x1, y1, x2, y2
+  const float* logits;  // [K][A][C + 4]
+  float* rec;           // [K*A][C + 4] the C class probabilities, x1, y1, x2, y2
   unsigned long long* keys;
   int* counters;        // 0: n candidates, 1: overflow flag ; [4..5] as u64: best key
   int K, w;
   float im_h, im_w, min_size_scaled;
-  float* cls_nchw;   // optional (1,2A,h,w)
+  float* cls_nchw;   // optional (1,C*A,h,w), channel c*A + a
   float* bbox_nchw;  // optional (1,4A,h,w)
 };
 struct DecodeGK {
@@ -180,12 +181,14 @@ struct DecodeGK {
   int sub_stride[8];
   int feat_stride;
   float score_thresh;
-  int probs_given;   // diagnostics (shf_debug_proposal): L[0..1] already hold bg/fg probabilities
+  int probs_given;   // diagnostics (shf_debug_proposal): L[0..C-1] already hold the class probabilities
   int blk_start[TG + 1];
   DecodeGM m[TG];
 };
 
+template <int NC>
 __global__ __launch_bounds__(256) void tail_decode_kernel(DecodeGK g) {
+  constexpr int NO = NC + 4;
   const int mi = tail_find_member(g.blk_start, blockIdx.x);
   const DecodeGM& p = g.m[mi];
   const int lb = blockIdx.x - g.blk_start[mi], lgrid = g.blk_start[mi + 1] - g.blk_start[mi];
@@ -204,17 +207,29 @@ __global__ __launch_bounds__(256) void tail_decode_kernel(DecodeGK g) {
       const int a = (int)(n % g.A);
       const int k = (int)(n / g.A);
       const int y = k / p.w, x = k - y * p.w;
-      const float* L = p.logits + n * 6;
-      const float c0 = L[0], c1 = L[1];
-      // SoftmaxLayer::Forward: max, subtract, exp, sum, divide (softmax_layer.cpp:27-60)
-      const float m = fmaxf(c0, c1);
-      const float e0 = expf(c0 - m), e1 = expf(c1 - m);
-      const float sum = e0 + e1;
-      const float bg = g.probs_given ? c0 : e0 / sum, fg = g.probs_given ? c1 : e1 / sum;
-      float dx = L[2], dy = L[3], dw = L[4], dh = L[5];
+      const float* L = p.logits + n * NO;
+      // SoftmaxLayer::Forward: max, subtract, exp, sum (from class 0 upward), divide (softmax_layer.cpp:27-60)
+      float lg[NC], e[NC], pr[NC];
+#pragma unroll
+      for (int c = 0; c < NC; ++c) lg[c] = L[c];
+      float m = lg[0];
+#pragma unroll
+      for (int c = 1; c < NC; ++c) m = fmaxf(m, lg[c]);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) e[c] = expf(lg[c] - m);
+      float sum = e[0];
+#pragma unroll
+      for (int c = 1; c < NC; ++c) sum += e[c];
+#pragma unroll
+      for (int c = 0; c < NC; ++c) pr[c] = g.probs_given ? lg[c] : e[c] / sum;
+      // the layer ranks, cuts and picks its fallback row by the best foreground class (proposal_layer.py:180-188)
+      float fg = pr[1];
+#pragma unroll
+      for (int c = 2; c < NC; ++c) fg = fmaxf(fg, pr[c]);
+      float dx = L[NC], dy = L[NC + 1], dw = L[NC + 2], dh = L[NC + 3];
       if (p.cls_nchw) {
-        p.cls_nchw[(size_t)a * p.K + k] = bg;
-        p.cls_nchw[(size_t)(g.A + a) * p.K + k] = fg;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) p.cls_nchw[(size_t)(c * g.A + a) * p.K + k] = pr[c];
       }
       if (p.bbox_nchw) {
         p.bbox_nchw[(size_t)(a * 4 + 0) * p.K + k] = dx;
@@ -242,8 +257,10 @@ __global__ __launch_bounds__(256) void tail_decode_kernel(DecodeGK g) {
       y1 = fmaxf(fminf(y1, mh), 0.f);
       x2 = fmaxf(fminf(x2, mw), 0.f);
       y2 = fmaxf(fminf(y2, mh), 0.f);
-      float* r = p.rec + n * 6;
-      r[0] = bg; r[1] = fg; r[2] = x1; r[3] = y1; r[4] = x2; r[5] = y2;
+      float* r = p.rec + n * NO;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) r[c] = pr[c];
+      r[NC] = x1; r[NC + 1] = y1; r[NC + 2] = x2; r[NC + 3] = y2;
       // anchor subsampling map + _filter_boxes (proposal_layer.py:160-175,231-236)
       const int ss = g.sub_stride[a];
       bool valid = (y % ss == 0) && (x % ss == 0);
@@ -288,7 +305,7 @@ struct GatherGM {
   const float* rec;
   int* counters;
   float* boxes5;
-  float* probs2;
+  float* probs;   // (R, C) score rows
 };
 struct GatherGK {
   int topN;
@@ -297,7 +314,9 @@ struct GatherGK {
 };
 // finalize + gather in one: every block derives R from the counters (block 0 of the member publishes it in
 // counters[2] for the host / the append stage)
+template <int NC>
 __global__ void tail_gather_kernel(GatherGK g) {
+  constexpr int NO = NC + 4;
   const int mi = tail_find_member(g.blk_start, blockIdx.x);
   const GatherGM& p = g.m[mi];
   const int lb = blockIdx.x - g.blk_start[mi], lgrid = g.blk_start[mi + 1] - g.blk_start[mi];
@@ -313,14 +332,14 @@ __global__ void tail_gather_kernel(GatherGK g) {
   for (int r = lb * blockDim.x + threadIdx.x; r < R; r += lgrid * blockDim.x) {
     const unsigned long long key = only_best ? best : p.keys[r];
     const unsigned n = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-    const float* q = p.rec + (size_t)n * 6;
+    const float* q = p.rec + (size_t)n * NO;
     p.boxes5[r * 5 + 0] = 0.f;
-    p.boxes5[r * 5 + 1] = q[2];
-    p.boxes5[r * 5 + 2] = q[3];
-    p.boxes5[r * 5 + 3] = q[4];
-    p.boxes5[r * 5 + 4] = q[5];
-    p.probs2[r * 2 + 0] = q[0];
-    p.probs2[r * 2 + 1] = q[1];
+    p.boxes5[r * 5 + 1] = q[NC];
+    p.boxes5[r * 5 + 2] = q[NC + 1];
+    p.boxes5[r * 5 + 3] = q[NC + 2];
+    p.boxes5[r * 5 + 4] = q[NC + 3];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) p.probs[r * NC + c] = q[c];
   }
 }
 
@@ -458,7 +477,7 @@ int launch_sort_desc_u64(unsigned long long* keys, const int* n_dev, size_t n_ma
 
 // ---------------------------------------------------------------------------
 static void fill_logits_shared(const TailArgs& a, TailGK& lk) {
-  lk.Wt = a.wcls[0];  // combined [A][6][Cf] matrix prepared by the net (see net_graph.cpp: build_tail_weights)
+  lk.Wt = a.wcls[0];  // combined [A][C + 4][Cf] matrix prepared by the net (see net_graph.cpp: build_tail_weights)
   lk.bt = a.bcls[0];
   lk.A = a.A; lk.Cf = a.Cf;
   for (int i = 0; i < a.A; ++i) {
@@ -469,16 +488,30 @@ static void fill_logits_shared(const TailArgs& a, TailGK& lk) {
 
 // A group of units through the proposal stage.  phase 0: everything; 1: reset + logits (the kernels that read the
 // head feature maps: `after_logits` is recorded behind them); 2: decode -> sort -> gather.
-int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* out_boxes5, float* const* out_probs2,
+// the kernels are instantiated on the class count: the two-class records and arithmetic are what they were before the class
+// axis existed
+#define SHF_TAIL_FOR_CLASSES(C, X) \
+  switch (C) {                     \
+    case 2: X(2); break;           \
+    case 3: X(3); break;           \
+    case 4: X(4); break;           \
+    case 5: X(5); break;           \
+    case 6: X(6); break;           \
+    case 7: X(7); break;           \
+    default: X(8); break;          \
+  }
+
+int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* out_boxes5, float* const* out_probs,
                       int n, hipStream_t s, hipEvent_t after_logits, int phase) {
   if (n < 1 || n > TG) { set_error("tail group: 1..16 units"); return -1; }
   const TailArgs& a0 = as[0];
   if (a0.A > 8) { set_error("tail: at most 8 anchors per cell"); return -1; }
+  if (a0.C < 2 || a0.C > kTailMaxClasses) { set_error("tail: 2 .. 8 classes"); return -1; }
   for (int m = 0; m < n; ++m) {
     const long long total = (long long)as[m].h * as[m].w * as[m].A;
     if ((size_t)total > wss[m]->cap_anchors) { set_error("tail: workspace too small"); return -1; }
     if (as[m].Cf % 128) { set_error("tail: head feature width must be a multiple of 128"); return -1; }
-    if (as[m].A != a0.A || as[m].Cf != a0.Cf || as[m].wcls[0] != a0.wcls[0] || as[m].f64 != a0.f64) {
+    if (as[m].A != a0.A || as[m].C != a0.C || as[m].Cf != a0.Cf || as[m].wcls[0] != a0.wcls[0] || as[m].f64 != a0.f64) {
       set_error("tail group: members must share the proposal layer");
       return -1;
     }
@@ -512,10 +545,13 @@ int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* ou
       blocks += (int)grid_for(((long long)g.K + 1) / 2 * 64);
     }
     lk.blk_start[n] = blocks;
-    if (a0.f64)
-      hipLaunchKernelGGL(tail_logits_kernel<true>, dim3(blocks), dim3(256), 0, s, lk);
-    else
-      hipLaunchKernelGGL(tail_logits_kernel<false>, dim3(blocks), dim3(256), 0, s, lk);
+#define SHF_X(NC)                                                                           \
+  if (a0.f64)                                                                               \
+    hipLaunchKernelGGL((tail_logits_kernel<true, NC>), dim3(blocks), dim3(256), 0, s, lk);  \
+  else                                                                                      \
+    hipLaunchKernelGGL((tail_logits_kernel<false, NC>), dim3(blocks), dim3(256), 0, s, lk)
+    SHF_TAIL_FOR_CLASSES(a0.C, SHF_X)
+#undef SHF_X
     // from here on the tails only touch their own workspaces: the head feature maps may be overwritten
     if (after_logits) SHF_HIP_OK(hipEventRecord(after_logits, s));
   }
@@ -551,7 +587,7 @@ int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* ou
     dblocks += (int)grid_for(total);
     GatherGM& q = gk.m[m];
     q.keys = wss[m]->keys; q.rec = wss[m]->rec; q.counters = wss[m]->counters;
-    q.boxes5 = out_boxes5[m]; q.probs2 = out_probs2[m];
+    q.boxes5 = out_boxes5[m]; q.probs = out_probs[m];
     const long long rmax = (a.pre_nms_topN > 0 && a.pre_nms_topN < total) ? a.pre_nms_topN : total;
     gk.blk_start[m] = gblocks;
     gblocks += (int)grid_for(rmax);
@@ -561,17 +597,21 @@ int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* ou
   }
   dk.blk_start[n] = dblocks;
   gk.blk_start[n] = gblocks;
-  hipLaunchKernelGGL(tail_decode_kernel, dim3(dblocks), dim3(256), 0, s, dk);
+#define SHF_X(NC) hipLaunchKernelGGL(tail_decode_kernel<NC>, dim3(dblocks), dim3(256), 0, s, dk)
+  SHF_TAIL_FOR_CLASSES(a0.C, SHF_X)
+#undef SHF_X
   if (launch_sort_desc_u64_group(keys, n_dev, n_max, n, s)) return -1;
-  hipLaunchKernelGGL(tail_gather_kernel, dim3(gblocks), dim3(256), 0, s, gk);
+#define SHF_X(NC) hipLaunchKernelGGL(tail_gather_kernel<NC>, dim3(gblocks), dim3(256), 0, s, gk)
+  SHF_TAIL_FOR_CLASSES(a0.C, SHF_X)
+#undef SHF_X
   SHF_HIP_OK(hipGetLastError());
   return 0;
 }
 
-int launch_tail(const TailArgs& a, TailWork& ws, float* out_boxes5, float* out_probs2, hipStream_t s,
+int launch_tail(const TailArgs& a, TailWork& ws, float* out_boxes5, float* out_probs, hipStream_t s,
                 hipEvent_t after_logits, int phase) {
   TailWork* w = &ws;
-  return launch_tail_group(&a, &w, &out_boxes5, &out_probs2, 1, s, after_logits, phase);
+  return launch_tail_group(&a, &w, &out_boxes5, &out_probs, 1, s, after_logits, phase);
 }
 
 int launch_tail_inject(const TailArgs& a, TailWork& ws, const float* scores_nchw, const float* deltas_nchw,
@@ -579,11 +619,12 @@ int launch_tail_inject(const TailArgs& a, TailWork& ws, const float* scores_nchw
   const int K = a.h * a.w;
   const long long total = (long long)K * a.A;
   if ((size_t)total > ws.cap_anchors) { set_error("tail: workspace too small"); return -1; }
+  if (a.C < 2 || a.C > kTailMaxClasses) { set_error("tail: 2 .. 8 classes"); return -1; }
   SHF_HIP_OK(hipMemsetAsync(ws.counters, 0, 8 * sizeof(int), s));
   TailGK lk = {};
   fill_logits_shared(a, lk);
   hipLaunchKernelGGL(tail_inject_kernel, dim3(grid_for(total)), dim3(256), 0, s, scores_nchw, deltas_nchw, ws.logits,
-                     K, a.A, lk, ws.counters);
+                     K, a.A, a.C, lk, ws.counters);
   SHF_HIP_OK(hipGetLastError());
   return 0;
 }

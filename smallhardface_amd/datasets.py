@@ -71,13 +71,16 @@ def writer_for(db_name):
 
 
 class ImageList(object):
-    """The imdb surface lib/test.py uses, over a plain list of image paths."""
+    """The imdb surface lib/test.py uses, over a plain list of image paths.  ``classes``: the class names, background
+    first (default ['bg', 'face']); the detection writers write class 1, as the reference's do."""
 
-    def __init__(self, name, image_paths, writer=None, root='', ground_truth=None):
+    def __init__(self, name, image_paths, writer=None, root='', ground_truth=None, classes=None):
         self.name = name
         self._image_paths = list(image_paths)
         self._root = root
-        self._classes = ['bg', 'face']
+        self._classes = ['bg', 'face'] if classes is None else list(classes)
+        if len(self._classes) < 2:
+            raise ValueError("ImageList: classes needs the background and at least one foreground class, got %r" % (self._classes,))
         if writer is None:
             try:
                 writer = writer_for(name)

@@ -215,6 +215,9 @@ class ShardedDetector(object):
                  group=None, force_collective=False, cap_rows=None):
         import torch
         from .config import cfg
+        if getattr(net, "num_classes", 2) > 2:
+            # the per-member device lists carry one foreground score per row (C ABI shf_detect_add_levels refuses likewise)
+            raise ValueError("ShardedDetector: the net has %d classes; the fused per-image path supports 2" % net.num_classes)
         self.net, self.rank, self.world = net, int(rank), int(world)
         self.shard, self.thresh, self.group = shard, float(thresh), group
         self.force_collective = bool(force_collective)

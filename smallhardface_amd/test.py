@@ -683,12 +683,19 @@ def inference_worker(rank, imdb, target_test, start, end, thresh, result_queue=N
         # fp32 MFMA path); SHF_CONV_MODE=0 keeps the library default (exact fp32)
         net.set_conv_mode("f16x3")
 
+    if net.num_classes and net.num_classes != imdb.num_classes:
+        # (detect() returns num_classes - 1 lists per image; the loop below would drop or miss some without a word)
+        raise ValueError("the net's proposal layer has {} classes, the imdb '{}' has {}".format(
+            net.num_classes, imdb.name, imdb.num_classes))
+
     timers = {'detect': Timer(), 'misc': Timer()}
     pyramid = True if len(cfg.TEST.SCALES) > 1 else False
     dets = [[[] for _ in range(start, end)] for _ in range(imdb.num_classes)]
     if fused is None:
         fused = os.environ.get("SHF_FUSED_DETECT", "1") != "0"
-    fused = fused and pyramid and len(cfg.TEST.LEVEL) == 0
+    # the device-resident path keeps one detection list per image: a net with more foreground classes takes the per-unit
+    # detect() loop and its class loop
+    fused = fused and pyramid and len(cfg.TEST.LEVEL) == 0 and net.num_classes <= 2
 
     def progress(i):
         if rank == 0:
