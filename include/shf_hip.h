@@ -244,6 +244,44 @@ int shf_detect_import(shf_net* net, const float* src_dev5, int n_rows);
 int shf_detect_export_many(shf_net* net, int n, shf_net** members, float* const* dst_dev5, int cap_rows,
                            int* n_rows);
 
+/* ---- per-class detection lists of a multi-class image (csrc/class_lists.hip) ----
+ * What detect() does on the host after its forwards, for a net with C classes (2 .. 8), on the device: the per-unit flip
+ * fix and unscale of forward_net (lib/test.py:52-66), the per-class > thresh cut (lib/test.py:161-167) and the per-class
+ * merge (:168-176).  `net` -- the head -- holds C - 1 lists of (x1, y1, x2, y2, score) fp32 rows, one per foreground
+ * class; they stay in HBM from the proposal layer's outputs to the merged boxes.  The lists are separate from the
+ * single-list fused path (shf_detect_*), whose refusal of C > 2 stands.  Every entry below refuses, by name and before
+ * anything is launched: a NULL net or argument, a net without a proposal layer, a head with shf_net_set_pipeline
+ * enabled, and cls outside 1..C-1 where a class is named.
+ *
+ * begin: empties the lists (lib/test.py:131-132, the empty all_probs / all_boxes). */
+int shf_class_lists_begin(shf_net* net);
+/* add (lib/test.py:52-66 per unit, :161-167 the cut): appends the outputs of n members, 1 <= n <= 16, each of which has
+ * completed a forward (shf_net_forward / shf_net_forward_group), read where they sit in the members' `boxes` / `cls_prob`
+ * device buffers; R is the row count the member's last forward recorded (a member whose proposal layer emitted only the
+ * dummy roi has R = 0 and contributes nothing).  Member i's boxes are mirrored about im_w[i] when flip[i] != 0, then
+ * divided by im_scale[i] (fp32 division).  List c - 1 receives every row with cls_prob[r, c] > thresh in (member, row)
+ * order -- np.where on the concatenated units -- behind the rows it already holds: a later group of the same image
+ * continues the lists.  Positions come from prefix sums, never from atomics.  A list holds at most units x rmax rows
+ * (rmax = cfg.TEST.N_DETS_PER_MODULE, or the anchor count when that is <= 0; the buffers grow to at least 16 x rmax):
+ * rows beyond that are dropped and the length is clamped.  Runs on `net`'s stream.  Also refused: n outside 1..16, a
+ * member without a completed forward, a member whose class count differs from the head's. */
+int shf_class_lists_add(shf_net* net, int n, shf_net** members, const int* im_w, const float* im_scale, const int* flip,
+                        float thresh);
+/* diagnostics: the same with HOST arrays injected in place of forwarded members (cf. shf_debug_append): boxes5[i] (R[i],5)
+ * and probs[i] (R[i],C) fp32, C = shf_net_num_classes(net); boxes5[i] / probs[i] may be NULL when R[i] == 0. */
+int shf_debug_class_lists_add(shf_net* net, int n, const float* const* boxes5, const float* const* probs, const int* R,
+                              const int* im_w, const float* im_scale, const int* flip, float thresh);
+/* counts[0 .. C-2] = rows of each list (synchronises `net`'s stream) */
+int shf_class_lists_count(shf_net* net, int* counts);
+/* the rows of class cls (1 .. C-1) to a caller-owned DEVICE buffer of cap_rows rows, as shf_detect_export does for the
+ * single list; returns the list's row count (which may exceed cap_rows: only cap_rows are written), -1 on error */
+int shf_class_lists_export(shf_net* net, int cls, float* dst_dev5, int cap_rows);
+/* the merge of class cls (lib/test.py:168-176) on the device: method / nms_thresh / out5 / cap / n_out as
+ * shf_detect_finish.  An empty class under BBOX_VOTE gives the row (10, 10, 20, 20, 0.0001) (lib/test.py:184-186); under
+ * NMS the rows are dets[keep] in keep order, none for an empty class.  More than 262144 rows in the class are refused
+ * like every merge. */
+int shf_class_lists_finish(shf_net* net, int cls, int method, float nms_thresh, double* out5, int cap, int* n_out);
+
 /* ---- stand-alone box ops ----------------------------------------------------- */
 /* nms(dets, thresh)  lib/nms/nms_wrapper.py:13 -> gpu_nms lib/nms/gpu_nms.pyx:16-31
  * -> _nms lib/nms/gpu_nms.hpp:1 (nms_kernel.cu:102-155).  Takes UNSORTED dets

@@ -112,6 +112,12 @@ def _declare(lib):
         "shf_detect_export": (ci, [vp, vp, ci, ip]),
         "shf_detect_import": (ci, [vp, vp, ci]),
         "shf_detect_export_many": (ci, [vp, ci, C.POINTER(vp), C.POINTER(vp), ci, ip]),
+        "shf_class_lists_begin": (ci, [vp]),
+        "shf_class_lists_add": (ci, [vp, ci, C.POINTER(vp), ip, fp, ip, cf]),
+        "shf_debug_class_lists_add": (ci, [vp, ci, C.POINTER(vp), C.POINTER(vp), ip, ip, fp, ip, cf]),
+        "shf_class_lists_count": (ci, [vp, ip]),
+        "shf_class_lists_export": (ci, [vp, ci, vp, ci]),
+        "shf_class_lists_finish": (ci, [vp, ci, ci, cf, dp, ci, ip]),
         "shf_debug_handover_event": (ci, [vp, ip, ip]),
         "shf_debug_merge": (ci, [vp, ci, cf, ci, vp, vp, vp, ip, vp, vp]),
         "shf_debug_proposal": (ci, [vp, fp, fp, ci, ci, fp, fp, fp, ci, ip, ip]),

@@ -3,7 +3,7 @@
     python -m smallhardface_amd.build          # incremental
     python -m smallhardface_amd.build --force
 
-hipcc cross-compiles without a GPU.  The box-arithmetic kernels (tail.hip, merge.hip,
+hipcc cross-compiles without a GPU.  The box-arithmetic kernels (tail.hip, class_lists.hip, merge.hip,
 eval.hip) and the image resize (pre.hip) are built with -ffp-contract=off so IoU / decode round like numpy and devIoU.
 """
 import os
@@ -22,6 +22,7 @@ SOURCES = [
     ("conv_f16x3.hip", []),
     ("misc.hip", []),
     ("tail.hip", ["-ffp-contract=off"]),
+    ("class_lists.hip", ["-ffp-contract=off"]),
     ("merge.hip", ["-ffp-contract=off"]),
     ("pre.hip", ["-ffp-contract=off"]),
     ("blob_io.hip", []),
@@ -30,10 +31,11 @@ SOURCES = [
     ("net_graph.cpp", []),
     ("net_forward.cpp", []),
     ("net_detect.cpp", []),
+    ("net_class_lists.cpp", []),
     ("net_api.cpp", []),
 ]
 HEADERS = ["shf_internal.h", "conv_common.h", "conv_lds_layout.h", "conv_f16x3_types.h", "conv_f16x3_8w.h", "conv_f16x3_w4d.h", "conv_f16x3_w4d_body.h", "conv_f16x3_pc.h", "conv_f16x3_k1.h", "conv_f16x3_h3.h", "conv_f64.h",
-           "proto_text.h", "net_internal.h", "eval.h", "blob_io.h", os.path.join("..", "..", "include", "shf_hip.h")]
+           "proto_text.h", "net_internal.h", "eval.h", "blob_io.h", "class_lists.h", os.path.join("..", "..", "include", "shf_hip.h")]
 
 
 def _newer(target, deps):

@@ -588,6 +588,88 @@ class Net(object):
     def detect_import(self, src_ptr, n_rows):
         _lib.check(self._lib.shf_detect_import(self._h, C.c_void_p(int(src_ptr)), int(n_rows)), "detect_import")
 
+    # -- per-class lists of a multi-class image (C ABI shf_class_lists_*) ---------------
+    def class_lists_begin(self):
+        """Empty this net's per-class detection lists: one per foreground class, resident on the device."""
+        self.commit_params()
+        self._apply_cfg()
+        _lib.check(self._lib.shf_class_lists_begin(self._h), "class_lists_begin")
+
+    def class_lists_add(self, members, im_w, im_scale, flip, thresh):
+        """Append the outputs of ``members`` -- nets that have completed ``forward()`` / ``forward_group``, at most 16 --
+        to the lists: per member forward_net's flip fix about ``im_w[i]`` when ``flip[i]`` and the division by
+        ``im_scale[i]``, then every row with ``cls_prob[r, c] > thresh`` to the list of class c, in (member, row) order.
+        Read from the members' device buffers; runs on this net's stream."""
+        members = list(members)
+        n = len(members)
+        if not (len(im_w) == len(im_scale) == len(flip) == n):
+            raise ValueError("class_lists_add: %d members, %d widths, %d scales, %d flips" % (n, len(im_w), len(im_scale), len(flip)))
+        mem = (C.c_void_p * max(n, 1))(*[getattr(m, "_h", None) for m in members])
+        _lib.check(self._lib.shf_class_lists_add(self._h, n, mem, (C.c_int * max(n, 1))(*[int(v) for v in im_w]),
+                                                 (C.c_float * max(n, 1))(*[float(v) for v in im_scale]),
+                                                 (C.c_int * max(n, 1))(*[1 if v else 0 for v in flip]), float(thresh)),
+                   "class_lists_add")
+
+    def debug_class_lists_add(self, boxes5, probs, im_w, im_scale, flip, thresh):
+        """``class_lists_add`` on injected host arrays (C ABI shf_debug_class_lists_add): per unit ``boxes5[i]`` (R_i, 5)
+        and ``probs[i]`` (R_i, C), C = ``self.num_classes``."""
+        nc = self.num_classes
+        bs = [np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 5) for b in boxes5]
+        ps = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, nc) for p in probs]
+        n = len(bs)
+        if not (len(ps) == len(im_w) == len(im_scale) == len(flip) == n):
+            raise ValueError("debug_class_lists_add: %d boxes, %d probs, %d widths, %d scales, %d flips"
+                             % (n, len(ps), len(im_w), len(im_scale), len(flip)))
+        # (a unit without score rows keeps the layer's dummy roi in boxes5: R is the number of SCORE rows)
+        R = [len(p) for p in ps]
+        assert all(len(b) >= r for b, r in zip(bs, R))
+        k = max(n, 1)
+        _lib.check(self._lib.shf_debug_class_lists_add(
+            self._h, n, (C.c_void_p * k)(*[b.ctypes.data for b in bs]), (C.c_void_p * k)(*[p.ctypes.data for p in ps]),
+            (C.c_int * k)(*R), (C.c_int * k)(*[int(v) for v in im_w]), (C.c_float * k)(*[float(v) for v in im_scale]),
+            (C.c_int * k)(*[1 if v else 0 for v in flip]), float(thresh)), "debug_class_lists_add")
+
+    def class_lists_count(self):
+        """Rows of each foreground class's list, class 1 first."""
+        n = max(self.num_classes - 1, 1)
+        cnt = (C.c_int * n)()
+        _lib.check(self._lib.shf_class_lists_count(self._h, cnt), "class_lists_count")
+        return [int(cnt[i]) for i in range(self.num_classes - 1)]
+
+    def class_lists_export(self, cls, dst_ptr=None, cap_rows=0):
+        """The rows of class ``cls`` (1 .. C-1): copied to the device buffer ``dst_ptr`` (``cap_rows`` rows; returns the
+        list's row count), or with ``dst_ptr=None`` returned as a float32 (n, 5) host array (tests)."""
+        if dst_ptr is not None:
+            n = self._lib.shf_class_lists_export(self._h, int(cls), C.c_void_p(int(dst_ptr)), int(cap_rows))
+            if n < 0:
+                raise _lib.ShfError("class_lists_export: " + _lib.last_error())
+            return n
+        import torch
+        n = self._lib.shf_class_lists_export(self._h, int(cls), None, 0)
+        if n < 0:
+            raise _lib.ShfError("class_lists_export: " + _lib.last_error())
+        buf = torch.empty((max(n, 1), 5), dtype=torch.float32, device="cuda")
+        m = self._lib.shf_class_lists_export(self._h, int(cls), C.c_void_p(buf.data_ptr()), n)
+        if m != n:
+            raise _lib.ShfError("class_lists_export: " + (_lib.last_error() if m < 0 else "the list changed under the export"))
+        return buf[:n].cpu().numpy()
+
+    def class_lists_finish(self, cls, method="BBOX_VOTE", nms_thresh=0.4, count=None):
+        """The merged boxes of class ``cls`` as detect() returns them: float64 (M, 5) for "BBOX_VOTE" (bbox_vote's
+        result), float32 ``dets[keep]`` rows for "NMS".  ``count``: the class's row count when the caller already has it
+        (class_lists_count), sizing the output without another read."""
+        m = {"BBOX_VOTE": 0, "NMS": 1}[method]
+        cap = max(int(self.class_lists_count()[int(cls) - 1] if count is None and 1 <= int(cls) < self.num_classes
+                      else (count or 0)), 1)
+        out = np.empty((cap, 5), dtype=np.float64)
+        n = C.c_int(0)
+        _lib.check(self._lib.shf_class_lists_finish(self._h, int(cls), m, float(nms_thresh),
+                                                    out.ctypes.data_as(C.POINTER(C.c_double)), cap, C.byref(n)),
+                   "class_lists_finish")
+        if n.value > cap:
+            raise _lib.ShfError("class_lists_finish: %d merged rows from a list of %d" % (n.value, cap))
+        return out[:n.value].copy() if m == 0 else out[:n.value].astype(np.float32)
+
     # -- diagnostics (tests) -----------------------------------------------------------
     def debug_proposal(self, scores, deltas, im_info):
         """ProposalLayer.forward on injected blobs through the HIP tail (C ABI shf_debug_proposal):

@@ -386,6 +386,7 @@ void shf_net::record_forward(bool plain, int R) {
   if (tail_layer >= 0) {
     blobs[boxes_blob].shape = {std::max(R, 1), 5};
     if (prob_blob >= 0) blobs[prob_blob].shape = {R, tail_C};
+    last_R = R;
   }
   // (tail-fused blobs too: "newer" for them means the tail workspace holds this forward's logits -- read on demand)
   for (size_t i = 0; i < blobs.size(); ++i)

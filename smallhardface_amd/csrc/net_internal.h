@@ -1,6 +1,7 @@
 // Internal declarations of the Net runtime (net_graph.cpp: build / shapes / parameters; net_forward.cpp: the layer walk
 // of one lane or a group of lanes (run_pass), Net.forward() and the profiler classes; net_detect.cpp: the fused per-image
-// detection pipeline; net_api.cpp: the rest of the C ABI of include/shf_hip.h).  One struct, four translation units (split
+// detection pipeline; net_class_lists.cpp: the per-class lists of a multi-class image; net_api.cpp: the rest of the C ABI of
+// include/shf_hip.h).  One struct, five translation units (split
 // in round 5 out of a 2 400-line net.cpp).
 #pragma once
 #include <algorithm>
@@ -14,6 +15,7 @@
 #include <set>
 
 #include "../../include/shf_hip.h"
+#include "class_lists.h"
 #include "conv_common.h"
 #include "proto_text.h"
 #include "shf_internal.h"
@@ -455,6 +457,12 @@ struct shf_net {
   int img_cap = 0, img_units = 0;
   int img_pass = 0;  // append passes since detect_begin: img_count[img_pass & 1] is the current list length
   MergeCtx merge;
+  // per-class lists of a multi-class image (net_class_lists.cpp, shf_class_lists_*): tail_C - 1 lists of cl_cap rows each in
+  // cl_dets (list c - 1 at row (c - 1) * cl_cap), their lengths in cl_len, the compaction's tile workspace, the staging of
+  // shf_debug_class_lists_add; cl_units counts the units added since begin.  Grow-only, on the head only.
+  DevBuf cl_dets, cl_len, cl_tiles, cl_stage;
+  int cl_cap = 0, cl_units = 0;
+  int last_R = -1;   // proposal rows of the last completed forward (record_forward); -1: none yet
   float cur_im_info[3] = {0, 0, 1};
   bool use_blob_im_info = true;
 

@@ -11,6 +11,9 @@ and error behaviour) on top of the pycaffe-compatible shim:
 
 plus ``detect_fused`` -- the same computation with the pyramid resident in HBM and all
 per-unit post-processing on the device (C ABI shf_detect_*), which is what bench.py times.
+``detect`` itself reads three opt-in switches from the environment at every call: ``SHF_DEVICE_LEVELS=1`` (the pyramid
+levels stay in HBM), ``SHF_GROUPED_FORWARD=1`` (an image's units as grouped forwards) and ``SHF_DEVICE_MERGE=1`` (grouped
+forwards whose outputs go into per-class device lists, cut and merged there: C ABI shf_class_lists_*, any class count).
 The reference's ``"NMS"`` branch calls a name it never imports; here it
 is wired to lib/nms's GPU semantics.
 """
@@ -168,21 +171,53 @@ def forward_net_group(nets, blobs, im_scales, flips):
     for a in range(0, n, GROUP_UNITS):
         chunk = list(range(a, min(a + GROUP_UNITS, n)))
         lanes = [nets[k - a] for k in chunk]
-        widths, dev = [], []
-        for k, net in zip(chunk, lanes):
-            # the inputs are written straight into the nets' blobs, as forward_net writes them, and forward_group runs on
-            # the blobs as they stand
-            w, data = _stage_unit(net, blobs[k], im_scales[k])
-            widths.append(w)
-            if isinstance(data, caffe.DeviceArray):
-                dev.append((net, data))
-            net.blobs['im_info'].data[...] = blobs[k]['im_info']
-        if dev:
-            caffe._load_device_group(lanes[0], [d[0] for d in dev], 'data', [d[1] for d in dev], None)
-        outs = lanes[0].forward_group(lanes)
+        widths, outs = _forward_chunk(lanes, [blobs[k] for k in chunk], [im_scales[k] for k in chunk])
         for k, net, w, blobs_out in zip(chunk, lanes, widths, outs):
             out.append(_unit_results(net, blobs_out, w, im_scales[k], flips[k], copy=True))
     return out
+
+
+def _forward_chunk(lanes, blobs, im_scales):
+    """One grouped pass: ``blobs[k]`` staged into ``lanes[k]`` as forward_net stages it, the device-resident levels loaded
+    with one launch, one ``Net.forward_group`` with the first lane as head.  Returns (level widths, forward_group's outputs)."""
+    widths, dev = [], []
+    for net, blob, im_scale in zip(lanes, blobs, im_scales):
+        # the inputs are written straight into the nets' blobs, as forward_net writes them, and forward_group runs on
+        # the blobs as they stand
+        w, data = _stage_unit(net, blob, im_scale)
+        widths.append(w)
+        if isinstance(data, caffe.DeviceArray):
+            dev.append((net, data))
+        net.blobs['im_info'].data[...] = blob['im_info']
+    if dev:
+        caffe._load_device_group(lanes[0], [d[0] for d in dev], 'data', [d[1] for d in dev], None)
+    return widths, lanes[0].forward_group(lanes)
+
+
+def _detect_device_merge(net, im_blobs, pyramid_scales, thresh, timers):
+    """detect()'s pyramid loop and class loop with the detections resident on the device (SHF_DEVICE_MERGE=1): the units
+    in forward_net_group's chunks, each chunk's outputs appended to the head's per-class lists where they sit
+    (Net.class_lists_add: flip fix, unscale, > thresh cut), every class merged from its list (Net.class_lists_finish).
+    The same cls_dets as the host loop, bit for bit."""
+    method = cfg.TEST.NMS_METHOD
+    if method not in ("BBOX_VOTE", "NMS"):
+        raise NotImplementedError("Unknown NMS method: {}".format(method))
+    chunks = group_units(len(pyramid_scales), bool(cfg.TEST.FLIP), GROUP_UNITS)
+    lanes = _group_lanes(net, min(sum(len(ch) for ch in chunks), GROUP_UNITS))
+    head = lanes[0]
+    head.class_lists_begin()
+    for ch in chunks:
+        members = lanes[:len(ch)]
+        ublobs = [{'data': im_blobs[i]['data'][..., ::-1]} if f else im_blobs[i] for i, f in ch]
+        scales = [pyramid_scales[i] for i, _ in ch]
+        widths, _ = _forward_chunk(members, ublobs, scales)
+        head.class_lists_add(members, widths, scales, [f for _, f in ch], thresh)
+    timers['detect'].toc()
+    timers['misc'].tic()
+    counts = head.class_lists_count()
+    cls_dets = [head.class_lists_finish(c + 1, method, cfg.TEST.NMS_THRESH, count=counts[c]) for c in range(len(counts))]
+    timers['misc'].toc()
+    return cls_dets
 
 
 def _group_lanes(net, n):
@@ -246,6 +281,10 @@ def detect(net, im_path, thresh=0.05, timers=None, pyramid=False, im=None):
             im_blobs = _get_image_blob_device(im, pyramid_scales, on_device=True)
         else:
             im_blobs = _get_image_blob_device(im, pyramid_scales)
+        if os.environ.get("SHF_DEVICE_MERGE") == "1" and 'boxes' in net.blobs and len(cfg.TEST.LEVEL) == 0:
+            # grouped forwards (the switch implies them) whose outputs never leave the device: per-class lists on the head
+            # net, cut and merged there.  Multi-level outputs (boxes_<level>) and TEST.LEVEL subsets keep the host merge.
+            return _detect_device_merge(net, im_blobs, pyramid_scales, thresh, timers), timers
         if os.environ.get("SHF_GROUPED_FORWARD") == "1":
             # the same units in the same order, as one grouped pass per 16 (Net.forward_group) instead of one forward each:
             # the same probs / boxes, so the same detections
