@@ -244,6 +244,8 @@ static int w4_pick_mt(const ConvArgs* as, int n, int nct) {
 // Every kernel instantiation of the split-fp16 modes, each with the profiler class its launches are booked under.  Columns:
 // NP = 3, 2, 1 fp16 products, then bf16 (one product on bf16 operands); [IN_SPLIT x NP] = the fp32-input forms, the split-input
 // forms, then bf16 (fp32 activations: no split input).
+// What each column computes, operand by operand, and which cells the bit-exact tests (tests/test_gpu_conv_modes.py) reach
+// and cannot reach: DESIGN.md, "Operand model of every mode, held bit for bit".
 // An entry's LDS size is its layout's (conv_lds_layout.h), named by the same macro arguments as the kernel; conv_lds<>
 // refuses at compile time a layout beyond the 160 KiB conv_set_lds_attributes asks for.
 #define SHF_8W1(PC, BN, DIL, KS, FUSE1, ...) \

@@ -114,7 +114,50 @@ def readout_forwards(onet):
     return -(-C // (32 if heads == 0 else 4))
 
 
-def read_fused_blob(gnet, onet, data, im_info):
+def _readout_pairs(onet):
+    heads = _readout_heads(onet)
+    pairs = [("cls_score", "bbox_pred")] if heads == 0 else [("cls_score_%d" % i, "bbox_pred_%d" % i) for i in range(heads)]
+    return heads, pairs, (8 if heads == 0 else 1), onet.params[pairs[0][0]][0].shape[1]
+
+
+def readout_set_predictors(gnet, onet, c0):
+    """One-hot predictor rows that copy channels c0 .. of the probed blob(s) into the logits (`read_fused_blob`): written
+    to `onet.params` and, `gnet` given, to its parameters (a net's lanes share them)."""
+    heads, pairs, A, C = _readout_pairs(onet)
+    for cn, bn in pairs:
+        wc = np.zeros((2 * A, C, 1, 1), np.float32)
+        wb = np.zeros((4 * A, C, 1, 1), np.float32)
+        for a in range(A):
+            ch = c0 + 4 * a
+            if ch + 3 < C:                       # (C % 128 == 0: whole groups of four)
+                wc[a, ch] = wc[A + a, ch + 1] = 1.0          # cls_score channel = cls * A + a
+                wb[4 * a, ch + 2] = wb[4 * a + 1, ch + 3] = 1.0
+        for name, wt in ((cn, wc), (bn, wb)):
+            onet.params[name][0][...] = wt
+            onet.params[name][1][...] = 0
+            if gnet is not None:
+                gnet.params[name][0].data[...] = wt
+                gnet.params[name][1].data[...] = 0
+
+
+def readout_take(net, onet, outs, c0):
+    """The channels `readout_set_predictors(.., c0)` copied, from the forwarded `net`'s predictor tops into `outs` (None:
+    allocated here); returns `outs`, one (C, h, w) array per probed blob."""
+    heads, pairs, A, C = _readout_pairs(onet)
+    for i, (cn, bn) in enumerate(pairs):
+        cs = np.array(net.blobs[cn + "_output"].data[0])
+        bb = np.array(net.blobs[bn + "_output"].data[0])
+        if outs is None:
+            outs = [np.zeros((C,) + cs.shape[1:], np.float32) for _ in pairs]
+        for a in range(A):
+            ch = c0 + 4 * a
+            if ch + 3 < C:
+                outs[i][ch], outs[i][ch + 1] = cs[a], cs[A + a]
+                outs[i][ch + 2], outs[i][ch + 3] = bb[4 * a], bb[4 * a + 1]
+    return outs
+
+
+def read_fused_blob(gnet, onet, data, im_info, mode="f16x3"):
     """What the probed blob(s) of a `mini_detector` hold after a FAST forward, exactly.
 
     After a split-fp16 forward on the fused path the intermediate blobs are recomputed by the per-layer kernels when read;
@@ -122,46 +165,22 @@ def read_fused_blob(gnet, onet, data, im_info):
     predictor rows and zero biases a logit is x * 1 + 0 * ... = x: per anchor the rows cls0, cls1, dx, dy each copy one
     channel (dw / dh stay zero: exp() in the decode cannot overflow), 32 channels per forward with the single-blob tail,
     4 per blob with the per-blob tail (exact one-hot rows there too, no random projection).  The predictors are written to
-    `onet.params` and loaded into `gnet`, which forwards in "f16x3" mode; `gnet` None forwards the oracle net instead
-    (the CPU check of this read-out).  Returns the (C, h, w) blob, or the list of them for the per-blob tail."""
-    heads = _readout_heads(onet)
+    `onet.params` and loaded into `gnet`, which forwards in conv mode `mode` (the logits kernel is fp32 arithmetic in every
+    mode: the copy is exact in the reduced modes as well); `gnet` None forwards the oracle net instead (the CPU check of
+    this read-out).  Returns the (C, h, w) blob, or the list of them for the per-blob tail."""
+    heads, pairs, A, C = _readout_pairs(onet)
     net = gnet if gnet is not None else onet
-    pairs = [("cls_score", "bbox_pred")] if heads == 0 else [("cls_score_%d" % i, "bbox_pred_%d" % i) for i in range(heads)]
-    A = 8 if heads == 0 else 1
-    C = onet.params[pairs[0][0]][0].shape[1]
     if gnet is not None:
-        gnet.set_conv_mode("f16x3")
+        gnet.set_conv_mode(mode)
     for net_ in (gnet, onet):
         if net_ is not None:
             net_.blobs['data'].reshape(*data.shape)
             net_.blobs['im_info'].reshape(*im_info.shape)
     outs = None
     for c0 in range(0, C, 4 * A):
-        for cn, bn in pairs:
-            wc = np.zeros((2 * A, C, 1, 1), np.float32)
-            wb = np.zeros((4 * A, C, 1, 1), np.float32)
-            for a in range(A):
-                ch = c0 + 4 * a
-                if ch + 3 < C:                       # (C % 128 == 0: whole groups of four)
-                    wc[a, ch] = wc[A + a, ch + 1] = 1.0          # cls_score channel = cls * A + a
-                    wb[4 * a, ch + 2] = wb[4 * a + 1, ch + 3] = 1.0
-            for name, wt in ((cn, wc), (bn, wb)):
-                onet.params[name][0][...] = wt
-                onet.params[name][1][...] = 0
-                if gnet is not None:
-                    gnet.params[name][0].data[...] = wt
-                    gnet.params[name][1].data[...] = 0
+        readout_set_predictors(gnet, onet, c0)
         net.forward(data=data, im_info=im_info)
-        for i, (cn, bn) in enumerate(pairs):
-            cs = np.array(net.blobs[cn + "_output"].data[0])
-            bb = np.array(net.blobs[bn + "_output"].data[0])
-            if outs is None:
-                outs = [np.zeros((C,) + cs.shape[1:], np.float32) for _ in pairs]
-            for a in range(A):
-                ch = c0 + 4 * a
-                if ch + 3 < C:
-                    outs[i][ch], outs[i][ch + 1] = cs[a], cs[A + a]
-                    outs[i][ch + 2], outs[i][ch + 3] = bb[4 * a], bb[4 * a + 1]
+        outs = readout_take(net, onet, outs, c0)
     return outs[0] if heads == 0 else outs
 
 
