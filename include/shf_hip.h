@@ -54,6 +54,12 @@ int shf_net_num_layers(shf_net* net);
 /* classes of the net's proposal layer, background first (proposal_layer.py:118: scores.shape[1] / A): 2 .. 8, taken from
  * the class predictors' output counts; 0 for a net without a proposal layer */
 int shf_net_num_classes(shf_net* net);
+/* proposal layers ("modules") of the net, 0 .. 4: the driver collects a net's proposals per level from the blobs named
+ * boxes_<level> / cls_prob_<level>, one pair per module (lib/test.py:67-83); a net with one module names them boxes /
+ * cls_prob.  Every module runs in Net.forward / shf_net_forward_group; the entry points that keep one device list per net
+ * (shf_detect_begin / _add_level / _add_levels, shf_class_lists_*, shf_debug_proposal, shf_debug_append) refuse a net with
+ * more than one.  0 for a net without a proposal layer */
+int shf_net_num_modules(shf_net* net);
 const char* shf_net_layer_name(shf_net* net, int i);
 const char* shf_net_layer_type(shf_net* net, int i);
 int shf_net_layer_num_params(shf_net* net, int layer);

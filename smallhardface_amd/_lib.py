@@ -75,6 +75,7 @@ def _declare(lib):
         "shf_net_output_blob": (ci, [vp, ci]),
         "shf_net_num_layers": (ci, [vp]),
         "shf_net_num_classes": (ci, [vp]),
+        "shf_net_num_modules": (ci, [vp]),
         "shf_net_layer_name": (C.c_char_p, [vp, ci]),
         "shf_net_layer_type": (C.c_char_p, [vp, ci]),
         "shf_net_layer_num_params": (ci, [vp, ci]),

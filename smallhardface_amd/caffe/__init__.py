@@ -278,6 +278,12 @@ class Net(object):
         """Classes of the proposal layer, background first (C ABI shf_net_num_classes); 0 without a proposal layer."""
         return int(self._lib.shf_net_num_classes(self._h))
 
+    @property
+    def num_modules(self):
+        """Proposal layers of the net (C ABI shf_net_num_modules): one per ``boxes_<level>`` / ``cls_prob_<level>`` pair the
+        driver collects (lib/test.py:67-83), 1 for the templates' single ``boxes`` / ``cls_prob``, 0 without one."""
+        return int(self._lib.shf_net_num_modules(self._h))
+
     def clone(self):
         """A lane: same parameter tensors, own activations / workspace / HIP stream
         (cf. Net::ShareTrainedLayersWith).  Keep ``self`` alive while the lane is used."""

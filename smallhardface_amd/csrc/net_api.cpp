@@ -155,6 +155,7 @@ int shf_net_num_outputs(shf_net* net) { return (int)net->outputs.size(); }
 int shf_net_output_blob(shf_net* net, int i) { return net->outputs[i]; }
 int shf_net_num_layers(shf_net* net) { return (int)net->layers.size(); }
 int shf_net_num_classes(shf_net* net) { return net->tail_layer >= 0 ? net->tail_C : 0; }
+int shf_net_num_modules(shf_net* net) { return (int)net->mods.size(); }
 const char* shf_net_layer_name(shf_net* net, int i) { return net->layers[i].name.c_str(); }
 const char* shf_net_layer_type(shf_net* net, int i) { return net->layers[i].type.c_str(); }
 int shf_net_layer_num_params(shf_net* net, int layer) { return (int)net->layers[layer].params.size(); }
@@ -777,11 +778,13 @@ int shf_debug_proposal(shf_net* net, const float* scores, const float* deltas, i
                        float* out_boxes5, float* out_probs, int cap, int* n_out, int* overflow) {
   API_BEGIN
   if (net->tail_layer < 0) throw std::runtime_error("net has no proposal layer");
+  refuse_multimodule("debug_proposal", net);
   if (h < 1 || w < 1) throw std::runtime_error("debug_proposal: bad map size");
   // (any (h, w): the layer itself does not care that the real graph only produces even head maps)
-  const int A = net->tail_A, NC = net->tail_C;
+  TailModule& M = net->mods[0];
+  const int A = M.A, NC = net->tail_C;
   const size_t K = (size_t)h * w;
-  net->ensure_tail_workspace(K * A);
+  net->ensure_tail_workspace(M, K * A);
   DevBuf ds, dd;
   ds.ensure(K * NC * A * 4);
   dd.ensure(K * 4 * A * 4);
@@ -789,20 +792,20 @@ int shf_debug_proposal(shf_net* net, const float* scores, const float* deltas, i
   HIP_THROW(hipMemcpyAsync(ds.p, scores, K * NC * A * 4, hipMemcpyHostToDevice, st));
   HIP_THROW(hipMemcpyAsync(dd.p, deltas, K * 4 * A * 4, hipMemcpyHostToDevice, st));
   TailArgs t;
-  t.A = A; t.C = NC; t.heads = net->tail_heads; t.Cf = net->tail_Cf;
+  t.A = A; t.C = NC; t.heads = M.heads; t.Cf = M.Cf;
   t.h = h; t.w = w;
-  for (int i = 0; i < A * 4; ++i) t.anchors[i] = (float)net->anchors[i];
-  for (int i = 0; i < A; ++i) t.sub_stride[i] = net->sub_stride[i];
-  t.feat_stride = net->feat_stride;
+  for (int i = 0; i < A * 4; ++i) t.anchors[i] = (float)M.anchors[i];
+  for (int i = 0; i < A; ++i) t.sub_stride[i] = M.sub_stride[i];
+  t.feat_stride = M.feat_stride;
   t.im_h = im_info3[0]; t.im_w = im_info3[1]; t.im_scale = im_info3[2];
   t.min_size = net->min_size; t.score_thresh = net->score_thresh; t.pre_nms_topN = net->pre_nms_topN;
   t.probs_given = 1;
-  float* boxes = (float*)net->blobs[net->boxes_blob].dev.p;
-  float* probs = net->prob_blob >= 0 ? (float*)net->blobs[net->prob_blob].dev.p : (float*)net->tw_rec.p;
-  CHECK_RC(launch_tail_inject(t, net->tw, (const float*)ds.p, (const float*)dd.p, st));
-  CHECK_RC(launch_tail(t, net->tw, boxes, probs, st, nullptr, 2));
+  float* boxes = (float*)net->blobs[M.boxes_blob].dev.p;
+  float* probs = net->probs_out();
+  CHECK_RC(launch_tail_inject(t, M.tw, (const float*)ds.p, (const float*)dd.p, st));
+  CHECK_RC(launch_tail(t, M.tw, boxes, probs, st, nullptr, 2));
   int cnt[8];
-  HIP_THROW(hipMemcpyAsync(cnt, net->tw.counters, sizeof(cnt), hipMemcpyDeviceToHost, st));
+  HIP_THROW(hipMemcpyAsync(cnt, M.tw.counters, sizeof(cnt), hipMemcpyDeviceToHost, st));
   HIP_THROW(hipStreamSynchronize(st));
   const int R = cnt[2];
   if (overflow) *overflow = cnt[1];
@@ -811,8 +814,8 @@ int shf_debug_proposal(shf_net* net, const float* scores, const float* deltas, i
   if (n_out) *n_out = R;
   HIP_THROW(hipMemcpy(out_boxes5, boxes, (size_t)std::min(rows_b, cap) * 5 * 4, hipMemcpyDeviceToHost));
   if (R > 0) HIP_THROW(hipMemcpy(out_probs, probs, (size_t)std::min(R, cap) * NC * 4, hipMemcpyDeviceToHost));
-  net->blobs[net->boxes_blob].shape = {rows_b, 5};
-  if (net->prob_blob >= 0) net->blobs[net->prob_blob].shape = {R, NC};
+  net->blobs[M.boxes_blob].shape = {rows_b, 5};
+  if (M.prob_blob >= 0) net->blobs[M.prob_blob].shape = {R, NC};
   return 0;
   API_END(-1)
 }
@@ -823,19 +826,21 @@ int shf_debug_append(shf_net* net, const float* boxes5, const float* probs2, int
                      int flip, float thresh) {
   API_BEGIN
   if (net->tail_layer < 0) throw std::runtime_error("net has no proposal layer");
+  refuse_multimodule("debug_append", net);
   refuse_multiclass_lists("debug_append", net);
   if (R < 0) throw std::runtime_error("debug_append: R < 0");
-  net->tw_counters.ensure(64);
-  net->tw.counters = (int*)net->tw_counters.p;
-  Blob& bb = net->blobs[net->boxes_blob];
+  TailModule& M = net->mods[0];
+  M.tw_counters.ensure(64);
+  M.tw.counters = (int*)M.tw_counters.p;
+  Blob& bb = net->blobs[M.boxes_blob];
   bb.dev.ensure((size_t)std::max(R, 1) * 5 * 4);
   float* probs;
-  if (net->prob_blob >= 0) {
-    net->blobs[net->prob_blob].dev.ensure((size_t)std::max(R, 1) * 2 * 4);
-    probs = (float*)net->blobs[net->prob_blob].dev.p;
+  if (M.prob_blob >= 0) {
+    net->blobs[M.prob_blob].dev.ensure((size_t)std::max(R, 1) * 2 * 4);
+    probs = (float*)net->blobs[M.prob_blob].dev.p;
   } else {
-    net->tw_rec.ensure((size_t)std::max(R, 1) * 2 * 4);
-    probs = (float*)net->tw_rec.p;
+    M.tw_rec.ensure((size_t)std::max(R, 1) * 2 * 4);
+    probs = (float*)M.tw_rec.p;
   }
   hipStream_t st = net->stream;
   if (R > 0) {
@@ -843,7 +848,7 @@ int shf_debug_append(shf_net* net, const float* boxes5, const float* probs2, int
     HIP_THROW(hipMemcpyAsync(probs, probs2, (size_t)R * 2 * 4, hipMemcpyHostToDevice, st));
   }
   const int cnt[8] = {R, 0, R, 0, 0, 0, 0, 0};  // C candidates (all kept: topN is raised below), published R
-  HIP_THROW(hipMemcpyAsync(net->tw.counters, cnt, sizeof(cnt), hipMemcpyHostToDevice, st));
+  HIP_THROW(hipMemcpyAsync(M.tw.counters, cnt, sizeof(cnt), hipMemcpyHostToDevice, st));
   HIP_THROW(hipStreamSynchronize(st));
   Restore<int> topN(net->pre_nms_topN);
   net->pre_nms_topN = std::max(R, 1);  // append_unit sizes its launch and the list growth from it

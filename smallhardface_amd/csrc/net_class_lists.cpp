@@ -11,6 +11,7 @@ void check_head(const char* who, const shf_net* net) {
   const std::string w = std::string(who) + ": ";
   if (!net) throw std::runtime_error(w + "NULL net");
   if (net->tail_layer < 0) throw std::runtime_error(w + "net has no proposal layer");
+  refuse_multimodule(who, net);
   if (net->pipelined)
     throw std::runtime_error(w + "the head has shf_net_set_pipeline enabled: its stream belongs to the image pipeline");
 }
@@ -37,7 +38,7 @@ void ensure_len(shf_net* net) {
 void ensure_lists(shf_net* net, int units_after) {
   ensure_len(net);
   const int nl = net->tail_C - 1;
-  const long long rmax = std::max<long long>(1, net->pre_nms_topN > 0 ? net->pre_nms_topN : (long long)net->tw.cap_anchors);
+  const long long rmax = std::max<long long>(1, net->pre_nms_topN > 0 ? net->pre_nms_topN : (long long)net->mods[0].tw.cap_anchors);
   const long long need = units_after * rmax;
   if (need <= net->cl_cap) return;
   const long long ncap = std::max(need, std::max<long long>(2LL * net->cl_cap, 16 * rmax));
@@ -101,12 +102,13 @@ int shf_class_lists_add(shf_net* net, int n, shf_net** members, const int* im_w,
     if (s->tail_layer < 0) throw std::runtime_error(w + " has no proposal layer");
     if (s->tail_C != net->tail_C)
       throw std::runtime_error(w + " has " + std::to_string(s->tail_C) + " classes, the head " + std::to_string(net->tail_C));
-    if (!s->forwarded || s->last_R < 0) throw std::runtime_error(w + " has not completed a forward");
+    if (s->mods.size() != 1) refuse_multimodule(who, s);
+    if (!s->forwarded || s->mods[0].last_R < 0) throw std::runtime_error(w + " has not completed a forward");
   }
   ClassListsUnit us[kClassListsMaxUnits];
   for (int m = 0; m < n; ++m) {
     shf_net* s = members[m];
-    us[m] = {(const float*)s->blobs[s->boxes_blob].dev.p, s->probs_out(), s->last_R, (float)im_w[m], im_scale[m],
+    us[m] = {(const float*)s->blobs[s->mods[0].boxes_blob].dev.p, s->probs_out(), s->mods[0].last_R, (float)im_w[m], im_scale[m],
              flip[m] ? 1 : 0};
   }
   add_units(net, us, n, thresh);

@@ -28,11 +28,19 @@ void refuse_multiclass_lists(const char* who, const shf_net* net) {
                              "(use Net.forward / forward_group and merge per class)");
 }
 
+void refuse_multimodule(const char* who, const shf_net* net) {
+  if (net->mods.size() > 1)
+    throw std::runtime_error(std::string(who) + ": the net has " + std::to_string(net->mods.size()) +
+                             " proposal modules; this entry point keeps one device list per net, fed by one proposal "
+                             "layer (use Net.forward / forward_group and merge the levels on the host)");
+}
+
 extern "C" {
 
 int shf_detect_begin(shf_net* net) {
   API_BEGIN
   if (net->tail_layer < 0) throw std::runtime_error("net has no proposal layer");
+  refuse_multimodule("detect_begin", net);
   refuse_multiclass_lists("detect_begin", net);
   if (!net->pipelined) HIP_THROW(hipMemsetAsync(net->range_flag.p, 0, 4, net->stream));
   net->img_count.ensure(64);
@@ -63,7 +71,7 @@ void shf_net::prepare_unit(const float* data, int data_on_device, int H, int W, 
 }
 
 void shf_net::ensure_img_cap(int units_after) {
-  const int rmax = pre_nms_topN > 0 ? pre_nms_topN : (int)tw.cap_anchors;
+  const int rmax = pre_nms_topN > 0 ? pre_nms_topN : (int)mods[0].tw.cap_anchors;
   const int need = units_after * rmax;
   if (need <= img_cap) return;
   // grow geometrically; keep what is already gathered
@@ -103,10 +111,11 @@ void append_units(shf_net* net, shf_net* const* srcs, int n, const int* im_w, co
       dst->img_pass = 1;  // the kernel writes count[0] = 0, count[1] = rows
     }
     AppendUnit& u = us[m];
-    u.boxes5 = (const float*)src->blobs[src->boxes_blob].dev.p;
+    const TailModule& M = src->mods[0];   // (the callers refuse nets with more than one module)
+    u.boxes5 = (const float*)src->blobs[M.boxes_blob].dev.p;
     u.probs2 = src->probs_out();
-    u.counters = src->tw.counters;
-    u.r_max = src->pre_nms_topN > 0 ? src->pre_nms_topN : (int)src->tw.cap_anchors;
+    u.counters = M.tw.counters;
+    u.r_max = src->pre_nms_topN > 0 ? src->pre_nms_topN : (int)M.tw.cap_anchors;
     u.im_w = (float)im_w[m]; u.im_scale = im_scale[m]; u.flip = flip[m];
     u.dets5 = (float*)dst->img_dets.p;
     u.keys = (unsigned long long*)dst->img_keys.p;
@@ -153,6 +162,7 @@ int shf_make_pyramid_level(shf_net* net, const uint8_t* im_bgr_dev, int im_h, in
 int shf_detect_add_level(shf_net* net, const float* data, int data_on_device, int H, int W, int im_h, int im_w,
                          float im_scale, int flip, float thresh) {
   API_BEGIN
+  refuse_multimodule("detect_add_level", net);
   refuse_multiclass_lists("detect_add_level", net);
   net->prepare_unit(data, data_on_device, H, W, net->stream);
   const float im_info[3] = {(float)im_h, (float)im_w, im_scale};
@@ -167,6 +177,7 @@ int shf_detect_add_levels(shf_net* net, int n, shf_net** members, const float* c
                           const int* H, const int* W, const int* im_h, const int* im_w, const float* im_scale,
                           const int* flip, float thresh, int per_member_lists) {
   API_BEGIN
+  refuse_multimodule("detect_add_levels", net);
   refuse_multiclass_lists("detect_add_levels", net);
   if (n < 1 || n > kMaxGroup) throw std::runtime_error("detect_add_levels: 1..16 units per group");
   for (int m = 0; m < n; ++m) {
@@ -184,8 +195,7 @@ int shf_detect_add_levels(shf_net* net, int n, shf_net** members, const float* c
   int first_feat_writer = (int)net->layers.size();
   for (size_t li = 0; li < net->layers.size(); ++li)
     for (int t : net->layers[li].tops)
-      for (int f : net->tail_feat_blobs)
-        if (t == f && (int)li < first_feat_writer) first_feat_writer = (int)li;
+      if (net->is_feat_blob(t) && (int)li < first_feat_writer) first_feat_writer = (int)li;
   // Pipelined heads (shf_net_set_pipeline): the convolutions and logits kernels of consecutive images share ONE
   // in-order stream, so no cross-stream hand-over is needed for the activation buffers; only the rest of the tails,
   // the appends and the merge run on this head's own stream, beside the next image's convolutions.

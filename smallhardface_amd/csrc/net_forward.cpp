@@ -48,25 +48,27 @@ static double conv_flops(const Layer& L, const std::vector<int>& in, const std::
 
 // the proposal stage's arguments for the current shapes (also sizes the workspace: pre_nms_topN is shared with the
 // other lanes and may have grown)
-TailArgs shf_net::tail_args(float im_h, float im_w, float im_scale, bool materialize) {
-  if (tail_w_dirty || tail_gen != *wgen) build_tail_weights();
+TailArgs shf_net::tail_args(int module, float im_h, float im_w, float im_scale, bool materialize) {
+  TailModule& M = mods[module];
+  if (M.w_dirty || M.gen != *wgen) build_tail_weights(M);
   TailArgs t;
-  t.A = tail_A; t.C = tail_C; t.heads = tail_heads; t.Cf = tail_Cf;
-  for (int i = 0; i < tail_heads; ++i) t.feat[i] = view_of(tail_feat_blobs[i]);
-  t.wcls[0] = (const float*)tail_W.p;
-  t.bcls[0] = (const float*)tail_b.p;
-  t.h = blobs[tail_feat_blobs[0]].shape[2];
-  t.w = blobs[tail_feat_blobs[0]].shape[3];
-  for (int i = 0; i < tail_A * 4; ++i) t.anchors[i] = (float)anchors[i];
-  for (int i = 0; i < tail_A; ++i) t.sub_stride[i] = sub_stride[i];
-  t.feat_stride = feat_stride;
+  t.module = module;
+  t.A = M.A; t.C = tail_C; t.heads = M.heads; t.Cf = M.Cf;
+  for (int i = 0; i < M.heads; ++i) t.feat[i] = view_of(M.feat_blobs[i]);
+  t.wcls[0] = (const float*)M.W.p;
+  t.bcls[0] = (const float*)M.b.p;
+  t.h = blobs[M.feat_blobs[0]].shape[2];
+  t.w = blobs[M.feat_blobs[0]].shape[3];
+  for (int i = 0; i < M.A * 4; ++i) t.anchors[i] = (float)M.anchors[i];
+  for (int i = 0; i < M.A; ++i) t.sub_stride[i] = M.sub_stride[i];
+  t.feat_stride = M.feat_stride;
   t.im_h = im_h; t.im_w = im_w; t.im_scale = im_scale;
   t.min_size = min_size; t.score_thresh = score_thresh; t.pre_nms_topN = pre_nms_topN;
   if (materialize) {
-    t.cls_prob_reshape_nchw = (float*)blobs[tail_cls_blob].dev.p;
-    t.bbox_pred_nchw = (float*)blobs[tail_box_blob].dev.p;
+    t.cls_prob_reshape_nchw = (float*)blobs[M.cls_blob].dev.p;
+    t.bbox_pred_nchw = (float*)blobs[M.box_blob].dev.p;
   }
-  ensure_tail_workspace((size_t)t.h * t.w * tail_A);
+  ensure_tail_workspace(M, (size_t)t.h * t.w * M.A);
   return t;
 }
 
@@ -139,13 +141,19 @@ ConvArgs shf_net::conv_args(int li, bool fused, int* flag) const {
 // the profiler's flops / bytes of layer li on this lane's unit, added to `flops` / `bytes`.  `heads` = 3: the three
 // shared-weight heads of one launch; a conv that absorbs its first-layer producer is credited with that layer's flops too.
 // A conv's weights are read once per launch, however many lanes it covers: run_pass counts them.
+void shf_net::tail_cost(int module, double& flops, double& bytes) const {
+  const TailModule& M = mods[module];
+  const Blob& f = blobs[M.feat_blobs[0]];
+  const double K = (double)f.shape[2] * f.shape[3];
+  flops += 2.0 * K * M.A * (tail_C + 4) * M.Cf;
+  bytes += 4.0 * K * (M.heads * M.Cf + M.A * 3 * (tail_C + 4));
+}
+
 void shf_net::add_cost(int li, bool fused, int heads, double& flops, double& bytes) const {
   const Layer& L = layers[li];
-  if (L.op == OP_TAIL) {
-    const Blob& f = blobs[tail_feat_blobs[0]];
-    const double K = (double)f.shape[2] * f.shape[3];
-    flops += 2.0 * K * tail_A * (tail_C + 4) * tail_Cf;
-    bytes += 4.0 * K * (tail_heads * tail_Cf + tail_A * 3 * (tail_C + 4));
+  if (L.op == OP_TAIL) {   // (booked at the last proposal layer, where the pass issues them: the tails of every module)
+    if (li == tail_layer)
+      for (int j = 0; j < (int)mods.size(); ++j) tail_cost(j, flops, bytes);
     return;
   }
   const Blob& ib = blobs[L.bottoms[0]];
@@ -157,6 +165,111 @@ void shf_net::add_cost(int li, bool fused, int heads, double& flops, double& byt
   if (absorbs_first(li, fused)) {
     const Layer& F = layers[L.first_src];
     flops += conv_flops(F, blobs[F.bottoms[0]].shape, blobs[F.tops[0]].shape);
+  }
+}
+
+// The tails of a pass: every (unit, module) pair is one ENTRY of the grouped tail kernels (tail.hip), unit-major, and the
+// entries go out as launch sequences of at most 16 (reset, logits, decode, sort stages, gather: one launch per stage and
+// sequence) -- a single forward() of a net with up to four modules is always one sequence, as many launches as one module
+// takes.  Called once per pass, at the LAST proposal layer of the walk: the feature maps of the earlier modules stay live
+// until then (every blob owns its buffer, nothing is recycled).
+//
+// The reset kernel also zeroes each lane's activation-exponent slots for the next pass (TailWork::amax, carried by the
+// lane's first module's entry alone: once per lane and pass).  It must run behind the last convolution of the walk, since
+// a module's convolutions read the slots that the trunk published -- which is why the tails do not go out module by
+// module at each proposal layer's own position.  What orders it there:
+//   TAIL_LANE      the walk's layers and the lane's sequence share ONE in-order stream (p.s): the reset is enqueued after
+//                  every convolution.  ev_logits is recorded behind the logits kernel, hence behind the reset: a later
+//                  pass that waits for logits_done finds the slots zeroed.
+//   TAIL_GROUP     the same stream order, all sequences on p.s; no events.
+//   TAIL_HANDOVER  phase 1 (reset + logits) of every sequence is enqueued on the layers' stream p.s behind the last
+//                  convolution; ev_convs is recorded on p.s AFTER phase 1, and it is the only thing the successor head's
+//                  early start waits for before its first convolutions publish into the slots.  Phase 2 runs on the
+//                  head's stream, which waits for ev_convs when it is not p.s, and touches the tail workspaces only.
+static void run_tails(const Pass& p, bool f64) {
+  if (p.tail == TAIL_NONE) return;
+  shf_net& h = *p.head;
+  const int nm = (int)p.u[0].lane->mods.size(), ne = p.n * nm;
+  std::vector<TailArgs> t(ne);
+  std::vector<TailWork*> tws(ne);
+  std::vector<float*> boxes(ne), probs(ne);
+  for (int m = 0; m < p.n; ++m) {
+    shf_net& ln = *p.u[m].lane;
+    for (int j = 0; j < nm; ++j) {
+      const int e = m * nm + j;
+      t[e] = ln.tail_args(j, p.u[m].im_h, p.u[m].im_w, p.u[m].im_scale, p.materialize);
+      t[e].f64 = f64 ? 1 : 0;
+      tws[e] = &ln.mods[j].tw;
+      boxes[e] = (float*)ln.blobs[ln.mods[j].boxes_blob].dev.p;
+      probs[e] = ln.probs_out(j);
+    }
+  }
+  // the profiler's flops / bytes of entries e0 .. e1 - 1
+  auto cost = [&](int e0, int e1) {
+    double fl = 0, by = 0;
+    for (int e = e0; e < e1; ++e) p.u[e / nm].lane->tail_cost(e % nm, fl, by);
+    return std::make_pair(fl, by);
+  };
+  // one launch sequence over entries e0 .. e1 - 1 (launch_tail_group's phases)
+  auto sequence = [&](int e0, int e1, hipStream_t s, hipEvent_t after_logits, int phase) {
+    CHECK_RC(launch_tail_group(&t[e0], &tws[e0], &boxes[e0], &probs[e0], e1 - e0, s, after_logits, phase));
+  };
+  if (p.tail == TAIL_LANE) {   // per lane: its modules as one sequence
+    for (int m = 0; m < p.n; ++m) {
+      shf_net& ln = *p.u[m].lane;
+      const auto c = cost(m * nm, (m + 1) * nm);
+      ProfScope ps(h.prof, p.s, PC_TAIL, c.first, c.second);
+      if (p.fused && !ln.ev_logits) HIP_THROW(hipEventCreateWithFlags(&ln.ev_logits, hipEventDisableTiming));
+      sequence(m * nm, (m + 1) * nm, p.s, p.fused ? ln.ev_logits : nullptr, 0);
+      if (p.fused) { ln.logits_done = ln.ev_logits; ln.logits_keep.reset(); }
+    }
+    return;
+  }
+  // the grouped steps: the lanes hold identical copies of a module's combined weights, one launch reads the first lane's
+  for (int e = nm; e < ne; ++e) t[e].wcls[0] = t[e % nm].wcls[0], t[e].bcls[0] = t[e % nm].bcls[0];
+  if (p.tail == TAIL_GROUP) {   // Net.forward() of a group: ONE launch per stage and sequence, all on the pass's stream
+    for (int e0 = 0; e0 < ne; e0 += kMaxGroup) {
+      const int e1 = std::min(ne, e0 + kMaxGroup);
+      const auto c = cost(e0, e1);
+      ProfScope ps(h.prof, p.s, PC_TAIL, c.first, c.second);
+      sequence(e0, e1, p.s, nullptr, 0);
+    }
+    return;
+  }
+  // TAIL_HANDOVER: ~15 launches per image instead of ~100.  Phase 1 (reset + logits) is what reads the feature maps and
+  // runs on the layers' stream; phase 2 works on the lanes' tail workspaces only and runs on the head's stream.
+  if (!h.ev_convs) {
+    h.ev_convs_own = std::make_shared<SharedEvent>();
+    HIP_THROW(hipEventCreateWithFlags(&h.ev_convs_own->e, hipEventDisableTiming));
+    h.ev_convs = h.ev_convs_own->e;
+  }
+  // the lanes' tail workspaces were last used by the predecessor head's tails (its own stream)
+  if (h.pred && h.pred->ev_mark) HIP_THROW(hipStreamWaitEvent(p.s, h.pred->ev_mark, 0));
+  for (int e0 = 0; e0 < ne; e0 += kMaxGroup) {
+    const int e1 = std::min(ne, e0 + kMaxGroup);
+    const auto c = cost(e0, e1);
+    ProfScope ps(h.prof, p.s, PC_TAIL, c.first, c.second);
+    sequence(e0, e1, p.s, nullptr, 1);
+  }
+  // recorded AFTER phase 1: its reset kernel zeroes the lanes' activation-exponent slots, which the successor head's
+  // first convolutions (an early start waits for this event only) publish into and read
+  HIP_THROW(hipEventRecord(h.ev_convs, p.s));
+  // a pipelined head's layers ran on the shared conv stream: the feature maps are consumed and ev_convs is every
+  // lane's hand-over mark; otherwise each lane gets its own, for passes issued from another head without a pipeline
+  const bool shared = p.s != h.stream;
+  if (shared) HIP_THROW(hipStreamWaitEvent(h.stream, h.ev_convs, 0));
+  for (int m = 0; m < p.n; ++m) {
+    shf_net& ln = *p.u[m].lane;
+    if (!shared) {
+      if (!ln.ev_logits) HIP_THROW(hipEventCreateWithFlags(&ln.ev_logits, hipEventDisableTiming));
+      HIP_THROW(hipEventRecord(ln.ev_logits, h.stream));
+    }
+    ln.logits_done = shared ? h.ev_convs : ln.ev_logits;
+    ln.logits_keep = shared ? h.ev_convs_own : nullptr;
+  }
+  for (int e0 = 0; e0 < ne; e0 += kMaxGroup) {
+    ProfScope ps(h.prof, h.stream, PC_TAIL, 0, 0);
+    sequence(e0, std::min(ne, e0 + kMaxGroup), h.stream, nullptr, 2);
   }
 }
 
@@ -258,75 +371,9 @@ void run_pass(const Pass& p) {
         }
         break;
       }
-      case OP_TAIL: {
-        if (p.tail == TAIL_NONE) break;
-        TailArgs t[kMaxGroup];
-        TailWork* tws[kMaxGroup];
-        float *boxes[kMaxGroup], *probs[kMaxGroup];
-        for (int m = 0; m < p.n; ++m) {
-          shf_net& ln = *p.u[m].lane;
-          t[m] = ln.tail_args(p.u[m].im_h, p.u[m].im_w, p.u[m].im_scale, p.materialize);
-          t[m].f64 = f64 ? 1 : 0;
-          tws[m] = &ln.tw;
-          boxes[m] = (float*)ln.blobs[ln.boxes_blob].dev.p;
-          probs[m] = ln.probs_out();
-        }
-        if (p.tail == TAIL_LANE) {
-          for (int m = 0; m < p.n; ++m) {
-            shf_net& ln = *p.u[m].lane;
-            const auto c = cost(li, m, m + 1, 1);
-            ProfScope ps(h.prof, p.s, PC_TAIL, c.first, c.second);
-            if (p.fused && !ln.ev_logits) HIP_THROW(hipEventCreateWithFlags(&ln.ev_logits, hipEventDisableTiming));
-            CHECK_RC(launch_tail(t[m], ln.tw, boxes[m], probs[m], p.s, p.fused ? ln.ev_logits : nullptr, 0));
-            if (p.fused) { ln.logits_done = ln.ev_logits; ln.logits_keep.reset(); }
-          }
-          break;
-        }
-        if (p.tail == TAIL_GROUP) {   // Net.forward() of a group: the tails as ONE launch per stage, all on the pass's stream
-          for (int m = 1; m < p.n; ++m) t[m].wcls[0] = t[0].wcls[0], t[m].bcls[0] = t[0].bcls[0];  // lanes hold identical copies
-          const auto c = cost(li, 0, p.n, 1);
-          ProfScope ps(h.prof, p.s, PC_TAIL, c.first, c.second);
-          CHECK_RC(launch_tail_group(t, tws, boxes, probs, p.n, p.s, nullptr, 0));
-          break;
-        }
-        // TAIL_HANDOVER: the tails of all units as ONE launch per stage (counters reset, logits, decode, sort stages,
-        // gather): ~15 launches per image instead of ~100.  Phase 1 (reset + logits) is what reads the feature maps and
-        // runs on the layers' stream; phase 2 works on the lanes' tail workspaces only and runs on the head's stream.
-        for (int m = 1; m < p.n; ++m) t[m].wcls[0] = t[0].wcls[0], t[m].bcls[0] = t[0].bcls[0];  // lanes hold identical copies
-        if (!h.ev_convs) {
-          h.ev_convs_own = std::make_shared<SharedEvent>();
-          HIP_THROW(hipEventCreateWithFlags(&h.ev_convs_own->e, hipEventDisableTiming));
-          h.ev_convs = h.ev_convs_own->e;
-        }
-        // the lanes' tail workspaces were last used by the predecessor head's tails (its own stream)
-        if (h.pred && h.pred->ev_mark) HIP_THROW(hipStreamWaitEvent(p.s, h.pred->ev_mark, 0));
-        {
-          const auto c = cost(li, 0, p.n, 1);
-          ProfScope ps(h.prof, p.s, PC_TAIL, c.first, c.second);
-          CHECK_RC(launch_tail_group(t, tws, boxes, probs, p.n, p.s, nullptr, 1));
-        }
-        // recorded AFTER phase 1: its reset kernel zeroes the lanes' activation-exponent slots, which the successor head's
-        // first convolutions (an early start waits for this event only) publish into and read
-        HIP_THROW(hipEventRecord(h.ev_convs, p.s));
-        // a pipelined head's layers ran on the shared conv stream: the feature maps are consumed and ev_convs is every
-        // lane's hand-over mark; otherwise each lane gets its own, for passes issued from another head without a pipeline
-        const bool shared = p.s != h.stream;
-        if (shared) HIP_THROW(hipStreamWaitEvent(h.stream, h.ev_convs, 0));
-        for (int m = 0; m < p.n; ++m) {
-          shf_net& ln = *p.u[m].lane;
-          if (!shared) {
-            if (!ln.ev_logits) HIP_THROW(hipEventCreateWithFlags(&ln.ev_logits, hipEventDisableTiming));
-            HIP_THROW(hipEventRecord(ln.ev_logits, h.stream));
-          }
-          ln.logits_done = shared ? h.ev_convs : ln.ev_logits;
-          ln.logits_keep = shared ? h.ev_convs_own : nullptr;
-        }
-        {
-          ProfScope ps(h.prof, h.stream, PC_TAIL, 0, 0);
-          CHECK_RC(launch_tail_group(t, tws, boxes, probs, p.n, h.stream, nullptr, 2));
-        }
+      case OP_TAIL:
+        if (li == n0.tail_layer) run_tails(p, f64);
         break;
-      }
     }
   }
 }
@@ -348,7 +395,7 @@ bool shf_net::forward_fast_eligible() const {
   static const bool knob = !(getenv("SHF_FORWARD_FAST") && atoi(getenv("SHF_FORWARD_FAST")) == 0);
   if (!knob || !split_mode() || tail_layer < 0 || data_blob < 0) return false;
   for (int o : outputs)
-    if (o != boxes_blob && o != prob_blob) return false;
+    if (module_of_output(o) < 0) return false;
   return true;
 }
 
@@ -381,12 +428,13 @@ void shf_net::stage_forward(hipStream_t st, Prof& pf) {
 }
 
 // ... and what the forward left in it: `plain` -- the per-layer kernels ran, every blob is materialised; R proposal rows
-void shf_net::record_forward(bool plain, int R) {
+void shf_net::record_forward(bool plain, const int* R) {
   plain_stale = !plain;
-  if (tail_layer >= 0) {
-    blobs[boxes_blob].shape = {std::max(R, 1), 5};
-    if (prob_blob >= 0) blobs[prob_blob].shape = {R, tail_C};
-    last_R = R;
+  for (size_t j = 0; j < mods.size(); ++j) {
+    TailModule& M = mods[j];
+    blobs[M.boxes_blob].shape = {std::max(R[j], 1), 5};
+    if (M.prob_blob >= 0) blobs[M.prob_blob].shape = {R[j], tail_C};
+    M.last_R = R[j];
   }
   // (tail-fused blobs too: "newer" for them means the tail workspace holds this forward's logits -- read on demand)
   for (size_t i = 0; i < blobs.size(); ++i)
@@ -414,21 +462,22 @@ static void forward_members(shf_net* head, int n, shf_net* const* members, TailS
     p.u[m] = {&ln, ln.last_im_info[0], ln.last_im_info[1], ln.last_im_info[2]};
   }
   const bool fast = head->forward_fast_eligible(), has_tail = head->tail_layer >= 0, split = head->split_mode();
-  int cnt[kMaxGroup][8] = {{0}}, flag = 0;
+  const int nm = (int)head->mods.size();
+  int cnt[kMaxGroup][kMaxModules][8] = {{{0}}}, flag = 0;
   auto run = [&](bool fused) {
     for (int m = 0; m < n; ++m) members[m]->reset_amax(st);
     p.fused = fused;
     run_pass(p);
   };
   auto copy_counters = [&]() {
-    if (has_tail)
-      for (int m = 0; m < n; ++m)
-        HIP_THROW(hipMemcpyAsync(cnt[m], members[m]->tw.counters, sizeof(cnt[m]), hipMemcpyDeviceToHost, st));
+    for (int m = 0; m < n; ++m)
+      for (int j = 0; j < nm; ++j)
+        HIP_THROW(hipMemcpyAsync(cnt[m][j], members[m]->mods[j].tw.counters, sizeof(cnt[m][j]), hipMemcpyDeviceToHost, st));
   };
   if (split) HIP_THROW(hipMemsetAsync(head->range_flag.p, 0, 4, st));
   run(fast);
   {
-    ProfScope ps(head->prof, st, PC_D2H, 0, (double)n * sizeof(cnt[0]) + 4);
+    ProfScope ps(head->prof, st, PC_D2H, 0, (double)n * nm * sizeof(cnt[0][0]) + 4);
     copy_counters();
     if (split) HIP_THROW(hipMemcpyAsync(&flag, head->range_flag.p, 4, hipMemcpyDeviceToHost, st));
   }
@@ -446,7 +495,11 @@ static void forward_members(shf_net* head, int n, shf_net* const* members, TailS
     HIP_THROW(hipStreamSynchronize(st));
     plain = true;
   }
-  for (int m = 0; m < n; ++m) members[m]->record_forward(plain, cnt[m][2]);
+  for (int m = 0; m < n; ++m) {
+    int R[kMaxModules] = {0};
+    for (int j = 0; j < nm; ++j) R[j] = cnt[m][j][2];
+    members[m]->record_forward(plain, R);
+  }
   if (!mirror_outputs || !has_tail) return;
   // the proposal outputs' host mirrors, now that the counts are known: every member's rows behind ONE synchronisation
   // (Blob.data of each would copy and synchronise on its own: 2 n round trips)
@@ -454,20 +507,23 @@ static void forward_members(shf_net* head, int n, shf_net* const* members, TailS
     ProfScope ps(head->prof, st, PC_D2H, 0, 0);
     for (int m = 0; m < n; ++m) {
       shf_net& ln = *members[m];
-      for (int bi : {ln.boxes_blob, ln.prob_blob}) {
-        if (bi < 0) continue;
-        Blob& b = ln.blobs[bi];
-        const size_t c = b.count();
-        b.host.ensure(std::max<size_t>(c, 1) * 4);
-        if (c > 0) HIP_THROW(hipMemcpyAsync(b.host.p, b.dev.p, c * 4, hipMemcpyDeviceToHost, st));
-      }
+      for (const TailModule& M : ln.mods)
+        for (int bi : {M.boxes_blob, M.prob_blob}) {
+          if (bi < 0) continue;
+          Blob& b = ln.blobs[bi];
+          const size_t c = b.count();
+          b.host.ensure(std::max<size_t>(c, 1) * 4);
+          if (c > 0) HIP_THROW(hipMemcpyAsync(b.host.p, b.dev.p, c * 4, hipMemcpyDeviceToHost, st));
+        }
     }
   }
   HIP_THROW(hipStreamSynchronize(st));
   for (int m = 0; m < n; ++m) {
     shf_net& ln = *members[m];
-    ln.blobs[ln.boxes_blob].dev_newer = false;
-    if (ln.prob_blob >= 0) ln.blobs[ln.prob_blob].dev_newer = false;
+    for (const TailModule& M : ln.mods) {
+      ln.blobs[M.boxes_blob].dev_newer = false;
+      if (M.prob_blob >= 0) ln.blobs[M.prob_blob].dev_newer = false;
+    }
   }
 }
 
@@ -527,22 +583,23 @@ void shf_net::materialize_fused(int bi) {
   const size_t n = b.count();
   b.host.ensure(std::max<size_t>(n, 1) * 4);
   if (!b.dev_newer || n == 0) return;          // (never forwarded: zeros, like a Caffe blob before its first forward)
-  const int A = tail_A, NC = tail_C, NO = tail_C + 4;
-  const int h = blobs[tail_feat_blobs[0]].shape[2], w = blobs[tail_feat_blobs[0]].shape[3];
+  const TailModule& M = mods[b.fused_mod];   // the module whose tail the blob's producer was folded into
+  const int A = M.A, NC = tail_C, NO = tail_C + 4;
+  const int h = blobs[M.feat_blobs[0]].shape[2], w = blobs[M.feat_blobs[0]].shape[3];
   const size_t K = (size_t)h * w;
   float* out = b.host.p;
   if (b.fused_role == FR_PROB_PLANES) {
     if (n != K * A * NC) throw std::runtime_error("blob '" + b.name + "': unexpected shape for the softmax output");
-    HIP_THROW(hipMemcpyAsync(out, blobs[tail_cls_blob].dev.p, n * 4, hipMemcpyDeviceToHost, stream));
+    HIP_THROW(hipMemcpyAsync(out, blobs[M.cls_blob].dev.p, n * 4, hipMemcpyDeviceToHost, stream));
     HIP_THROW(hipStreamSynchronize(stream));
     b.dev_newer = false;
     return;
   }
   std::vector<float> lg(K * A * NO);
-  HIP_THROW(hipMemcpyAsync(lg.data(), tw.logits, lg.size() * 4, hipMemcpyDeviceToHost, stream));
+  HIP_THROW(hipMemcpyAsync(lg.data(), M.tw.logits, lg.size() * 4, hipMemcpyDeviceToHost, stream));
   HIP_THROW(hipStreamSynchronize(stream));
   auto L = [&](size_t k, int a, int o) { return lg[(k * A + a) * NO + o]; };
-  const bool per_head = tail_heads != 1;
+  const bool per_head = M.heads != 1;
   switch (b.fused_role) {
     case FR_CLS_CONV:
       if (n != (per_head ? NC : NC * (size_t)A) * K) throw std::runtime_error("blob '" + b.name + "': unexpected shape");

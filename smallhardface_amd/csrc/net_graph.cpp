@@ -117,6 +117,180 @@ void shf::check_blob_dims(const std::vector<int>& shp, const std::string& name) 
   }
 }
 
+// One proposal module: walk back from its ProposalLayer through the layers folded into the tail
+void shf_net::build_module(int mj, const std::map<int, int>& producer, std::map<int, int>& fused_by) {
+  TailModule& M = mods[mj];
+  Layer& T = layers[M.layer];
+  std::set<int> fused_layers;
+  if (T.bottoms.size() != 3 || T.tops.empty())
+    throw std::runtime_error("ProposalLayer: expected bottoms (cls_prob, bbox_pred, im_info)");
+  M.cls_blob = T.bottoms[0];
+  M.box_blob = T.bottoms[1];
+  M.boxes_blob = T.tops[0];
+  M.prob_blob = T.tops.size() > 1 ? T.tops[1] : -1;
+  auto prod = [&](int blob, const char* want) -> int {
+    auto it = producer.find(blob);
+    if (it == producer.end() || layers[it->second].type != want)
+      throw std::runtime_error(std::string("tail: expected a ") + want + " producing '" + blobs[blob].name + "'");
+    return it->second;
+  };
+  // cls branch: Reshape <- Softmax <- (Concat axis2 of 1x1 convs | Reshape <- 1x1 conv)
+  const int l_rs = prod(M.cls_blob, "Reshape");
+  const int l_sm = prod(layers[l_rs].bottoms[0], "Softmax");
+  fused_layers.insert(l_rs);
+  fused_layers.insert(l_sm);
+  int pre = layers[l_sm].bottoms[0], l_pre_rs = -1;
+  auto pit = producer.find(pre);
+  if (pit == producer.end()) throw std::runtime_error("tail: dangling softmax input");
+  if (layers[pit->second].type == "Concat") {
+    const int l_cc = pit->second;
+    if (geti(layers[l_cc].msg->sub("concat_param"), "axis", 1) != 2)
+      throw std::runtime_error("tail: class-score concat must be on axis 2");
+    fused_layers.insert(l_cc);
+    for (int b : layers[l_cc].bottoms) M.cls_layers.push_back(prod(b, "Convolution"));
+  } else if (layers[pit->second].type == "Reshape") {
+    l_pre_rs = pit->second;
+    fused_layers.insert(pit->second);
+    M.cls_layers.push_back(prod(layers[pit->second].bottoms[0], "Convolution"));
+  } else {
+    throw std::runtime_error("tail: unsupported class-score branch");
+  }
+  // box branch: Concat axis1 of 1x1 convs | single 1x1 conv
+  auto bit = producer.find(M.box_blob);
+  if (bit == producer.end()) throw std::runtime_error("tail: dangling bbox input");
+  if (layers[bit->second].type == "Concat") {
+    if (geti(layers[bit->second].msg->sub("concat_param"), "axis", 1) != 1)
+      throw std::runtime_error("tail: bbox concat must be on axis 1");
+    fused_layers.insert(bit->second);
+    for (int b : layers[bit->second].bottoms) M.box_layers.push_back(prod(b, "Convolution"));
+  } else if (layers[bit->second].type == "Convolution") {
+    M.box_layers.push_back(bit->second);
+  } else {
+    throw std::runtime_error("tail: unsupported bbox branch");
+  }
+  if (M.cls_layers.size() != M.box_layers.size())
+    throw std::runtime_error("tail: class / bbox branches disagree");
+  M.heads = (int)M.cls_layers.size();
+  for (int i = 0; i < M.heads; ++i) {
+    Layer& c = layers[M.cls_layers[i]];
+    Layer& b = layers[M.box_layers[i]];
+    if (c.k != 1 || b.k != 1 || c.bottoms[0] != b.bottoms[0])
+      throw std::runtime_error("tail: cls/bbox predictors must be 1x1 convs on the same head blob");
+    M.feat_blobs.push_back(c.bottoms[0]);
+    fused_layers.insert(M.cls_layers[i]);
+    fused_layers.insert(M.box_layers[i]);
+  }
+  const PMsg* py = T.msg->sub("python_param");
+  auto ps = parse_param_str(py->str("param_str"));
+  std::vector<double> fs = ps.count("feat_stride") ? ps["feat_stride"] : std::vector<double>{16};
+  std::vector<double> scales = ps.count("scales") ? ps["scales"] : std::vector<double>{8, 16, 32};
+  std::vector<double> ratios = ps.count("ratios") ? ps["ratios"] : std::vector<double>{0.5, 1, 2};
+  std::vector<double> shifts = ps.count("shifts") ? ps["shifts"] : std::vector<double>{0};
+  const int base_size = ps.count("base_size") ? (int)ps["base_size"][0] : 16;
+  const bool subsampled = ps.count("subsampled") ? ps["subsampled"][0] != 0 : true;
+  if (ps.count("num_feats") && ps["num_feats"][0] != 1) throw std::runtime_error("tail: num_feats != 1 unsupported");
+  // what the reference's layer cannot run is refused here with the layer's name, not answered: an empty list raises in its
+  // setup, a stride below 1 divides by zero in the subsampling map (proposal_layer.py:163-164)
+  if (fs.empty() || scales.empty() || ratios.empty() || shifts.empty())
+    throw std::runtime_error("ProposalLayer '" + T.name + "': feat_stride, scales, ratios and shifts need at least one entry");
+  for (double v : fs)
+    if (!(v >= 1 && v <= 4096))
+      throw std::runtime_error("ProposalLayer '" + T.name + "': feat_stride entries must be in 1 .. 4096");
+  gen_anchors(base_size, ratios, scales, shifts, fs, M.anchors);
+  M.A = (int)M.anchors.size() / 4;
+  if (M.A < 1) throw std::runtime_error("ProposalLayer '" + T.name + "': the param string yields no anchors");
+  if (M.A > 8) throw std::runtime_error("tail: more than 8 anchors per cell unsupported");
+  M.feat_stride = (int)fs[0];
+  M.sub_stride.assign(M.A, 1);
+  if (subsampled) {
+    // anchor i is kept on every (feat_stride[i // len(shifts)**2] // feat_stride[0])-th row and column
+    // (proposal_layer.py:160-165): with fewer feat_stride entries than that index reaches the reference raises IndexError
+    const size_t need = (size_t)(M.A - 1) / (shifts.size() * shifts.size()) + 1;
+    if (fs.size() < need)
+      throw std::runtime_error("ProposalLayer '" + T.name + "': feat_stride has " + std::to_string(fs.size()) +
+                               " entries, the anchor subsampling of " + std::to_string(M.A) + " anchors indexes " +
+                               std::to_string(need) + " (the reference raises IndexError); give one stride per anchor "
+                               "group or 'subsampled': False");
+    for (int i = 0; i < M.A; ++i) {
+      const size_t idx = (size_t)i / (shifts.size() * shifts.size());
+      M.sub_stride[i] = (int)fs[idx] / (int)fs[0];
+      if (M.sub_stride[i] < 1)   // (a slice step of zero: ValueError in the reference)
+        throw std::runtime_error("ProposalLayer '" + T.name + "': feat_stride entries must not be smaller than the first one");
+    }
+  }
+  if (M.heads != 1 && M.heads != M.A) throw std::runtime_error("tail: heads must be 1 or == anchors");
+  // the class count (proposal_layer.py:118: scores.shape[1] / A): every per-head predictor has C outputs, the single-blob
+  // one C * A with channel c * A + a; the Reshapes around the softmax must say the same
+  const std::string who = "ProposalLayer '" + T.name + "': ";
+  const bool per_head = M.heads != 1;
+  int C = -1;
+  for (int i = 0; i < M.heads; ++i) {
+    const Layer& c = layers[M.cls_layers[i]];
+    if (!per_head && c.nout % M.A)
+      throw std::runtime_error(who + "class predictor '" + c.name + "' has " + std::to_string(c.nout) + " outputs, not a multiple of the " +
+                               std::to_string(M.A) + " anchors");
+    const int ci = per_head ? c.nout : c.nout / M.A;
+    if (C >= 0 && ci != C)
+      throw std::runtime_error(who + "class predictors '" + layers[M.cls_layers[0]].name + "' and '" + c.name +
+                               "' disagree on the class count (" + std::to_string(C) + " vs " + std::to_string(ci) + ")");
+    C = ci;
+    if (layers[M.box_layers[i]].nout != (per_head ? 4 : 4 * M.A))
+      throw std::runtime_error(who + "bbox predictor '" + layers[M.box_layers[i]].name + "' channel count does not match the anchors");
+  }
+  auto reshape_dim1 = [&](int li2) {
+    const PMsg* rp = layers[li2].msg->sub("reshape_param");
+    std::vector<int> dims;
+    if (rp && rp->sub("shape"))
+      for (auto d : rp->sub("shape")->all("dim")) dims.push_back(atoi(d->scalar.c_str()));
+    return dims.size() > 1 ? dims[1] : 0;
+  };
+  if (l_pre_rs >= 0 && reshape_dim1(l_pre_rs) != C)
+    throw std::runtime_error(who + "Reshape '" + layers[l_pre_rs].name + "' makes " + std::to_string(reshape_dim1(l_pre_rs)) +
+                             " class planes, the predictor has " + std::to_string(C) + " classes per anchor");
+  if (reshape_dim1(l_rs) != C * M.A)
+    throw std::runtime_error(who + "Reshape '" + layers[l_rs].name + "' makes " + std::to_string(reshape_dim1(l_rs)) +
+                             " channels, the predictors give " + std::to_string(C) + " classes x " + std::to_string(M.A) + " anchors");
+  if (C < 2) throw std::runtime_error(who + "at least 2 classes (background and one foreground class) are needed, the predictors have " + std::to_string(C));
+  if (C > kTailMaxClasses)
+    throw std::runtime_error(who + std::to_string(C) + " classes: the tail supports at most " + std::to_string(kTailMaxClasses));
+  // Net.num_classes is one number, and the tail kernels are instantiated on it: the modules of a net agree on it
+  if (mj > 0 && C != tail_C)
+    throw std::runtime_error("ProposalLayers '" + layers[mods[0].layer].name + "' and '" + T.name + "' disagree on the class count (" +
+                             std::to_string(tail_C) + " vs " + std::to_string(C) + "): the modules of a net share one class count");
+  tail_C = C;
+  // a layer folded into one module's tail has its top in that module's workspace alone: a predictor, score concat / reshape
+  // or softmax that two proposal layers both read would have to live in both
+  for (int li2 : fused_layers) {
+    auto own = fused_by.find(li2);
+    if (own != fused_by.end() && own->second != mj)
+      throw std::runtime_error("ProposalLayers '" + layers[mods[own->second].layer].name + "' and '" + T.name + "' both fuse layer '" +
+                               layers[li2].name + "' (blob '" + blobs[layers[li2].tops[0]].name + "'): every module needs its own "
+                               "predictors, softmax and reshapes");
+    fused_by[li2] = mj;
+  }
+  for (int li2 : fused_layers) {
+    layers[li2].op = OP_SKIP;
+    // what the top holds, for the on-demand read-back (shf_net::materialize_fused)
+    int role = FR_NONE, head = -1;
+    for (int i = 0; i < M.heads; ++i) {
+      if (M.cls_layers[i] == li2) role = FR_CLS_CONV, head = i;
+      if (M.box_layers[i] == li2) role = FR_BOX_CONV, head = i;
+    }
+    if (role == FR_NONE && layers[li2].type == "Softmax") role = FR_PROB_PLANES;
+    if (role == FR_NONE && (layers[li2].type == "Concat" || layers[li2].type == "Reshape")) role = FR_CLS_PLANES;
+    for (int t : layers[li2].tops) {
+      blobs[t].kind = BK_FUSED;
+      blobs[t].fused_role = role;
+      blobs[t].fused_head = head;
+      blobs[t].fused_mod = mj;
+    }
+  }
+  blobs[M.cls_blob].kind = BK_NCHW_MAT;
+  blobs[M.box_blob].kind = BK_NCHW_MAT;
+  blobs[M.boxes_blob].kind = BK_FLAT;
+  if (M.prob_blob >= 0) blobs[M.prob_blob].kind = BK_FLAT;
+}
+
 void shf_net::build(const std::string& text, const char* caffemodel) {
   proto_text = text;
   if (!clone_src && getenv("SHF_CONV_MODE")) conv_mode = atoi(getenv("SHF_CONV_MODE"));
@@ -254,6 +428,8 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
         throw std::runtime_error("Python layer '" + L.name + "': only ProposalLayer has a native implementation");
       L.op = OP_TAIL;
       tail_layer = (int)li;
+      mods.emplace_back();
+      mods.back().layer = (int)li;
     } else if (L.type == "Concat" || L.type == "Softmax" || L.type == "Reshape" || L.type == "Split" ||
                L.type == "Input") {
       L.op = OP_SKIP;
@@ -263,168 +439,34 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
     for (int t : L.tops) producer[t] = (int)li;
   }
 
-  // ---- the fused tail: walk back from the proposal layer
-  std::set<int> fused_layers;
-  if (tail_layer >= 0) {
-    Layer& T = layers[tail_layer];
-    if (T.bottoms.size() != 3 || T.tops.empty())
-      throw std::runtime_error("ProposalLayer: expected bottoms (cls_prob, bbox_pred, im_info)");
-    tail_cls_blob = T.bottoms[0];
-    tail_box_blob = T.bottoms[1];
-    boxes_blob = T.tops[0];
-    prob_blob = T.tops.size() > 1 ? T.tops[1] : -1;
-    auto prod = [&](int blob, const char* want) -> int {
-      auto it = producer.find(blob);
-      if (it == producer.end() || layers[it->second].type != want)
-        throw std::runtime_error(std::string("tail: expected a ") + want + " producing '" + blobs[blob].name + "'");
-      return it->second;
-    };
-    // cls branch: Reshape <- Softmax <- (Concat axis2 of 1x1 convs | Reshape <- 1x1 conv)
-    const int l_rs = prod(tail_cls_blob, "Reshape");
-    const int l_sm = prod(layers[l_rs].bottoms[0], "Softmax");
-    fused_layers.insert(l_rs);
-    fused_layers.insert(l_sm);
-    int pre = layers[l_sm].bottoms[0], l_pre_rs = -1;
-    auto pit = producer.find(pre);
-    if (pit == producer.end()) throw std::runtime_error("tail: dangling softmax input");
-    if (layers[pit->second].type == "Concat") {
-      const int l_cc = pit->second;
-      if (geti(layers[l_cc].msg->sub("concat_param"), "axis", 1) != 2)
-        throw std::runtime_error("tail: class-score concat must be on axis 2");
-      fused_layers.insert(l_cc);
-      for (int b : layers[l_cc].bottoms) tail_cls_layers.push_back(prod(b, "Convolution"));
-    } else if (layers[pit->second].type == "Reshape") {
-      l_pre_rs = pit->second;
-      fused_layers.insert(pit->second);
-      tail_cls_layers.push_back(prod(layers[pit->second].bottoms[0], "Convolution"));
-    } else {
-      throw std::runtime_error("tail: unsupported class-score branch");
-    }
-    // box branch: Concat axis1 of 1x1 convs | single 1x1 conv
-    auto bit = producer.find(tail_box_blob);
-    if (bit == producer.end()) throw std::runtime_error("tail: dangling bbox input");
-    if (layers[bit->second].type == "Concat") {
-      if (geti(layers[bit->second].msg->sub("concat_param"), "axis", 1) != 1)
-        throw std::runtime_error("tail: bbox concat must be on axis 1");
-      fused_layers.insert(bit->second);
-      for (int b : layers[bit->second].bottoms) tail_box_layers.push_back(prod(b, "Convolution"));
-    } else if (layers[bit->second].type == "Convolution") {
-      tail_box_layers.push_back(bit->second);
-    } else {
-      throw std::runtime_error("tail: unsupported bbox branch");
-    }
-    if (tail_cls_layers.size() != tail_box_layers.size())
-      throw std::runtime_error("tail: class / bbox branches disagree");
-    tail_heads = (int)tail_cls_layers.size();
-    for (int i = 0; i < tail_heads; ++i) {
-      Layer& c = layers[tail_cls_layers[i]];
-      Layer& b = layers[tail_box_layers[i]];
-      if (c.k != 1 || b.k != 1 || c.bottoms[0] != b.bottoms[0])
-        throw std::runtime_error("tail: cls/bbox predictors must be 1x1 convs on the same head blob");
-      tail_feat_blobs.push_back(c.bottoms[0]);
-      fused_layers.insert(tail_cls_layers[i]);
-      fused_layers.insert(tail_box_layers[i]);
-    }
-    const PMsg* py = T.msg->sub("python_param");
-    auto ps = parse_param_str(py->str("param_str"));
-    std::vector<double> fs = ps.count("feat_stride") ? ps["feat_stride"] : std::vector<double>{16};
-    std::vector<double> scales = ps.count("scales") ? ps["scales"] : std::vector<double>{8, 16, 32};
-    std::vector<double> ratios = ps.count("ratios") ? ps["ratios"] : std::vector<double>{0.5, 1, 2};
-    std::vector<double> shifts = ps.count("shifts") ? ps["shifts"] : std::vector<double>{0};
-    const int base_size = ps.count("base_size") ? (int)ps["base_size"][0] : 16;
-    const bool subsampled = ps.count("subsampled") ? ps["subsampled"][0] != 0 : true;
-    if (ps.count("num_feats") && ps["num_feats"][0] != 1) throw std::runtime_error("tail: num_feats != 1 unsupported");
-    // what the reference's layer cannot run is refused here with the layer's name, not answered: an empty list raises in its
-    // setup, a stride below 1 divides by zero in the subsampling map (proposal_layer.py:163-164)
-    if (fs.empty() || scales.empty() || ratios.empty() || shifts.empty())
-      throw std::runtime_error("ProposalLayer '" + T.name + "': feat_stride, scales, ratios and shifts need at least one entry");
-    for (double v : fs)
-      if (!(v >= 1 && v <= 4096))
-        throw std::runtime_error("ProposalLayer '" + T.name + "': feat_stride entries must be in 1 .. 4096");
-    gen_anchors(base_size, ratios, scales, shifts, fs, anchors);
-    tail_A = (int)anchors.size() / 4;
-    if (tail_A < 1) throw std::runtime_error("ProposalLayer '" + T.name + "': the param string yields no anchors");
-    if (tail_A > 8) throw std::runtime_error("tail: more than 8 anchors per cell unsupported");
-    feat_stride = (int)fs[0];
-    sub_stride.assign(tail_A, 1);
-    if (subsampled) {
-      // anchor i is kept on every (feat_stride[i // len(shifts)**2] // feat_stride[0])-th row and column
-      // (proposal_layer.py:160-165): with fewer feat_stride entries than that index reaches the reference raises IndexError
-      const size_t need = (size_t)(tail_A - 1) / (shifts.size() * shifts.size()) + 1;
-      if (fs.size() < need)
-        throw std::runtime_error("ProposalLayer '" + T.name + "': feat_stride has " + std::to_string(fs.size()) +
-                                 " entries, the anchor subsampling of " + std::to_string(tail_A) + " anchors indexes " +
-                                 std::to_string(need) + " (the reference raises IndexError); give one stride per anchor "
-                                 "group or 'subsampled': False");
-      for (int i = 0; i < tail_A; ++i) {
-        const size_t idx = (size_t)i / (shifts.size() * shifts.size());
-        sub_stride[i] = (int)fs[idx] / (int)fs[0];
-        if (sub_stride[i] < 1)   // (a slice step of zero: ValueError in the reference)
-          throw std::runtime_error("ProposalLayer '" + T.name + "': feat_stride entries must not be smaller than the first one");
-      }
-    }
-    if (tail_heads != 1 && tail_heads != tail_A) throw std::runtime_error("tail: heads must be 1 or == anchors");
-    // the class count (proposal_layer.py:118: scores.shape[1] / A): every per-head predictor has C outputs, the single-blob
-    // one C * A with channel c * A + a; the Reshapes around the softmax must say the same
-    const std::string who = "ProposalLayer '" + T.name + "': ";
-    const bool per_head = tail_heads != 1;
-    int C = -1;
-    for (int i = 0; i < tail_heads; ++i) {
-      const Layer& c = layers[tail_cls_layers[i]];
-      if (!per_head && c.nout % tail_A)
-        throw std::runtime_error(who + "class predictor '" + c.name + "' has " + std::to_string(c.nout) + " outputs, not a multiple of the " +
-                                 std::to_string(tail_A) + " anchors");
-      const int ci = per_head ? c.nout : c.nout / tail_A;
-      if (C >= 0 && ci != C)
-        throw std::runtime_error(who + "class predictors '" + layers[tail_cls_layers[0]].name + "' and '" + c.name +
-                                 "' disagree on the class count (" + std::to_string(C) + " vs " + std::to_string(ci) + ")");
-      C = ci;
-      if (layers[tail_box_layers[i]].nout != (per_head ? 4 : 4 * tail_A))
-        throw std::runtime_error(who + "bbox predictor '" + layers[tail_box_layers[i]].name + "' channel count does not match the anchors");
-    }
-    auto reshape_dim1 = [&](int li2) {
-      const PMsg* rp = layers[li2].msg->sub("reshape_param");
-      std::vector<int> dims;
-      if (rp && rp->sub("shape"))
-        for (auto d : rp->sub("shape")->all("dim")) dims.push_back(atoi(d->scalar.c_str()));
-      return dims.size() > 1 ? dims[1] : 0;
-    };
-    if (l_pre_rs >= 0 && reshape_dim1(l_pre_rs) != C)
-      throw std::runtime_error(who + "Reshape '" + layers[l_pre_rs].name + "' makes " + std::to_string(reshape_dim1(l_pre_rs)) +
-                               " class planes, the predictor has " + std::to_string(C) + " classes per anchor");
-    if (reshape_dim1(l_rs) != C * tail_A)
-      throw std::runtime_error(who + "Reshape '" + layers[l_rs].name + "' makes " + std::to_string(reshape_dim1(l_rs)) +
-                               " channels, the predictors give " + std::to_string(C) + " classes x " + std::to_string(tail_A) + " anchors");
-    if (C < 2) throw std::runtime_error(who + "at least 2 classes (background and one foreground class) are needed, the predictors have " + std::to_string(C));
-    if (C > kTailMaxClasses)
-      throw std::runtime_error(who + std::to_string(C) + " classes: the tail supports at most " + std::to_string(kTailMaxClasses));
-    tail_C = C;
-    for (int li2 : fused_layers) {
-      layers[li2].op = OP_SKIP;
-      // what the top holds, for the on-demand read-back (shf_net::materialize_fused)
-      int role = FR_NONE, head = -1;
-      for (int i = 0; i < tail_heads; ++i) {
-        if (tail_cls_layers[i] == li2) role = FR_CLS_CONV, head = i;
-        if (tail_box_layers[i] == li2) role = FR_BOX_CONV, head = i;
-      }
-      if (role == FR_NONE && layers[li2].type == "Softmax") role = FR_PROB_PLANES;
-      if (role == FR_NONE && (layers[li2].type == "Concat" || layers[li2].type == "Reshape")) role = FR_CLS_PLANES;
-      for (int t : layers[li2].tops) {
-        blobs[t].kind = BK_FUSED;
-        blobs[t].fused_role = role;
-        blobs[t].fused_head = head;
-      }
-    }
-    blobs[tail_cls_blob].kind = BK_NCHW_MAT;
-    blobs[tail_box_blob].kind = BK_NCHW_MAT;
-    blobs[boxes_blob].kind = BK_FLAT;
-    if (prob_blob >= 0) blobs[prob_blob].kind = BK_FLAT;
+  // ---- the fused tails: walk back from every proposal layer
+  std::map<int, int> fused_by;   // layer folded into a tail -> its module
+  if ((int)mods.size() > kMaxModules) {
+    std::string names;
+    for (auto& M : mods) names += (names.empty() ? "'" : ", '") + layers[M.layer].name + "'";
+    throw std::runtime_error(std::to_string(mods.size()) + " ProposalLayers (" + names + "): a net holds at most " +
+                             std::to_string(kMaxModules) + " proposal modules");
   }
-
+  for (int mj = 0; mj < (int)mods.size(); ++mj) {
+    const std::string lname = "'" + layers[mods[mj].layer].name + "'";
+    try {
+      build_module(mj, producer, fused_by);
+    } catch (const std::runtime_error& e) {   // (every refusal of the walk names its module's layer)
+      const std::string what = e.what();
+      if (what.find(lname) != std::string::npos) throw;
+      throw std::runtime_error(what + " (ProposalLayer " + lname + ")");
+    }
+    for (int q = 0; q < mj; ++q)
+      for (int t : layers[mods[q].layer].tops)
+        for (int u : layers[mods[mj].layer].tops)
+          if (t == u)
+            throw std::runtime_error("ProposalLayers '" + layers[mods[q].layer].name + "' and " + lname + " write the same top '" +
+                                     blobs[t].name + "'");
+  }
   // ---- channel-concat views (zero-copy): bottoms of a non-fused axis-1 Concat live inside the top
   for (size_t li = 0; li < layers.size(); ++li) {
     Layer& L = layers[li];
-    if (L.type != "Concat" || fused_layers.count((int)li)) continue;
+    if (L.type != "Concat" || fused_by.count((int)li)) continue;
     if (geti(L.msg->sub("concat_param"), "axis", 1) != 1)
       throw std::runtime_error("Concat '" + L.name + "': only channel concat is supported outside the tail");
     for (int b : L.bottoms) {
@@ -438,18 +480,18 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   infer_shapes();
   // the per-head tail packs Cf weights per row from every head's predictors and reads Cf channels of every head blob at the
   // first one's map size (build_tail_weights, tail_logits_kernel): heads of another shape would be read out of bounds
-  if (tail_layer >= 0) {
-    const std::vector<int>& s0 = blobs[tail_feat_blobs[0]].shape;
+  for (const TailModule& M : mods) {
+    const std::vector<int>& s0 = blobs[M.feat_blobs[0]].shape;
     if (s0.size() != 4)
-      throw std::runtime_error("ProposalLayer '" + layers[tail_layer].name + "': head blob '" + blobs[tail_feat_blobs[0]].name + "' is not 4-D");
-    for (int fb : tail_feat_blobs) {
+      throw std::runtime_error("ProposalLayer '" + layers[M.layer].name + "': head blob '" + blobs[M.feat_blobs[0]].name + "' is not 4-D");
+    for (int fb : M.feat_blobs) {
       const std::vector<int>& s = blobs[fb].shape;
       if (s.size() != 4 || s[1] != s0[1])
-        throw std::runtime_error("ProposalLayer '" + layers[tail_layer].name + "': head blobs '" + blobs[tail_feat_blobs[0]].name +
+        throw std::runtime_error("ProposalLayer '" + layers[M.layer].name + "': head blobs '" + blobs[M.feat_blobs[0]].name +
                                  "' and '" + blobs[fb].name + "' differ in channel count (" + std::to_string(s0[1]) + " vs " +
                                  std::to_string(s.size() == 4 ? s[1] : 0) + "): the per-head predictors must read heads of one width");
       if (s[2] != s0[2] || s[3] != s0[3])
-        throw std::runtime_error("ProposalLayer '" + layers[tail_layer].name + "': head blobs '" + blobs[tail_feat_blobs[0]].name +
+        throw std::runtime_error("ProposalLayer '" + layers[M.layer].name + "': head blobs '" + blobs[M.feat_blobs[0]].name +
                                  "' and '" + blobs[fb].name + "' differ in map size");
     }
   }
@@ -589,7 +631,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
     for (size_t bi = 0; bi < blobs.size() && conv_knobs().split_act; ++bi) {
       Blob& B = blobs[bi];
       if (B.owner >= 0 || B.kind != BK_NHWC || B.shape.size() != 4) continue;
-      if (std::count(tail_feat_blobs.begin(), tail_feat_blobs.end(), (int)bi)) continue;
+      if (is_feat_blob((int)bi)) continue;
       bool concat_member = false;
       for (auto& O : blobs) concat_member = concat_member || O.owner == (int)bi;
       if (concat_member) continue;
@@ -693,68 +735,69 @@ void shf_net::alloc_buffers() {
     Blob& b = blobs[i];
     if (b.kind == BK_FUSED) continue;
     if (b.owner >= 0) continue;  // view into a concat buffer
-    if (b.kind == BK_FLAT && ((int)i == boxes_blob || (int)i == prob_blob)) continue;  // sized by the tail
+    if (b.kind == BK_FLAT && module_of_output((int)i) >= 0) continue;  // sized by the tail
     b.dev.ensure(std::max<size_t>(b.count(), 1) * sizeof(float));
   }
-  if (tail_layer >= 0) {
-    Blob& f = blobs[tail_feat_blobs[0]];
-    ensure_tail_workspace((size_t)f.shape[2] * f.shape[3] * tail_A);
+  for (TailModule& M : mods) {
+    Blob& f = blobs[M.feat_blobs[0]];
+    ensure_tail_workspace(M, (size_t)f.shape[2] * f.shape[3] * M.A);
   }
 }
 
-// tail workspace + proposal output blobs for `total` anchors (grow-only)
-void shf_net::ensure_tail_workspace(size_t total) {
+// module M's tail workspace + proposal output blobs for `total` anchors (grow-only)
+void shf_net::ensure_tail_workspace(TailModule& M, size_t total) {
   size_t npad = 1;
   while (npad < total) npad <<= 1;
   const size_t rec = (size_t)tail_C + 4;   // floats per anchor: the class scores and four box values
-  tw_logits.ensure(total * rec * 4);
-  tw_rec.ensure(total * rec * 4);
-  tw_keys.ensure(std::max<size_t>(npad, 16384) * 8);
-  tw_counters.ensure(64);
-  tw.logits = (float*)tw_logits.p;
-  tw.rec = (float*)tw_rec.p;
-  tw.keys = (unsigned long long*)tw_keys.p;
-  tw.counters = (int*)tw_counters.p;
-  tw.amax = fp16_mode() ? (unsigned*)amax_slots.p : nullptr;   // (the tail's reset kernel zeroes the slots for the next pass)
+  M.tw_logits.ensure(total * rec * 4);
+  M.tw_rec.ensure(total * rec * 4);
+  M.tw_keys.ensure(std::max<size_t>(npad, 16384) * 8);
+  M.tw_counters.ensure(64);
+  TailWork& tw = M.tw;
+  tw.logits = (float*)M.tw_logits.p;
+  tw.rec = (float*)M.tw_rec.p;
+  tw.keys = (unsigned long long*)M.tw_keys.p;
+  tw.counters = (int*)M.tw_counters.p;
+  // (the tail's reset kernel zeroes the lane's slots for the next pass: once per lane, so the first module's entry carries them)
+  tw.amax = fp16_mode() && &M == &mods[0] ? (unsigned*)amax_slots.p : nullptr;
   tw.n_amax = (int)blobs.size();
   tw.cap_anchors = total;
   tw.cap_keys = npad;
   const size_t rmax = (pre_nms_topN > 0) ? std::min<size_t>(total, (size_t)pre_nms_topN) : total;
-  blobs[boxes_blob].dev.ensure(std::max<size_t>(rmax, 1) * 5 * 4);
-  if (prob_blob >= 0) blobs[prob_blob].dev.ensure(std::max<size_t>(rmax, 1) * tail_C * 4);
+  blobs[M.boxes_blob].dev.ensure(std::max<size_t>(rmax, 1) * 5 * 4);
+  if (M.prob_blob >= 0) blobs[M.prob_blob].dev.ensure(std::max<size_t>(rmax, 1) * tail_C * 4);
 }
 
-void shf_net::build_tail_weights() {
-  if (tail_layer < 0) return;
-  tail_Cf = blobs[tail_feat_blobs[0]].shape[1];
-  const int A = tail_A, Cf = tail_Cf, NC = tail_C, NO = tail_C + 4;
+void shf_net::build_tail_weights(TailModule& M) {
+  M.Cf = blobs[M.feat_blobs[0]].shape[1];
+  const int A = M.A, Cf = M.Cf, NC = tail_C, NO = tail_C + 4;
   std::vector<float> W((size_t)A * NO * Cf, 0.f), B((size_t)A * NO, 0.f);
   for (int a = 0; a < A; ++a) {
-    const int h = tail_heads == 1 ? 0 : a;
-    Layer& c = layers[tail_cls_layers[h]];
-    Layer& b = layers[tail_box_layers[h]];
+    const int h = M.heads == 1 ? 0 : a;
+    Layer& c = layers[M.cls_layers[h]];
+    Layer& b = layers[M.box_layers[h]];
     const float* cw = c.params[0]->host.data();
     const float* bw = b.params[0]->host.data();
     const float* cb = c.params.size() > 1 ? c.params[1]->host.data() : nullptr;
     const float* bb = b.params.size() > 1 ? b.params[1]->host.data() : nullptr;
     for (int cls = 0; cls < NC; ++cls) {
       // plain template: cls_score channel = cls*A + a (Reshape (0,C,-1,0)); dilation template: channel = cls
-      const int row = tail_heads == 1 ? cls * A + a : cls;
+      const int row = M.heads == 1 ? cls * A + a : cls;
       memcpy(&W[((size_t)a * NO + cls) * Cf], cw + (size_t)row * Cf, Cf * sizeof(float));
       B[a * NO + cls] = cb ? cb[row] : 0.f;
     }
     for (int j = 0; j < 4; ++j) {
-      const int row = tail_heads == 1 ? a * 4 + j : j;
+      const int row = M.heads == 1 ? a * 4 + j : j;
       memcpy(&W[((size_t)a * NO + NC + j) * Cf], bw + (size_t)row * Cf, Cf * sizeof(float));
       B[a * NO + NC + j] = bb ? bb[row] : 0.f;
     }
   }
-  tail_W.ensure(W.size() * 4);
-  tail_b.ensure(B.size() * 4);
-  HIP_THROW(hipMemcpy(tail_W.p, W.data(), W.size() * 4, hipMemcpyHostToDevice));
-  HIP_THROW(hipMemcpy(tail_b.p, B.data(), B.size() * 4, hipMemcpyHostToDevice));
-  tail_w_dirty = false;
-  tail_gen = *wgen;
+  M.W.ensure(W.size() * 4);
+  M.b.ensure(B.size() * 4);
+  HIP_THROW(hipMemcpy(M.W.p, W.data(), W.size() * 4, hipMemcpyHostToDevice));
+  HIP_THROW(hipMemcpy(M.b.p, B.data(), B.size() * 4, hipMemcpyHostToDevice));
+  M.w_dirty = false;
+  M.gen = *wgen;
 }
 
 void shf_net::commit_params(int li) {
@@ -766,8 +809,12 @@ void shf_net::commit_params(int li) {
   };
   // the raw / packed tensors are shared by every lane cloned from this net: nothing may be in flight on any stream
   HIP_THROW(hipDeviceSynchronize());
-  const bool in_tail = std::count(tail_cls_layers.begin(), tail_cls_layers.end(), li) ||
-                       std::count(tail_box_layers.begin(), tail_box_layers.end(), li);
+  bool in_tail = false;   // a predictor of some module: its weights go into that module's combined matrix
+  for (TailModule& M : mods)
+    if (std::count(M.cls_layers.begin(), M.cls_layers.end(), li) || std::count(M.box_layers.begin(), M.box_layers.end(), li)) {
+      in_tail = true;
+      M.w_dirty = true;
+    }
   for (size_t pi = 0; pi < L.params.size(); ++pi) {
     ParamBlob& p = *L.params[pi];
     p.raw.ensure(p.count() * 4);
@@ -850,7 +897,6 @@ void shf_net::commit_params(int li) {
     }
     p.dirty = false;
   }
-  if (in_tail) tail_w_dirty = true;
   ++*wgen;
 }
 

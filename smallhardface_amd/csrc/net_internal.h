@@ -136,6 +136,7 @@ struct Blob {
   // after Net.forward() (shf_net::materialize_fused): what they hold, and for a predictor's top which head it belongs to
   int fused_role = 0;              // FusedRole
   int fused_head = -1;
+  int fused_mod = -1;              // ... and which proposal module's tail it was folded into
   size_t count() const {
     size_t c = 1;
     for (int d : shape) c *= (size_t)d;
@@ -325,6 +326,26 @@ int conv_f16x3_plan_probe(int Cin, int Cout, int H, int W, int in_split, int poo
 }
 using namespace shf;
 
+// One ProposalLayer of the graph with the predictors fused into it: what the tail kernels need to know about it, its
+// combined weights, its workspace and its output blobs.  Everything here was one-per-net while a net held one such layer.
+constexpr int kMaxModules = kTailMaxModules;   // proposal layers per net (tail.hip TM)
+struct TailModule {
+  int layer = -1;                                   // the Python layer
+  std::vector<int> cls_layers, box_layers;          // per head (or single)
+  std::vector<int> feat_blobs;
+  int A = 0, heads = 0, Cf = 0;
+  int cls_blob = -1, box_blob = -1, boxes_blob = -1, prob_blob = -1;
+  std::vector<double> anchors;
+  std::vector<int> sub_stride;
+  int feat_stride = 8;
+  DevBuf W, b;                                      // [A][C + 4][Cf] / [A][C + 4] (build_tail_weights)
+  bool w_dirty = true;
+  int gen = -1;
+  TailWork tw;
+  DevBuf tw_logits, tw_rec, tw_keys, tw_counters;
+  int last_R = -1;   // proposal rows of the last completed forward (record_forward); -1: none yet
+};
+
 // configuration shared by a net and every lane cloned from it: the arithmetic mode and what the reference's Python
 // layer reads from the global cfg at every forward (lib/layers/proposal_layer.py:88-92)
 struct NetShared {
@@ -391,22 +412,27 @@ struct shf_net {
   hipStream_t stream = nullptr;
   Prof prof;
   int phase = 1;
-  // tail
+  // tail: one record per ProposalLayer of the graph ("module": the SSH-style detector has one per backbone stride, each with
+  // its own boxes_<level> / cls_prob_<level> tops, lib/test.py:67-83), in prototxt order.  tail_layer: the LAST proposal
+  // layer of the walk, where a pass issues the tails of all its modules as one launch sequence (-1: no tail).  The class
+  // count is one number per net (Net.num_classes): modules that disagree are refused at construction.
+  std::deque<TailModule> mods;
   int tail_layer = -1;
-  std::vector<int> tail_cls_layers, tail_box_layers;  // per head (or single)
-  std::vector<int> tail_feat_blobs;
-  int tail_A = 0, tail_heads = 0, tail_Cf = 0;
   int tail_C = 2;   // classes (background first), 2 .. kTailMaxClasses: from the predictors' output counts
-  int tail_cls_blob = -1, tail_box_blob = -1, im_info_blob = -1, boxes_blob = -1, prob_blob = -1, data_blob = -1;
-  std::vector<double> anchors;
-  std::vector<int> sub_stride;
-  int feat_stride = 8;
-  DevBuf tail_W, tail_b;
-  bool tail_w_dirty = true;
+  int im_info_blob = -1, data_blob = -1;
+  int module_of_output(int bi) const {   // the module whose boxes / cls_prob top blob bi is, or -1
+    for (size_t j = 0; j < mods.size(); ++j)
+      if (bi == mods[j].boxes_blob || bi == mods[j].prob_blob) return (int)j;
+    return -1;
+  }
+  bool is_feat_blob(int bi) const {
+    for (auto& M : mods)
+      if (std::count(M.feat_blobs.begin(), M.feat_blobs.end(), bi)) return true;
+    return false;
+  }
   std::string proto_text;
   shf_net* clone_src = nullptr;     // lanes share the parameter tensors of the net they were cloned from
   std::shared_ptr<int> wgen = std::make_shared<int>(0);  // bumped by every param commit
-  int tail_gen = -1;
   hipEvent_t ev_mark = nullptr;
   hipEvent_t ev_logits = nullptr;  // recorded by every fused tail pass right after its logits kernel
   hipEvent_t logits_done = nullptr;  // what a later pass over this member waits for: its own ev_logits, or --
@@ -439,8 +465,6 @@ struct shf_net {
     if (fp16_mode() && amax_slots.p) HIP_THROW(hipMemsetAsync(amax_slots.p, 0, blobs.size() * 4, st));
   }
   DevBuf range_flag;  // device int: raised by a split-fp16 conv epilogue that produced |x| > 65504 (fp16 hi overflows)
-  TailWork tw;
-  DevBuf tw_logits, tw_rec, tw_keys, tw_counters;
   // Net.forward() in a split-fp16 mode on a detector graph runs the FUSED path's kernels (fused first pair, pools in the
   // convolutions' epilogues, split activation format -- the very pass shf_detect_add_level runs, so lib/test.py's ten
   // net.forward() calls give the detections of the device-resident path bit for bit) and leaves the intermediate blobs
@@ -462,7 +486,6 @@ struct shf_net {
   // shf_debug_class_lists_add; cl_units counts the units added since begin.  Grow-only, on the head only.
   DevBuf cl_dets, cl_len, cl_tiles, cl_stage;
   int cl_cap = 0, cl_units = 0;
-  int last_R = -1;   // proposal rows of the last completed forward (record_forward); -1: none yet
   float cur_im_info[3] = {0, 0, 1};
   bool use_blob_im_info = true;
 
@@ -504,18 +527,23 @@ struct shf_net {
   void build(const std::string& text, const char* caffemodel);
   void infer_shapes();
   void alloc_buffers();
-  void ensure_tail_workspace(size_t total_anchors);
+  void build_module(int mj, const std::map<int, int>& producer, std::map<int, int>& fused_by);   // the back-walk from mods[mj].layer
+  void ensure_tail_workspace(TailModule& M, size_t total_anchors);
   void commit_params(int li);
-  void build_tail_weights();
+  void build_tail_weights(TailModule& M);
   // the proposal stage's arguments (rebuilds the combined weights after a commit, sizes the workspace); `materialize`:
   // the tail also writes the cls_prob_reshape / bbox_pred blobs (Net.forward())
-  TailArgs tail_args(float im_h, float im_w, float im_scale, bool materialize);
-  float* probs_out() { return prob_blob >= 0 ? (float*)blobs[prob_blob].dev.p : (float*)tw_rec.p; }
+  TailArgs tail_args(int module, float im_h, float im_w, float im_scale, bool materialize);
+  float* probs_out(int module = 0) {
+    TailModule& M = mods[module];
+    return M.prob_blob >= 0 ? (float*)blobs[M.prob_blob].dev.p : (float*)M.tw_rec.p;
+  }
   // this lane's part of the layer walk (net_forward.cpp run_pass), none of which launches anything
   bool split16(const Layer& L) const;          // a split-fp16 kernel runs this conv (kclass 0, packed, eligible shape)
   bool absorbs_first(int li, bool fused) const;   // conv li computes its first-layer producer in its halo staging
   ConvArgs conv_args(int li, bool fused, int* flag) const;   // `flag`: the range flag of the pass
   void add_cost(int li, bool fused, int heads, double& flops, double& bytes) const;
+  void tail_cost(int module, double& flops, double& bytes) const;   // one module's tail on this lane's unit
   // one unit on this lane: its own stream, range flag and profiler
   void run_unit(bool fused, const float im_info[3], TailStep tail, bool materialize = false);
   void prepare_unit(const float* data, int data_on_device, int H, int W, hipStream_t st);
@@ -524,7 +552,7 @@ struct shf_net {
   // pass (shapes, host-newer inputs up on the pass's stream, im_info -> last_im_info), record_forward after it
   void forward();
   void stage_forward(hipStream_t st, Prof& pf);
-  void record_forward(bool plain, int R);
+  void record_forward(bool plain, const int* R);   // R[j]: module j's proposal rows
   const float* stage_nchw(int bi, bool is_input);   // an NHWC activation's NCHW image in `stage` (host_data, device_data)
   float* host_data(int bi);
   const float* device_data(int bi);   // Blob.gpu_data(): the blob's fp32 NCHW image on the device (shf_blob_device_data)
@@ -560,6 +588,9 @@ void append_units(shf_net* net, shf_net* const* srcs, int n, const int* im_w, co
                   float thresh, bool per_member, hipStream_t st = nullptr, Prof* pf = nullptr);
 // ... whose rows carry ONE foreground score: throws, naming the class count, for a net with more than two classes
 void refuse_multiclass_lists(const char* who, const shf_net* net);
+// ... and that hold ONE list per net, fed from one proposal layer's outputs: throws, naming the entry point and the module
+// count, for a net with several proposal layers (its levels go through Net.forward / forward_group and the host merge)
+void refuse_multimodule(const char* who, const shf_net* net);
 
 // ---------------------------------------------------------------------------
 // C ABI

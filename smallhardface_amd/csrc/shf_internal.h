@@ -134,6 +134,7 @@ int launch_pyramid_level(const uint8_t* im, int im_h, int im_w, double scale, in
 
 // ---- detection tail ------------------------------------------------------------
 constexpr int kTailMaxClasses = 8;   // class counts the tail kernels are instantiated for: 2 .. 8 (background + 1 .. 7)
+constexpr int kTailMaxModules = 4;   // proposal layers ("modules": one per backbone stride of an SSH-style net) per launch
 struct TailArgs {
   // per-anchor-set (dilation head) features and 1x1 weights
   int A = 3;                 // anchors per cell (== number of heads, or 1 head with A outputs)
@@ -157,6 +158,9 @@ struct TailArgs {
   float* bbox_pred_nchw = nullptr;         // (1,4A,h,w)
   int f64 = 0;               // conv mode "f64": the predictors' dot products accumulate in binary64, one rounding to fp32
   int probs_given = 0;       // diagnostics: the logits workspace already holds the class probabilities (launch_tail_inject)
+  // which proposal module of its net this entry belongs to (0 .. kTailMaxModules - 1): the entries of one module share A,
+  // Cf, the weights, the anchors and the strides -- the launch takes them from the first entry of each module
+  int module = 0;
 };
 struct TailWork {  // device workspace owned by the net, sized for the largest level seen
   float* logits = nullptr;           // [K][A][C + 4]
@@ -178,8 +182,9 @@ int launch_tail_inject(const TailArgs& a, TailWork& ws, const float* scores_nchw
                        hipStream_t s);
 // after_logits: recorded once the feature maps are consumed; phase 1 = only up to there, 2 = only the rest
 
-// the same for a GROUP of independent units (the units of an image's pyramid): ONE launch per stage.  phase 0:
-// everything; 1: counters reset + logits kernel (after_logits recorded behind it); 2: decode -> sort -> gather
+// the same for a GROUP of independent entries (the units of an image's pyramid, times the proposal modules of the net):
+// ONE launch per stage.  phase 0: everything; 1: counters reset + logits kernel (after_logits recorded behind it); 2:
+// decode -> sort -> gather.  The class count and the f64 flag are uniform; everything else an entry's module decides.
 int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* out_boxes5, float* const* out_probs,
                       int n, hipStream_t s, hipEvent_t after_logits = nullptr, int phase = 0);
 

@@ -22,7 +22,11 @@ static inline unsigned grid_for(long long n, int block = 256) {
   return (unsigned)g;
 }
 
-constexpr int TG = 16;  // members per grouped launch (the units of an image's pyramid)
+constexpr int TG = 16;  // entries per grouped launch (the units of an image's pyramid, times the net's proposal modules)
+constexpr int TM = kTailMaxModules;  // proposal modules per launch: an entry's geometry is its module's, looked up by index
+// The entry and module tables below go to the kernels by value.  HIP documents 4 KiB as the most a kernel's arguments may
+// take; hipcc for gfx950 does not enforce it (a kernel with a 4 100-byte argument compiles), so the budget is asserted here
+constexpr size_t kKernargLimit = 4096;
 
 // which member does block `b` belong to?  blk_start[q] = first block of member q (unused entries INT_MAX)
 __device__ __forceinline__ int tail_find_member(const int* blk_start, int b) {
@@ -57,21 +61,26 @@ __global__ void tail_reset_kernel(TailResetK p) {
   }
 }
 
-struct TailGM {  // per member
+struct TailGM {  // per entry: one unit's feature maps for one module
   const float* feat[8];
   int fstride[8];
   float* logits;    // [K][A][C + 4]
   int* counters;    // [1] = overflow flag
   int K, w;
+  int mod;          // index into TailGK::mod
 };
-struct TailGK {
+struct TailLM {  // per module: the predictors and the anchor extents
   const float* Wt;  // [A][C + 4][Cf]  rows: cls0 .. cls(C-1), dx, dy, dw, dh
   const float* bt;  // [A][C + 4]
   int A, Cf;
   float aw[8], ah[8];  // base anchor widths / heights (x2-x1+1)
+};
+struct TailGK {
   int blk_start[TG + 1];
+  TailLM mod[TM];
   TailGM m[TG];
 };
+static_assert(sizeof(TailGK) <= kKernargLimit, "the logits kernel's entry and module tables must fit the kernarg segment");
 
 // ---- 1x1 cls/reg convs: wave handles two pixels, 32 lanes x float4 per pixel -------------
 // F64 (conv mode "f64"): the products and the sum in binary64 (a product of two fp32 values is exact there), the bias added
@@ -83,24 +92,25 @@ __global__ __launch_bounds__(256) void tail_logits_kernel(TailGK g) {
   typedef typename std::conditional<F64, double, float>::type acc_t;
   const int mi = tail_find_member(g.blk_start, blockIdx.x);
   const TailGM& p = g.m[mi];
+  const TailLM& md = g.mod[p.mod];
   const int lb = blockIdx.x - g.blk_start[mi], lgrid = g.blk_start[mi + 1] - g.blk_start[mi];
   const int lane = threadIdx.x & 63;
   const int sub = lane >> 5, q = lane & 31;
   const long long wave = ((long long)lb * blockDim.x + threadIdx.x) >> 6;
   const long long nwaves = ((long long)lgrid * blockDim.x) >> 6;
   const long long npairs = ((long long)p.K + 1) / 2;
-  for (int a = 0; a < g.A; ++a) {
+  for (int a = 0; a < md.A; ++a) {
     const float* f = p.feat[a];
     const int fs = p.fstride[a];
     for (long long pr = wave; pr < npairs; pr += nwaves) {
       const long long k = pr * 2 + sub;
       acc_t part[NO] = {};
       if (k < p.K) {
-        for (int c0 = 0; c0 < g.Cf; c0 += 128) {
+        for (int c0 = 0; c0 < md.Cf; c0 += 128) {
           const float4 x = *(const float4*)(f + (size_t)k * fs + c0 + q * 4);
 #pragma unroll
           for (int o = 0; o < NO; ++o) {
-            const float4 wv = *(const float4*)(g.Wt + ((size_t)a * NO + o) * g.Cf + c0 + q * 4);
+            const float4 wv = *(const float4*)(md.Wt + ((size_t)a * NO + o) * md.Cf + c0 + q * 4);
             if constexpr (F64)
               part[o] += (double)x.x * (double)wv.x + (double)x.y * (double)wv.y + (double)x.z * (double)wv.z + (double)x.w * (double)wv.w;
             else
@@ -129,13 +139,13 @@ __global__ __launch_bounds__(256) void tail_logits_kernel(TailGK g) {
         }
       }
       if (q == 0 && k < p.K) {
-        float* L = p.logits + ((size_t)k * g.A + a) * NO;
+        float* L = p.logits + ((size_t)k * md.A + a) * NO;
         bool of = false;
 #pragma unroll
         for (int o = 0; o < NO; ++o) {
-          const float v = (float)(part[o] + (acc_t)g.bt[a * NO + o]);
+          const float v = (float)(part[o] + (acc_t)md.bt[a * NO + o]);
           L[o] = v;
-          if (o >= NC + 2) of |= delta_overflows(v, o == NC + 2 ? g.aw[a] : g.ah[a]);
+          if (o >= NC + 2) of |= delta_overflows(v, o == NC + 2 ? md.aw[a] : md.ah[a]);
         }
         if (of) atomicOr(&p.counters[1], 1);
       }
@@ -146,7 +156,7 @@ __global__ __launch_bounds__(256) void tail_logits_kernel(TailGK g) {
 // diagnostics: (1,C*A,h,w) probabilities (channel c*A + a) + (1,4A,h,w) deltas in the blobs' NCHW layout -> the tail's
 // [K][A][C + 4] records, raising the same overflow flag the logits kernel raises
 __global__ void tail_inject_kernel(const float* __restrict__ scores, const float* __restrict__ deltas,
-                                   float* __restrict__ logits, int K, int A, int NC, TailGK g, int* counters) {
+                                   float* __restrict__ logits, int K, int A, int NC, TailLM g, int* counters) {
   const long long total = (long long)K * A;
   for (long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x; n < total;
        n += (long long)gridDim.x * blockDim.x) {
@@ -174,25 +184,31 @@ struct DecodeGM {  // per member
   float im_h, im_w, min_size_scaled;
   float* cls_nchw;   // optional (1,C*A,h,w), channel c*A + a
   float* bbox_nchw;  // optional (1,4A,h,w)
+  int mod;           // index into DecodeGK::mod
 };
-struct DecodeGK {
+struct DecodeLM {  // per module: the anchor set and the strides
   int A;
   float anchors[32];
   int sub_stride[8];
   int feat_stride;
+};
+struct DecodeGK {
+  DecodeLM mod[TM];
   float score_thresh;
   int probs_given;   // diagnostics (shf_debug_proposal): L[0..C-1] already hold the class probabilities
   int blk_start[TG + 1];
   DecodeGM m[TG];
 };
+static_assert(sizeof(DecodeGK) <= kKernargLimit, "the decode kernel's entry and module tables must fit the kernarg segment");
 
 template <int NC>
 __global__ __launch_bounds__(256) void tail_decode_kernel(DecodeGK g) {
   constexpr int NO = NC + 4;
   const int mi = tail_find_member(g.blk_start, blockIdx.x);
   const DecodeGM& p = g.m[mi];
+  const DecodeLM& md = g.mod[p.mod];
   const int lb = blockIdx.x - g.blk_start[mi], lgrid = g.blk_start[mi + 1] - g.blk_start[mi];
-  const long long total = (long long)p.K * g.A;
+  const long long total = (long long)p.K * md.A;
   const bool clamp = p.counters[1] != 0;
   const int lane = threadIdx.x & 63;
   const long long step = (long long)lgrid * blockDim.x;
@@ -204,8 +220,8 @@ __global__ __launch_bounds__(256) void tail_decode_kernel(DecodeGK g) {
     bool cand = false;
     unsigned long long key = 0;
     if (n < total) {
-      const int a = (int)(n % g.A);
-      const int k = (int)(n / g.A);
+      const int a = (int)(n % md.A);
+      const int k = (int)(n / md.A);
       const int y = k / p.w, x = k - y * p.w;
       const float* L = p.logits + n * NO;
       // SoftmaxLayer::Forward: max, subtract, exp, sum (from class 0 upward), divide (softmax_layer.cpp:27-60)
@@ -229,7 +245,7 @@ __global__ __launch_bounds__(256) void tail_decode_kernel(DecodeGK g) {
       float dx = L[NC], dy = L[NC + 1], dw = L[NC + 2], dh = L[NC + 3];
       if (p.cls_nchw) {
 #pragma unroll
-        for (int c = 0; c < NC; ++c) p.cls_nchw[(size_t)(c * g.A + a) * p.K + k] = pr[c];
+        for (int c = 0; c < NC; ++c) p.cls_nchw[(size_t)(c * md.A + a) * p.K + k] = pr[c];
       }
       if (p.bbox_nchw) {
         p.bbox_nchw[(size_t)(a * 4 + 0) * p.K + k] = dx;
@@ -241,9 +257,9 @@ __global__ __launch_bounds__(256) void tail_decode_kernel(DecodeGK g) {
         if (dw > 50.f) dw = 5.f;
         if (dh > 50.f) dh = 5.f;
       }
-      const float sx = (float)(x * g.feat_stride), sy = (float)(y * g.feat_stride);
-      const float ax1 = g.anchors[a * 4 + 0] + sx, ay1 = g.anchors[a * 4 + 1] + sy;
-      const float ax2 = g.anchors[a * 4 + 2] + sx, ay2 = g.anchors[a * 4 + 3] + sy;
+      const float sx = (float)(x * md.feat_stride), sy = (float)(y * md.feat_stride);
+      const float ax1 = md.anchors[a * 4 + 0] + sx, ay1 = md.anchors[a * 4 + 1] + sy;
+      const float ax2 = md.anchors[a * 4 + 2] + sx, ay2 = md.anchors[a * 4 + 3] + sy;
       // bbox_transform_inv (bbox_transform.py:39-75), fp32, unfused
       const float widths = ax2 - ax1 + 1.0f, heights = ay2 - ay1 + 1.0f;
       const float ctr_x = ax1 + 0.5f * widths, ctr_y = ay1 + 0.5f * heights;
@@ -262,7 +278,7 @@ __global__ __launch_bounds__(256) void tail_decode_kernel(DecodeGK g) {
       for (int c = 0; c < NC; ++c) r[c] = pr[c];
       r[NC] = x1; r[NC + 1] = y1; r[NC + 2] = x2; r[NC + 3] = y2;
       // anchor subsampling map + _filter_boxes (proposal_layer.py:160-175,231-236)
-      const int ss = g.sub_stride[a];
+      const int ss = md.sub_stride[a];
       bool valid = (y % ss == 0) && (x % ss == 0);
       const float ws = x2 - x1 + 1.f, hs = y2 - y1 + 1.f;
       valid = valid && (ws >= p.min_size_scaled) && (hs >= p.min_size_scaled);
@@ -476,7 +492,7 @@ int launch_sort_desc_u64(unsigned long long* keys, const int* n_dev, size_t n_ma
 }
 
 // ---------------------------------------------------------------------------
-static void fill_logits_shared(const TailArgs& a, TailGK& lk) {
+static void fill_logits_shared(const TailArgs& a, TailLM& lk) {
   lk.Wt = a.wcls[0];  // combined [A][C + 4][Cf] matrix prepared by the net (see net_graph.cpp: build_tail_weights)
   lk.bt = a.bcls[0];
   lk.A = a.A; lk.Cf = a.Cf;
@@ -505,13 +521,20 @@ int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* ou
                       int n, hipStream_t s, hipEvent_t after_logits, int phase) {
   if (n < 1 || n > TG) { set_error("tail group: 1..16 units"); return -1; }
   const TailArgs& a0 = as[0];
-  if (a0.A > 8) { set_error("tail: at most 8 anchors per cell"); return -1; }
   if (a0.C < 2 || a0.C > kTailMaxClasses) { set_error("tail: 2 .. 8 classes"); return -1; }
+  // first[j]: the first entry of module j -- the launch takes the module's geometry and weights from it, and the module's
+  // other entries must agree with it
+  const TailArgs* first[TM] = {nullptr};
   for (int m = 0; m < n; ++m) {
-    const long long total = (long long)as[m].h * as[m].w * as[m].A;
+    const TailArgs& a = as[m];
+    if (a.module < 0 || a.module >= TM) { set_error("tail group: module index outside 0 .. 3"); return -1; }
+    if (a.A < 1 || a.A > 8) { set_error("tail: at most 8 anchors per cell"); return -1; }
+    const long long total = (long long)a.h * a.w * a.A;
     if ((size_t)total > wss[m]->cap_anchors) { set_error("tail: workspace too small"); return -1; }
-    if (as[m].Cf % 128) { set_error("tail: head feature width must be a multiple of 128"); return -1; }
-    if (as[m].A != a0.A || as[m].C != a0.C || as[m].Cf != a0.Cf || as[m].wcls[0] != a0.wcls[0] || as[m].f64 != a0.f64) {
+    if (a.Cf % 128) { set_error("tail: head feature width must be a multiple of 128"); return -1; }
+    if (!first[a.module]) first[a.module] = &a;
+    const TailArgs& f = *first[a.module];
+    if (a.A != f.A || a.C != a0.C || a.Cf != f.Cf || a.wcls[0] != f.wcls[0] || a.f64 != a0.f64) {
       set_error("tail group: members must share the proposal layer");
       return -1;
     }
@@ -525,8 +548,9 @@ int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* ou
       rk.n_amax[m] = wss[m]->n_amax;
     }
     hipLaunchKernelGGL(tail_reset_kernel, dim3(1), dim3(TG * 8), 0, s, rk);
-    TailGK lk;
-    fill_logits_shared(a0, lk);
+    TailGK lk = {};
+    for (int j = 0; j < TM; ++j)
+      if (first[j]) fill_logits_shared(*first[j], lk.mod[j]);
     int blocks = 0;
     for (int q = 0; q <= TG; ++q) lk.blk_start[q] = 0x7fffffff;
     for (int m = 0; m < n; ++m) {
@@ -541,6 +565,7 @@ int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* ou
       g.counters = wss[m]->counters;
       g.K = a.h * a.w;
       g.w = a.w;
+      g.mod = a.module;
       lk.blk_start[m] = blocks;
       blocks += (int)grid_for(((long long)g.K + 1) / 2 * 64);
     }
@@ -559,11 +584,16 @@ int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* ou
     SHF_HIP_OK(hipGetLastError());
     return 0;
   }
-  DecodeGK dk;
-  dk.A = a0.A;
-  for (int i = 0; i < a0.A * 4; ++i) dk.anchors[i] = a0.anchors[i];
-  for (int i = 0; i < a0.A; ++i) dk.sub_stride[i] = a0.sub_stride[i] < 1 ? 1 : a0.sub_stride[i];
-  dk.feat_stride = a0.feat_stride;
+  DecodeGK dk = {};
+  for (int j = 0; j < TM; ++j) {
+    if (!first[j]) continue;
+    const TailArgs& f = *first[j];
+    DecodeLM& md = dk.mod[j];
+    md.A = f.A;
+    for (int i = 0; i < f.A * 4; ++i) md.anchors[i] = f.anchors[i];
+    for (int i = 0; i < f.A; ++i) md.sub_stride[i] = f.sub_stride[i] < 1 ? 1 : f.sub_stride[i];
+    md.feat_stride = f.feat_stride;
+  }
   dk.score_thresh = a0.score_thresh;
   dk.probs_given = a0.probs_given;
   GatherGK gk;
@@ -583,6 +613,7 @@ int launch_tail_group(const TailArgs* as, TailWork* const* wss, float* const* ou
     d.min_size_scaled = a.min_size * a.im_scale;
     d.cls_nchw = a.cls_prob_reshape_nchw;
     d.bbox_nchw = a.bbox_pred_nchw;
+    d.mod = a.module;
     dk.blk_start[m] = dblocks;
     dblocks += (int)grid_for(total);
     GatherGM& q = gk.m[m];
@@ -621,7 +652,7 @@ int launch_tail_inject(const TailArgs& a, TailWork& ws, const float* scores_nchw
   if ((size_t)total > ws.cap_anchors) { set_error("tail: workspace too small"); return -1; }
   if (a.C < 2 || a.C > kTailMaxClasses) { set_error("tail: 2 .. 8 classes"); return -1; }
   SHF_HIP_OK(hipMemsetAsync(ws.counters, 0, 8 * sizeof(int), s));
-  TailGK lk = {};
+  TailLM lk = {};
   fill_logits_shared(a, lk);
   hipLaunchKernelGGL(tail_inject_kernel, dim3(grid_for(total)), dim3(256), 0, s, scores_nchw, deltas_nchw, ws.logits,
                      K, a.A, a.C, lk, ws.counters);

@@ -732,9 +732,10 @@ def inference_worker(rank, imdb, target_test, start, end, thresh, result_queue=N
     dets = [[[] for _ in range(start, end)] for _ in range(imdb.num_classes)]
     if fused is None:
         fused = os.environ.get("SHF_FUSED_DETECT", "1") != "0"
-    # the device-resident path keeps one detection list per image: a net with more foreground classes takes the per-unit
-    # detect() loop and its class loop
-    fused = fused and pyramid and len(cfg.TEST.LEVEL) == 0 and net.num_classes <= 2
+    # the device-resident path keeps one detection list per image, fed by one proposal layer: a net with more foreground
+    # classes, or with several proposal modules (boxes_<level> outputs), takes the per-unit detect() loop, its level loop
+    # and its class loop
+    fused = fused and pyramid and len(cfg.TEST.LEVEL) == 0 and net.num_classes <= 2 and net.num_modules == 1
 
     def progress(i):
         if rank == 0:
@@ -840,6 +841,10 @@ def pyramid_sharded_inference(imdb, target_test, thresh=0.05, strict=False, prog
         caffe.set_mode_gpu()
         caffe.set_device(dev_id)
         net = caffe.Net(str(target_test), str(cfg.TEST.MODEL), caffe.TEST)
+        if net.num_modules > 1:
+            # (the shards exchange one device list per image: shf_detect_* refuse a net with several proposal layers)
+            raise ValueError("TEST.SHARD pyramid needs a net with one proposal layer, '{}' has {} (boxes_<level> outputs): "
+                             "use TEST.SHARD images".format(target_test, net.num_modules))
         if "SHF_CONV_MODE" not in os.environ:
             net.set_conv_mode("f16x3")
         n_flip = 2 if cfg.TEST.FLIP else 1
