@@ -4,7 +4,8 @@
     python -m smallhardface_amd.build --force
 
 hipcc cross-compiles without a GPU.  The box-arithmetic kernels (tail.hip, class_lists.hip, merge.hip,
-eval.hip) and the image resize (pre.hip) are built with -ffp-contract=off so IoU / decode round like numpy and devIoU.
+eval.hip) and the image resize (pre.hip) are built with -ffp-contract=off so IoU / decode round like numpy and devIoU;
+so is the combine kernel (eltwise.hip): coeff * x and the add of an Eltwise SUM round separately.
 """
 import os
 import subprocess
@@ -21,6 +22,7 @@ SOURCES = [
     ("conv.hip", []),
     ("conv_f16x3.hip", []),
     ("misc.hip", []),
+    ("eltwise.hip", ["-ffp-contract=off"]),
     ("tail.hip", ["-ffp-contract=off"]),
     ("class_lists.hip", ["-ffp-contract=off"]),
     ("merge.hip", ["-ffp-contract=off"]),

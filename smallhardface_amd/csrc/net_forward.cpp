@@ -27,7 +27,8 @@ const char* const kProfNames[PC_COUNT] = {"conv_mfma_f32_kernel<3, 1, 128, 8, 16
                                            "conv_mfma_f16x3_w4d_kernel<true, 4, 1, 3, false, 2>", "conv_mfma_f16x3_w4d_kernel<true, 4, 1, 3, false, 4>",
                                            "conv_mfma_f16x3_heads3_kernel<true, 3>",
                                            "conv_first_kernel", "conv_direct_kernel", "conv_mfma_f64_kernel", "maxpool_kernel",
-                                           "deconv_depthwise", "detect_tail", "box_merge", "layout", "h2d_copy", "d2h_copy"};
+                                           "deconv_depthwise", "detect_tail", "box_merge", "layout", "h2d_copy", "d2h_copy",
+                                           "eltwise_combine"};
 
 int run_conv_plan(const ConvPlan& pl, hipStream_t s, Prof& prof, double flops, double bytes) {
   if (!pl.err.empty()) {
@@ -138,6 +139,61 @@ ConvArgs shf_net::conv_args(int li, bool fused, int* flag) const {
   return a;
 }
 
+bool shf_net::combine_runs(int li, bool fused) const {
+  const Layer& L = layers[li];
+  if (L.folded_into < 0) return true;
+  // a ReLU behind a copying Concat is part of the Concat's launches on both paths; the other folds are the fused path's
+  return !(fused || layers[L.folded_into].op == OP_CONCAT_COPY);
+}
+
+CombineArgs shf_net::combine_args(int li, bool fused, int member) const {
+  const Layer& L = layers[li];
+  CombineArgs a;
+  a.out = view_of(L.tops[0]);
+  a.out_amax = amax_slot(L.tops[0]);
+  auto crop_window = [&](const Layer& C, int i) {
+    a.in[i] = view_of(C.bottoms[0]);
+    a.c0[i] = C.crop_origin[1]; a.y0[i] = C.crop_origin[2]; a.x0[i] = C.crop_origin[3];
+  };
+  switch (L.op) {
+    case OP_ELTWISE:
+      a.n_in = (int)L.bottoms.size();
+      a.op = L.eop;
+      for (int i = 0; i < a.n_in; ++i) {
+        a.coeff[i] = L.coeff[i];
+        int crop = -1;   // bottom i is the top of a Crop folded into this layer: read its source through the offsets
+        for (size_t lj = 0; fused && lj < layers.size(); ++lj)
+          if (layers[lj].op == OP_CROP && layers[lj].folded_into == li && layers[lj].tops[0] == L.bottoms[i]) crop = (int)lj;
+        if (crop >= 0) crop_window(layers[crop], i);
+        else a.in[i] = view_of(L.bottoms[i]);
+      }
+      break;
+    case OP_CROP:
+      crop_window(L, 0);
+      break;
+    case OP_RELU:
+      a.in[0] = view_of(L.bottoms[0]);
+      a.act = 1;
+      a.slope = L.slope;
+      break;
+    case OP_CONCAT_COPY: {
+      int off = 0;
+      for (int j = 0; j < member; ++j) off += blobs[L.bottoms[j]].shape[1];
+      a.in[0] = view_of(L.bottoms[member]);
+      a.out.coff += off;
+      a.out.C = a.in[0].C;
+      break;
+    }
+    default:
+      throw std::runtime_error("layer '" + L.name + "' is no combine launch");
+  }
+  if (L.fold_relu >= 0 && (fused || L.op == OP_CONCAT_COPY)) {
+    a.act = 1;
+    a.slope = layers[L.fold_relu].slope;
+  }
+  return a;
+}
+
 // the profiler's flops / bytes of layer li on this lane's unit, added to `flops` / `bytes`.  `heads` = 3: the three
 // shared-weight heads of one launch; a conv that absorbs its first-layer producer is credited with that layer's flops too.
 // A conv's weights are read once per launch, however many lanes it covers: run_pass counts them.
@@ -154,6 +210,15 @@ void shf_net::add_cost(int li, bool fused, int heads, double& flops, double& byt
   if (L.op == OP_TAIL) {   // (booked at the last proposal layer, where the pass issues them: the tails of every module)
     if (li == tail_layer)
       for (int j = 0; j < (int)mods.size(); ++j) tail_cost(j, flops, bytes);
+    return;
+  }
+  if (L.op == OP_ELTWISE || L.op == OP_CROP || L.op == OP_RELU || L.op == OP_CONCAT_COPY) {
+    // the combine launch: n - 1 operations per output element, n reads and one write of it (a Crop folded into an Eltwise
+    // is read through its offsets: the same count; a folded ReLU costs nothing more; a copying Concat: every member once)
+    const double out = (double)blobs[L.tops[0]].count();
+    const int n = L.op == OP_ELTWISE ? (int)L.bottoms.size() : 1;
+    flops += (n - 1) * out;
+    bytes += 4.0 * (n + 1) * out;
     return;
   }
   const Blob& ib = blobs[L.bottoms[0]];
@@ -368,6 +433,26 @@ void run_pass(const Pass& p) {
           const auto c = cost(li, m, m + 1, 1);
           ProfScope ps(h.prof, p.s, PC_DECONV, c.first, c.second);
           CHECK_RC(launch_deconv_depthwise(in[m], out[m], w, b, L.k, L.stride, L.pad, p.s, dflag, slot[m]));
+        }
+        break;
+      }
+      case OP_ELTWISE:
+      case OP_CROP:
+      case OP_RELU:
+      case OP_CONCAT_COPY: {
+        if (!n0.combine_runs(li, fused)) break;   // applied in another layer's launch on this path
+        // one launch over the lanes of the pass; a copying Concat: one per member blob, into its channel window of the top
+        const int parts = L.op == OP_CONCAT_COPY ? (int)L.bottoms.size() : 1;
+        CombineArgs ca[kMaxGroup];
+        for (int j = 0; j < parts; ++j) {
+          for (int m = 0; m < p.n; ++m) ca[m] = p.u[m].lane->combine_args(li, fused, j);
+          auto c = cost(li, 0, p.n, 1);
+          if (L.op == OP_CONCAT_COPY) {   // (this member's share of the top)
+            const double share = (double)ca[0].out.C / std::max(1, n0.blobs[L.tops[0]].shape[1]);
+            c.first *= share; c.second *= share;
+          }
+          ProfScope ps(h.prof, p.s, PC_ELTWISE, c.first, c.second);
+          CHECK_RC_LAYER(launch_combine_group(ca, p.n, f64 ? 1 : 0, h.fp16_mode() ? flag : nullptr, p.s), L.name);
         }
         break;
       }

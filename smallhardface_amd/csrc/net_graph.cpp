@@ -399,19 +399,86 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
       if (L.group < 1 || L.nout % L.group) throw std::runtime_error("layer '" + L.name + "': group must divide num_output");
       L.op = (L.type == "Convolution") ? OP_CONV : OP_DECONV;
     } else if (L.type == "ReLU") {
-      if (L.bottoms.size() != 1 || L.tops.size() != 1 || L.bottoms[0] != L.tops[0])
-        throw std::runtime_error("ReLU '" + L.name + "': only in-place ReLU after a convolution is supported");
+      // relu_layer.cpp: max(x, 0) + negative_slope * min(x, 0), in place or not (NeuronLayer: one bottom, one top)
+      if (L.bottoms.size() != 1 || L.tops.size() != 1)
+        throw std::runtime_error("ReLU '" + L.name + "': takes exactly one bottom and one top (" + std::to_string(L.bottoms.size()) +
+                                 " / " + std::to_string(L.tops.size()) + " given)");
+      const double slope = L.msg->sub("relu_param") ? L.msg->sub("relu_param")->real("negative_slope", 0) : 0.0;
+      L.slope = (float)slope;
+      if (!std::isfinite(slope) || !std::isfinite(L.slope))
+        throw std::runtime_error("ReLU '" + L.name + "': negative_slope is not a finite fp32 number");
+      const bool in_place = L.bottoms[0] == L.tops[0];
       auto pit = producer.find(L.bottoms[0]);
-      if (pit == producer.end() || layers[pit->second].type != "Convolution")
-        throw std::runtime_error("ReLU '" + L.name + "': producer is not a Convolution");
-      if (L.msg->sub("relu_param") && L.msg->sub("relu_param")->real("negative_slope", 0) != 0)
-        throw std::runtime_error("ReLU negative_slope != 0 unsupported");
-      // nothing may read the pre-activation value between the conv and this ReLU
-      for (size_t lj = pit->second + 1; lj < li; ++lj)
-        for (int b : layers[lj].bottoms)
-          if (b == L.bottoms[0]) throw std::runtime_error("ReLU '" + L.name + "': blob read before activation");
-      layers[pit->second].relu = 1;
-      L.op = OP_SKIP;
+      if (in_place && L.slope == 0.f && pit != producer.end() && layers[pit->second].type == "Convolution") {
+        // the detector's own case: folded into the convolution's epilogue.  Nothing may read the pre-activation value
+        // between the conv and this ReLU
+        for (size_t lj = pit->second + 1; lj < li; ++lj)
+          for (int b : layers[lj].bottoms)
+            if (b == L.bottoms[0]) throw std::runtime_error("ReLU '" + L.name + "': blob read before activation");
+        layers[pit->second].relu = 1;
+        L.op = OP_SKIP;
+      } else {
+        if (std::count(inputs.begin(), inputs.end(), L.bottoms[0]))
+          throw std::runtime_error("ReLU '" + L.name + "': bottom '" + blobs[L.bottoms[0]].name + "' is a net input: the layer reads NHWC "
+                                   "activations, put a convolution in between");
+        L.op = OP_RELU;
+      }
+    } else if (L.type == "Eltwise") {
+      // EltwiseLayer::LayerSetUp / Reshape (eltwise_layer.cpp:10-40): Caffe CHECKs these and aborts, here the graph is refused
+      const std::string who = "Eltwise '" + L.name + "': ";
+      const PMsg* ep = L.msg->sub("eltwise_param");
+      const std::string opn = ep ? ep->str("operation", "SUM") : "SUM";
+      if (opn == "SUM" || opn == "1") L.eop = COMBINE_SUM;
+      else if (opn == "PROD" || opn == "0") L.eop = COMBINE_PROD;
+      else if (opn == "MAX" || opn == "2") L.eop = COMBINE_MAX;
+      else throw std::runtime_error(who + "unknown operation '" + opn + "' (PROD, SUM or MAX)");
+      if (L.bottoms.size() < 2)
+        throw std::runtime_error(who + "needs at least 2 bottoms, " + std::to_string(L.bottoms.size()) + " given");
+      if (L.bottoms.size() > (size_t)kCombineMaxIn)
+        throw std::runtime_error(who + std::to_string(L.bottoms.size()) + " bottoms: at most " + std::to_string(kCombineMaxIn) +
+                                 " are supported");
+      if (L.tops.size() != 1) throw std::runtime_error(who + "takes exactly one top");
+      if (ep)
+        for (auto c : ep->all("coeff")) L.coeff.push_back((float)std::strtod(c->scalar.c_str(), nullptr));
+      if (!L.coeff.empty() && L.coeff.size() != L.bottoms.size())
+        throw std::runtime_error(who + std::to_string(L.coeff.size()) + " coeff values for " + std::to_string(L.bottoms.size()) +
+                                 " bottoms: Eltwise takes one coefficient per bottom, or none");
+      if (!L.coeff.empty() && L.eop != COMBINE_SUM)
+        throw std::runtime_error(who + "takes coefficients only for summation (operation " + opn + ")");
+      for (float c : L.coeff)
+        if (!std::isfinite(c)) throw std::runtime_error(who + "a coeff is not a finite fp32 number");
+      if (L.coeff.empty()) L.coeff.assign(L.bottoms.size(), 1.f);
+      for (int b : L.bottoms) {
+        if (std::count(inputs.begin(), inputs.end(), b))
+          throw std::runtime_error(who + "bottom '" + blobs[b].name + "' is a net input: the layer reads NHWC activations, put a "
+                                   "convolution in between");
+        if (b == L.tops[0]) throw std::runtime_error(who + "cannot run in place on '" + blobs[b].name + "'");
+      }
+      L.op = OP_ELTWISE;
+    } else if (L.type == "Crop") {
+      // CropLayer::LayerSetUp (crop_layer.cpp:15-34)
+      const std::string who = "Crop '" + L.name + "': ";
+      if (L.bottoms.size() != 2 || L.tops.size() != 1)
+        throw std::runtime_error(who + "takes exactly two bottoms (the data and the blob that gives the size) and one top, " +
+                                 std::to_string(L.bottoms.size()) + " / " + std::to_string(L.tops.size()) + " given");
+      const PMsg* cp = L.msg->sub("crop_param");
+      int axis = geti(cp, "axis", 2);
+      if (axis < 0) axis += 4;   // (CanonicalAxisIndex of a 4-D blob)
+      if (axis < 0 || axis > 3) throw std::runtime_error(who + "axis " + std::to_string(geti(cp, "axis", 2)) + " is outside a 4-D blob");
+      if (axis == 0) throw std::runtime_error(who + "axis 0: cropping the batch axis is not supported");
+      L.crop_axis = axis;
+      if (cp)
+        for (auto o : cp->all("offset")) L.crop_offsets.push_back(atoi(o->scalar.c_str()));
+      if (L.crop_offsets.size() > 1 && (int)L.crop_offsets.size() != 4 - axis)
+        throw std::runtime_error(who + std::to_string(L.crop_offsets.size()) + " offsets for " + std::to_string(4 - axis) +
+                                 " cropped axes (axis " + std::to_string(axis) + "): give none, one for all, or one per cropped axis");
+      for (int b : L.bottoms)
+        if (std::count(inputs.begin(), inputs.end(), b))
+          throw std::runtime_error(who + "bottom '" + blobs[b].name + "' is a net input: the layer reads NHWC activations, "
+                                   "put a convolution in between");
+      if (L.bottoms[0] == L.tops[0] || L.bottoms[1] == L.tops[0])
+        throw std::runtime_error(who + "cannot run in place on '" + blobs[L.tops[0]].name + "'");
+      L.op = OP_CROP;
     } else if (L.type == "Pooling") {
       const PMsg* pp = L.msg->sub("pooling_param");
       if (pp && pp->str("pool", "MAX") != "MAX") throw std::runtime_error("only MAX pooling is supported");
@@ -469,11 +536,72 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
     if (L.type != "Concat" || fused_by.count((int)li)) continue;
     if (geti(L.msg->sub("concat_param"), "axis", 1) != 1)
       throw std::runtime_error("Concat '" + L.name + "': only channel concat is supported outside the tail");
+    // Caffe's Concat copies: its bottoms keep their values when a later in-place ReLU rewrites the top.  As views they would
+    // be rewritten with it, so such a Concat copies here too (one combine launch per member, the ReLU applied on the way
+    // when it comes directly behind) and its members keep their own buffers.
+    int rewriter = -1;
+    for (size_t lj = li + 1; lj < layers.size() && rewriter < 0; ++lj) {
+      const Layer& Q = layers[lj];
+      if (Q.op == OP_RELU && Q.bottoms[0] == Q.tops[0] && Q.tops[0] == L.tops[0]) rewriter = (int)lj;
+    }
+    if (rewriter >= 0) {
+      for (int b : L.bottoms)
+        if (std::count(inputs.begin(), inputs.end(), b))
+          throw std::runtime_error("Concat '" + L.name + "': bottom '" + blobs[b].name + "' is a net input and the top is rewritten "
+                                   "in place by ReLU '" + layers[rewriter].name + "': the copy reads NHWC activations");
+      L.op = OP_CONCAT_COPY;
+      continue;
+    }
     for (int b : L.bottoms) {
       if (blobs[b].owner >= 0 || std::count(inputs.begin(), inputs.end(), b))
         throw std::runtime_error("Concat '" + L.name + "': bottom already aliased");
       blobs[b].owner = L.tops[0];
     }
+  }
+  // ---- what the combine launches read is a plain fp32 NHWC activation (not a blob of a proposal tail)
+  for (const Layer& L : layers) {
+    if (L.op != OP_ELTWISE && L.op != OP_CROP && L.op != OP_RELU && L.op != OP_CONCAT_COPY) continue;
+    for (int b : L.bottoms)
+      if (blobs[b].kind != BK_NHWC)
+        throw std::runtime_error(L.type + " '" + L.name + "': bottom '" + blobs[b].name + "' is not an NHWC activation (it belongs to "
+                                 "a proposal tail)");
+  }
+  // ---- folds of the combine launches.  An in-place ReLU directly behind an Eltwise, a Crop or a copying Concat (nothing
+  //      reads the blob in between) is applied in that layer's launch: behind the Concat always (the two ARE one launch per
+  //      member), behind the other two on the fused path.  A Crop whose only reader is an Eltwise, and which is no net
+  //      output, is read through its offsets by that Eltwise on the fused path and never written.
+  for (size_t li = 0; li < layers.size(); ++li) {
+    Layer& R = layers[li];
+    if (R.op != OP_RELU || R.bottoms[0] != R.tops[0]) continue;
+    const int x = R.tops[0];
+    if (blobs[x].owner >= 0)   // a member of a zero-copy Concat: rewriting it AFTER the Concat would rewrite the Concat's top
+      for (size_t lc = 0; lc < li; ++lc)
+        if (layers[lc].type == "Concat" && !layers[lc].tops.empty() && layers[lc].tops[0] == blobs[x].owner)
+          throw std::runtime_error("ReLU '" + R.name + "': rewrites '" + blobs[x].name + "' in place after Concat '" + layers[lc].name +
+                                   "' has taken it as a bottom (the Concat's top is a view of its bottoms here)");
+    int prod = -1;
+    bool read_between = false;
+    for (int lj = (int)li - 1; lj >= 0 && prod < 0; --lj) {
+      if (std::count(layers[lj].tops.begin(), layers[lj].tops.end(), x)) prod = lj;
+      else if (std::count(layers[lj].bottoms.begin(), layers[lj].bottoms.end(), x)) read_between = true;
+    }
+    if (prod < 0 || read_between || layers[prod].fold_relu >= 0) continue;
+    const OpType po = layers[prod].op;
+    if (po != OP_ELTWISE && po != OP_CROP && po != OP_CONCAT_COPY) continue;
+    layers[prod].fold_relu = (int)li;
+    R.folded_into = prod;
+  }
+  for (size_t li = 0; li < layers.size(); ++li) {
+    Layer& C = layers[li];
+    if (C.op != OP_CROP || std::count(outputs.begin(), outputs.end(), C.tops[0])) continue;
+    int reader = -1, readers = 0;
+    for (size_t lj = 0; lj < layers.size(); ++lj)
+      if (lj != li && std::count(layers[lj].bottoms.begin(), layers[lj].bottoms.end(), C.tops[0])) { ++readers; reader = (int)lj; }
+    if (readers != 1 || reader < (int)li || layers[reader].op != OP_ELTWISE) continue;
+    bool source_rewritten = false;   // (an in-place layer on the Crop's bottom between the two: the Eltwise would read the new values)
+    for (int lj = (int)li + 1; lj < reader; ++lj)
+      source_rewritten = source_rewritten || std::count(layers[lj].tops.begin(), layers[lj].tops.end(), C.bottoms[0]) > 0;
+    if (!source_rewritten) C.folded_into = reader;
   }
 
   // ---- params (shapes need channel counts: run shape inference once)
@@ -683,7 +811,45 @@ void shf_net::infer_shapes() {
     } else if (L.type == "Deconvolution") {
       blobs[L.tops[0]].shape = {bs[0], L.nout, L.stride * (bs[2] - 1) + L.k - 2 * L.pad,
                                 L.stride * (bs[3] - 1) + L.k - 2 * L.pad};
+    } else if (L.type == "Eltwise") {
+      // EltwiseLayer::Reshape (eltwise_layer.cpp:32-40): every bottom has the first one's shape
+      if (bs.size() != 4)
+        throw std::runtime_error("Eltwise '" + L.name + "': bottom '" + blobs[L.bottoms[0]].name + "' is not 4-D");
+      for (int b : L.bottoms)
+        if (blobs[b].shape != bs) {
+          auto txt = [](const std::vector<int>& s) {
+            std::string o = "(";
+            for (size_t i = 0; i < s.size(); ++i) o += (i ? ", " : "") + std::to_string(s[i]);
+            return o + ")";
+          };
+          throw std::runtime_error("Eltwise '" + L.name + "': bottoms '" + blobs[L.bottoms[0]].name + "' " + txt(bs) + " and '" +
+                                   blobs[b].name + "' " + txt(blobs[b].shape) + " differ in shape");
+        }
+      blobs[L.tops[0]].shape = bs;
+    } else if (L.type == "Crop") {
+      // CropLayer::Reshape (crop_layer.cpp:36-78): axes from `axis` on take the second bottom's size, from the offset
+      const std::vector<int>& rs = blobs[L.bottoms[1]].shape;
+      for (int b : L.bottoms)
+        if (blobs[b].shape.size() != 4)
+          throw std::runtime_error("Crop '" + L.name + "': bottom '" + blobs[b].name + "' is not 4-D");
+      std::vector<int> s = bs;
+      for (int ax = 0; ax < 4; ++ax) {
+        int off = 0;
+        if (ax >= L.crop_axis) {
+          s[ax] = rs[ax];
+          if (L.crop_offsets.size() == 1) off = L.crop_offsets[0];
+          else if (L.crop_offsets.size() > 1) off = L.crop_offsets[ax - L.crop_axis];
+          if (off < 0 || (long long)off + rs[ax] > bs[ax])
+            throw std::runtime_error("Crop '" + L.name + "': axis " + std::to_string(ax) + ": size " + std::to_string(rs[ax]) +
+                                     " at offset " + std::to_string(off) + " exceeds the " + std::to_string(bs[ax]) + " of bottom '" +
+                                     blobs[L.bottoms[0]].name + "'");
+        }
+        L.crop_origin[ax] = off;
+      }
+      blobs[L.tops[0]].shape = s;
     } else if (L.type == "ReLU" || L.type == "Softmax" || L.type == "Split") {
+      if (L.op == OP_RELU && bs.size() != 4)
+        throw std::runtime_error("ReLU '" + L.name + "': bottom '" + blobs[L.bottoms[0]].name + "' is not 4-D");
       for (int t : L.tops) blobs[t].shape = bs;
     } else if (L.type == "Pooling") {
       int ho = (int)std::ceil((bs[2] + 2 * L.pad - L.k) / (double)L.stride) + 1;

@@ -155,7 +155,10 @@ enum FusedRole {
 
 void check_blob_dims(const std::vector<int>& shp, const std::string& name);   // net_graph.cpp: Blob::Reshape's limits
 
-enum OpType { OP_SKIP, OP_CONV, OP_POOL, OP_DECONV, OP_TAIL };
+// OP_ELTWISE / OP_CROP / OP_RELU / OP_CONCAT_COPY: launches of the combine kernel (eltwise.hip).  OP_RELU: a ReLU that is not
+// the in-place, slope-0 one behind a Convolution (that one is Layer::relu of the convolution, OP_SKIP); OP_CONCAT_COPY: a
+// channel Concat that copies, because a later in-place ReLU rewrites its top (every other channel Concat is a zero-copy view)
+enum OpType { OP_SKIP, OP_CONV, OP_POOL, OP_DECONV, OP_TAIL, OP_ELTWISE, OP_CROP, OP_RELU, OP_CONCAT_COPY };
 
 struct Layer {
   std::string name, type;
@@ -175,6 +178,17 @@ struct Layer {
   // siblings (same bottom, same parameter blobs); on those, the index of the dilation-1 layer.  One launch covers the three
   // when the shapes and the mode allow (plan_conv_heads3).
   int heads3_d2 = -1, heads3_d4 = -1, heads3_lead = -1;
+  // the combine launches (eltwise.hip)
+  int eop = COMBINE_COPY;          // Eltwise: its operation
+  std::vector<float> coeff;        // Eltwise SUM: one per bottom (all 1 when the prototxt gives none)
+  float slope = 0.f;               // ReLU: negative_slope
+  int crop_axis = 2;               // Crop: first cropped axis, and the origin per blob axis (set by shape inference)
+  std::vector<int> crop_offsets;   //   as the prototxt gives them: none, one, or one per cropped axis
+  int crop_origin[4] = {0, 0, 0, 0};
+  // folds of the fused path (on the per-layer path every layer runs on its own and every blob holds Caffe's values):
+  int fold_relu = -1;              // Eltwise / Crop / copying Concat: index of the in-place ReLU applied in its launch
+  int folded_into = -1;            // ReLU: the layer whose launch applies it; Crop: the Eltwise that reads through its offsets
+                                   // (a ReLU behind a copying Concat is folded on BOTH paths: the two are one launch per member)
 };
 
 extern const char* const kProfNames[PC_COUNT];   // net_forward.cpp
@@ -542,6 +556,10 @@ struct shf_net {
   bool split16(const Layer& L) const;          // a split-fp16 kernel runs this conv (kclass 0, packed, eligible shape)
   bool absorbs_first(int li, bool fused) const;   // conv li computes its first-layer producer in its halo staging
   ConvArgs conv_args(int li, bool fused, int* flag) const;   // `flag`: the range flag of the pass
+  // the combine launch of layer li (Eltwise, Crop, free-standing ReLU; `member`: which bottom of a copying Concat) with the
+  // folds the path allows, and whether the layer runs a launch of its own on that path
+  CombineArgs combine_args(int li, bool fused, int member = 0) const;
+  bool combine_runs(int li, bool fused) const;
   void add_cost(int li, bool fused, int heads, double& flops, double& bytes) const;
   void tail_cost(int module, double& flops, double& bytes) const;   // one module's tail on this lane's unit
   // one unit on this lane: its own stream, range flag and profiler

@@ -32,7 +32,9 @@ enum ProfClass {
   PC_CONV_F16X3_64_K1, PC_CONV_F16X3_PC,
   PC_CONV_F16X3_W4D_0, PC_CONV_F16X3_W4D_7 = PC_CONV_F16X3_W4D_0 + 7,   // dual-tile family: + in_split * 4 + (rows == 8) * 2 + (tiles == 1)
   PC_CONV_F16X3_PCP, PC_CONV_F16X3_K1G, PC_CONV_F16X3_W4D_D2, PC_CONV_F16X3_W4D_D4, PC_CONV_F16X3_H3,
-  PC_CONV_FIRST, PC_CONV_DIRECT, PC_CONV_F64, PC_POOL, PC_DECONV, PC_TAIL, PC_MERGE, PC_LAYOUT, PC_H2D, PC_D2H, PC_COUNT
+  PC_CONV_FIRST, PC_CONV_DIRECT, PC_CONV_F64, PC_POOL, PC_DECONV, PC_TAIL, PC_MERGE, PC_LAYOUT, PC_H2D, PC_D2H,
+  PC_ELTWISE,   // the combine kernel (eltwise.hip): Eltwise, Crop, free-standing ReLU, a copying Concat
+  PC_COUNT
 };
 
 // ---- convolution (stride 1, "same" geometry: pad == dil*(k-1)/2) ------------
@@ -126,6 +128,24 @@ int launch_deconv_depthwise_group(const View* ins, const View* outs, int n, cons
                                   int stride, int pad, hipStream_t s, int* range_flag = nullptr,
                                   unsigned* const* out_amax = nullptr);
 int launch_copy_view(const View& in, const View& out, hipStream_t s);       // concat fallback
+// the combine kernel (eltwise.hip): out = act(op over i < n_in of coeff[i] * in[i] shifted by (y0[i], x0[i], c0[i])).  Eltwise:
+// n_in 2 .. 4; Crop: COPY of one input from an offset; free-standing ReLU: COPY with the activation (out may BE in[0]'s
+// memory when no offset is set).  Input i's window (origin + the output's H, W, C) must lie inside in[i].
+constexpr int kCombineMaxIn = 4;
+enum CombineOp { COMBINE_SUM, COMBINE_PROD, COMBINE_MAX, COMBINE_COPY };
+struct CombineArgs {
+  int n_in = 1, op = COMBINE_COPY;
+  int act = 0;              // 1: max(x, 0) + slope * min(x, 0) on the result
+  float slope = 0.f;
+  float coeff[kCombineMaxIn] = {1.f, 1.f, 1.f, 1.f};   // SUM only
+  View in[kCombineMaxIn];
+  int y0[kCombineMaxIn] = {0, 0, 0, 0}, x0[kCombineMaxIn] = {0, 0, 0, 0}, c0[kCombineMaxIn] = {0, 0, 0, 0};
+  View out;
+  unsigned* out_amax = nullptr;   // the output blob's activation-exponent slot (fp16 modes) or null
+};
+// ONE launch over n <= 16 members that share the operation and the channel count (the lanes of a grouped pass); f64: SUM
+// and PROD accumulate in binary64 and round once; range_flag (fp16 modes): raised when an output leaves the fp16 range
+int launch_combine_group(const CombineArgs* as, int n, int f64, int* range_flag, hipStream_t s);
 int launch_nhwc_to_nchw(const View& in, float* out_nchw, hipStream_t s);    // blob.data read-back
 int launch_nchw_to_nhwc(const float* in_nchw, const View& out, hipStream_t s);
 // pyramid unit from the raw BGR uint8 image (pre.hip)
