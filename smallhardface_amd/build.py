@@ -36,7 +36,7 @@ SOURCES = [
     ("net_class_lists.cpp", []),
     ("net_api.cpp", []),
 ]
-HEADERS = ["shf_internal.h", "conv_common.h", "conv_lds_layout.h", "conv_f16x3_types.h", "conv_f16x3_8w.h", "conv_f16x3_w4d.h", "conv_f16x3_w4d_body.h", "conv_f16x3_pc.h", "conv_f16x3_k1.h", "conv_f16x3_h3.h", "conv_f64.h",
+HEADERS = ["shf_internal.h", "conv_common.h", "conv_lds_layout.h", "conv_f16x3_types.h", "conv_f16x3_8w.h", "conv_f16x3_w4d.h", "conv_f16x3_w4d_body.h", "conv_f16x3_pc.h", "conv_f16x3_k1.h", "conv_f16x3_h3.h", "conv_f64.h", "conv_gen.h",
            "proto_text.h", "net_internal.h", "eval.h", "blob_io.h", "class_lists.h", os.path.join("..", "..", "include", "shf_hip.h")]
 
 

@@ -19,6 +19,7 @@
 
 #include "conv_common.h"
 #include "conv_f64.h"
+#include "conv_gen.h"
 #include "shf_internal.h"
 
 namespace shf {
@@ -372,7 +373,9 @@ void pack_conv_weights(const float* w, int Cout, int Cin, int k, float* dst) {
       }
 }
 
-int conv_kernel_class(int Cin, int Cout, int k, int pad, int dil, bool in_nchw) {
+int conv_kernel_class(int Cin, int Cout, int k, int pad, int dil, bool in_nchw, int stride) {
+  // everything outside the "same" family the other classes are written for, from either input layout
+  if (stride != 1 || !((k == 3 && pad == dil) || (k == 1 && pad == 0))) return kConvClassGeneral;
   if (in_nchw) return 1;
   const bool same = (k == 3 && pad == dil && (dil == 1 || dil == 2 || dil == 4)) || (k == 1 && pad == 0);
   if (same && Cin % KC == 0 && Cout % 64 == 0) return 0;
@@ -524,6 +527,10 @@ int launch_conv_first(const float* in_nchw, const ConvArgs& a, hipStream_t s) {
   SHF_HIP_OK(hipGetLastError());
   return 0;
 }
+
+int launch_conv_gen(const ConvArgs* as, int n, hipStream_t s) { return launch_conv_gen_impl(as, n, s); }
+size_t gen_conv_weight_floats(int Cout, int Cin, int k) { return gen_conv_weight_floats_impl(Cout, Cin, k); }
+void pack_conv_weights_gen(const float* w, int Cout, int Cin, int k, float* dst) { pack_conv_weights_gen_impl(w, Cout, Cin, k, dst); }
 
 int launch_conv_direct(const ConvArgs& a, hipStream_t s) {
   const long long total = (long long)a.in.B * a.in.H * a.in.W * a.out.C;

@@ -68,7 +68,8 @@ struct ConvK {
 // The two low bits walk a 2x2 window so that the 4 consecutive C rows a lane owns
 // form one pooling window (kept for a fused 2x2 max-pool epilogue).
 // which member of the group does pixel tile `pt` belong to?
-__device__ __forceinline__ int conv_find_member(const ConvK& p, int pt) {
+template <typename K>   // (ConvK, or the general kernel's ConvGenK: any argument struct with a tile_starts table)
+__device__ __forceinline__ int conv_find_member(const K& p, int pt) {
   int mi = 0;
 #pragma unroll
   for (int q = 1; q < MAX_GROUP; ++q) mi += (pt >= p.tile_starts[q]) ? 1 : 0;
@@ -79,7 +80,8 @@ __device__ __forceinline__ int conv_find_member(const ConvK& p, int pt) {
 // ~40-instruction float sequence (two of them were ~1.5 k cycles of every block's prologue); n / d = umulhi(n, floor(2^32
 // / d) + 1) is exact while n * d < 2^32 (tile counts are < 2^20).
 __device__ __forceinline__ unsigned conv_div(unsigned n, unsigned d, unsigned inv) { return d == 1 ? n : __umulhi(n, inv); }
-__device__ __forceinline__ void conv_split_tile(const ConvMember& mem, int pt, int& b, int& ty, int& tx) {
+template <typename M>
+__device__ __forceinline__ void conv_split_tile(const M& mem, int pt, int& b, int& ty, int& tx) {
   b = (int)conv_div((unsigned)pt, (unsigned)mem.tiles_per_img, mem.inv_tiles_per_img);
   pt -= b * mem.tiles_per_img;
   ty = (int)conv_div((unsigned)pt, (unsigned)mem.tiles_x, mem.inv_tiles_x);

@@ -28,7 +28,7 @@ const char* const kProfNames[PC_COUNT] = {"conv_mfma_f32_kernel<3, 1, 128, 8, 16
                                            "conv_mfma_f16x3_heads3_kernel<true, 3>",
                                            "conv_first_kernel", "conv_direct_kernel", "conv_mfma_f64_kernel", "maxpool_kernel",
                                            "deconv_depthwise", "detect_tail", "box_merge", "layout", "h2d_copy", "d2h_copy",
-                                           "eltwise_combine"};
+                                           "eltwise_combine", "conv_mfma_gen_kernel"};
 
 int run_conv_plan(const ConvPlan& pl, hipStream_t s, Prof& prof, double flops, double bytes) {
   if (!pl.err.empty()) {
@@ -102,6 +102,8 @@ ConvArgs shf_net::conv_args(int li, bool fused, int* flag) const {
   a.wraw = (const float*)w.raw.p;
   a.wpacked = (const float*)w.packed.p;
   a.wfirst = (const float*)w.first_t.p;
+  a.wgen = (const float*)w.packed_gen.p;
+  a.stride = L.stride;
   a.wsplit16 = s16 ? (bf ? w.packed16b.p : w.packed16.p) : nullptr;
   a.wsplit16h = s16 ? (bf ? w.packed16hb.p : w.packed16h.p) : nullptr;
   a.wsplit16r = s16 ? (bf ? w.packed16rb.p : w.packed16r.p) : nullptr;
@@ -109,6 +111,8 @@ ConvArgs shf_net::conv_args(int li, bool fused, int* flag) const {
   a.bf16 = bf && s16 ? 1 : 0;
   a.f64 = f64_mode() ? 1 : 0;
   if (a.f64 && L.kclass == 1) a.img = nchw_input(L.bottoms[0]);   // (the one f64 kernel reads the first layer's NCHW image itself)
+  // ... and so does the general-geometry kernel, in every mode (a stem on the image: no layout pass)
+  if (L.kclass == kConvClassGeneral && blobs[L.bottoms[0]].kind == BK_INPUT_NCHW) a.img = nchw_input(L.bottoms[0]);
   // an fp16 mode: every producer of a map that a split-fp16 conv may read guards the fp16 range
   a.range_flag = fp16_mode() ? flag : nullptr;
   a.in_amax = amax_slot(L.bottoms[0]);
@@ -364,6 +368,12 @@ void run_pass(const Pass& p) {
         if (L.first_dst >= 0 && n0.absorbs_first(L.first_dst, fused)) break;   // computed inside the next conv's halo staging
         if (L.heads3_lead >= 0 && heads3_done == L.heads3_lead) break;        // written by the dilation-1 sibling's launch
         for (int m = 0; m < p.n; ++m) a1[m] = p.u[m].lane->conv_args(li, fused, flag);
+        if (L.kclass == kConvClassGeneral) {   // the general geometry: one launch over the lanes, in every mode (f64: its binary64 form)
+          const auto c = cost(li, 0, p.n, 1);
+          ProfScope ps(h.prof, p.s, PC_CONV_GEN, c.first, c.second);
+          CHECK_RC_LAYER(launch_conv_gen(a1, p.n, p.s), L.name);
+          break;
+        }
         if (L.kclass != 0 && !f64) {   // the first-layer kernel (NCHW image in) and the generic direct one: a launch per lane
           for (int m = 0; m < p.n; ++m) {
             const auto c = cost(li, m, m + 1, 1);

@@ -630,9 +630,6 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
     std::vector<std::vector<int>> shapes;
     if (L.type == "Convolution") {
       if (L.group != 1) throw std::runtime_error("Convolution '" + L.name + "': group != 1 unsupported");
-      if (L.stride != 1) throw std::runtime_error("Convolution '" + L.name + "': stride != 1 unsupported");
-      if (!((L.k == 3 && L.pad == L.dil) || (L.k == 1 && L.pad == 0)))
-        throw std::runtime_error("Convolution '" + L.name + "': only 3x3 pad==dilation and 1x1 pad 0 are supported");
       shapes.push_back({L.nout, cin, L.k, L.k});
     } else {
       if (L.group != cin || L.nout != cin)
@@ -658,7 +655,9 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
       L.params.push_back(pb);
     }
     if (L.type == "Convolution")
-      L.kclass = conv_kernel_class(cin, L.nout, L.k, L.pad, L.dil, blobs[L.bottoms[0]].kind == BK_INPUT_NCHW);
+      // (class 3, the general geometry: any stride / pad / kernel outside the "same" family -- no fused pool, no fused first
+      // pair, no split-format input or output: each of those plans asks for class 0 or 1)
+      L.kclass = conv_kernel_class(cin, L.nout, L.k, L.pad, L.dil, blobs[L.bottoms[0]].kind == BK_INPUT_NCHW, L.stride);
   }
   // ---- conv -> MAX 2x2/2 pool pairs that the fused (detect) path runs as one kernel
   for (size_t li = 0; li < layers.size(); ++li) {
@@ -801,11 +800,20 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
 }
 
 void shf_net::infer_shapes() {
+  // (a refusal below leaves some blobs at the refused input's shapes: whatever the next forward's input, it infers again)
+  last_data_shape.clear();
   for (auto& L : layers) {
     if (L.type == "Input") continue;
     auto& bs = blobs[L.bottoms.empty() ? 0 : L.bottoms[0]].shape;
     if (L.type == "Convolution") {
       if (bs.size() != 4) throw std::runtime_error("Convolution '" + L.name + "': 4-D bottom expected");
+      // BaseConvolutionLayer::compute_output_shape (base_conv_layer.cpp:17-29) would give a size <= 0: only a layer of the
+      // general geometry can get here (3x3 pad == dilation and 1x1 pad 0 keep the map's size)
+      const int kext = L.dil * (L.k - 1) + 1;
+      if (kext > bs[2] + 2 * L.pad || kext > bs[3] + 2 * L.pad)
+        throw std::runtime_error("Convolution '" + L.name + "': kernel extent " + std::to_string(kext) + " (dilation * (kernel_size - 1) + 1) exceeds "
+                                 "the padded input " + std::to_string(bs[2] + 2 * L.pad) + " x " + std::to_string(bs[3] + 2 * L.pad) +
+                                 " of bottom '" + blobs[L.bottoms[0]].name + "'");
       blobs[L.tops[0]].shape = {bs[0], L.nout, conv_out(bs[2], L.k, L.pad, L.stride, L.dil),
                                 conv_out(bs[3], L.k, L.pad, L.stride, L.dil)};
     } else if (L.type == "Deconvolution") {
@@ -1006,6 +1014,13 @@ void shf_net::commit_params(int li) {
           p.bf_stale = false;
         }
       }
+    }
+    if (pi == 0 && L.type == "Convolution" && L.kclass == kConvClassGeneral && !in_tail) {
+      // the general-geometry kernel's pack, K over (ky, kx, cin): its one parameter form in every conv mode
+      std::vector<float> packed(gen_conv_weight_floats(p.shape[0], p.shape[1], p.shape[2]));
+      pack_conv_weights_gen(p.host.data(), p.shape[0], p.shape[1], p.shape[2], packed.data());
+      p.packed_gen.ensure(packed.size() * 4);
+      HIP_THROW(hipMemcpy(p.packed_gen.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
     }
     if (pi == 0 && L.type == "Convolution" && L.kclass == 0 && !in_tail) {
       std::vector<float> packed(p.count());

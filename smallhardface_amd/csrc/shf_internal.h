@@ -34,6 +34,7 @@ enum ProfClass {
   PC_CONV_F16X3_PCP, PC_CONV_F16X3_K1G, PC_CONV_F16X3_W4D_D2, PC_CONV_F16X3_W4D_D4, PC_CONV_F16X3_H3,
   PC_CONV_FIRST, PC_CONV_DIRECT, PC_CONV_F64, PC_POOL, PC_DECONV, PC_TAIL, PC_MERGE, PC_LAYOUT, PC_H2D, PC_D2H,
   PC_ELTWISE,   // the combine kernel (eltwise.hip): Eltwise, Crop, free-standing ReLU, a copying Concat
+  PC_CONV_GEN,  // the general-geometry convolution (conv_gen.h), its fp32 and its f64 form
   PC_COUNT
 };
 
@@ -47,8 +48,10 @@ struct ConvArgs {
   const void* wsplit16r = nullptr; // fused first pair (conv_f16x3_pc.h): [Cin/32][tap][Cout][8 rotated 16-byte pieces], 128-byte rows
   const void* wsplit16h = nullptr; // dual-tile 4-wave kernel: [Cin/16][tap][Cout][hi16|lo16], lo UNSCALED, weights x 1/wscale_inv
   float wscale_inv = 1.f;          // ... and the power of two the epilogue multiplies back
+  const float* wgen = nullptr;     // general-geometry kernel: [ceil(K/32)][Cout][32], K over (ky, kx, cin) (conv_gen.h)
   const float* bias = nullptr;     // [Cout] or null
   int k = 3, dil = 1, pad = 1;
+  int stride = 1;                  // != 1 only on the general-geometry kernel
   int relu = 0;
   const float* img = nullptr;  // fused first layer (f16x3 only): raw NCHW image, transposed weights, bias
   const float* w1t = nullptr;
@@ -73,8 +76,15 @@ struct ConvArgs {
   unsigned* out_amax = nullptr;
   unsigned* pool_amax = nullptr;
 };
-// which kernel class a conv will use: 0 = mfma implicit GEMM, 1 = first-layer direct (NCHW in), 2 = generic direct
-int conv_kernel_class(int Cin, int Cout, int k, int pad, int dil, bool in_nchw);
+// which kernel class a conv will use: 0 = mfma implicit GEMM, 1 = first-layer direct (NCHW in), 2 = generic direct,
+// 3 = general geometry (stride != 1, or neither 3x3 pad == dilation nor 1x1 pad 0: conv_gen.h), from either input layout
+constexpr int kConvClassGeneral = 3;
+int conv_kernel_class(int Cin, int Cout, int k, int pad, int dil, bool in_nchw, int stride = 1);
+// the general-geometry kernel: ONE launch over n <= 16 members that share the layer.  `img` set: the layer reads the NCHW
+// net input itself; f64: binary64 accumulation, one rounding.  Its weight pack (made on commit for its layers only):
+int launch_conv_gen(const ConvArgs* as, int n, hipStream_t s);
+size_t gen_conv_weight_floats(int Cout, int Cin, int k);
+void pack_conv_weights_gen(const float* w, int Cout, int Cin, int k, float* dst);
 // first layer: input is the NCHW 'data' blob (B,Cin,H,W), Cin <= 8, Cout % 16 == 0
 int launch_conv_first(const float* in_nchw, const ConvArgs& a, hipStream_t s);
 int launch_conv_direct(const ConvArgs& a, hipStream_t s);
