@@ -5,7 +5,8 @@
 
 hipcc cross-compiles without a GPU.  The box-arithmetic kernels (tail.hip, class_lists.hip, merge.hip,
 eval.hip) and the image resize (pre.hip) are built with -ffp-contract=off so IoU / decode round like numpy and devIoU;
-so is the combine kernel (eltwise.hip): coeff * x and the add of an Eltwise SUM round separately.
+so is the combine kernel (eltwise.hip): coeff * x and the add of an Eltwise SUM round separately, and the channel-affine
+kernel (norm.hip): BatchNorm's subtraction and division, Scale's product and add each round once.
 """
 import os
 import subprocess
@@ -23,6 +24,7 @@ SOURCES = [
     ("conv_f16x3.hip", []),
     ("misc.hip", []),
     ("eltwise.hip", ["-ffp-contract=off"]),
+    ("norm.hip", ["-ffp-contract=off"]),
     ("tail.hip", ["-ffp-contract=off"]),
     ("class_lists.hip", ["-ffp-contract=off"]),
     ("merge.hip", ["-ffp-contract=off"]),

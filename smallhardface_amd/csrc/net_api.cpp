@@ -169,6 +169,7 @@ int shf_net_param_shape(shf_net* net, int layer, int idx, int* dims) {
 float* shf_net_param_data(shf_net* net, int layer, int idx) {
   auto& p = *net->layers[layer].params[idx];
   p.dirty = true;
+  ++p.version;
   return p.host.data();
 }
 

@@ -28,7 +28,7 @@ const char* const kProfNames[PC_COUNT] = {"conv_mfma_f32_kernel<3, 1, 128, 8, 16
                                            "conv_mfma_f16x3_heads3_kernel<true, 3>",
                                            "conv_first_kernel", "conv_direct_kernel", "conv_mfma_f64_kernel", "maxpool_kernel",
                                            "deconv_depthwise", "detect_tail", "box_merge", "layout", "h2d_copy", "d2h_copy",
-                                           "eltwise_combine", "conv_mfma_gen_kernel"};
+                                           "eltwise_combine", "conv_mfma_gen_kernel", "channel_affine"};
 
 int run_conv_plan(const ConvPlan& pl, hipStream_t s, Prof& prof, double flops, double bytes) {
   if (!pl.err.empty()) {
@@ -98,7 +98,7 @@ ConvArgs shf_net::conv_args(int li, bool fused, int* flag) const {
   a.in = view_of(L.bottoms[0]);   // (the first-layer kernel takes only its shape from it: its input is the NCHW image)
   a.out = view_of(L.tops[0]);
   a.k = L.k; a.dil = L.dil; a.pad = L.pad; a.relu = L.relu;
-  a.bias = L.params.size() > 1 ? (const float*)L.params[1]->raw.p : nullptr;
+  a.bias = conv_bias(L);   // (with a BatchNorm / Scale folded in: the effective one)
   a.wraw = (const float*)w.raw.p;
   a.wpacked = (const float*)w.packed.p;
   a.wfirst = (const float*)w.first_t.p;
@@ -138,7 +138,7 @@ ConvArgs shf_net::conv_args(int li, bool fused, int* flag) const {
     a.img = nchw_input(F.bottoms[0]);
     a.w1t = (const float*)F.params[0]->first_t.p;
     a.w1f = bf ? F.params[0]->first_frag_b.p : F.params[0]->first_frag.p;
-    a.b1 = F.params.size() > 1 ? (const float*)F.params[1]->raw.p : nullptr;
+    a.b1 = conv_bias(F);
   }
   return a;
 }
@@ -147,7 +147,43 @@ bool shf_net::combine_runs(int li, bool fused) const {
   const Layer& L = layers[li];
   if (L.folded_into < 0) return true;
   // a ReLU behind a copying Concat is part of the Concat's launches on both paths; the other folds are the fused path's
-  return !(fused || layers[L.folded_into].op == OP_CONCAT_COPY);
+  // ... and so is one behind a BatchNorm / Scale chain
+  return !(fused || layers[L.folded_into].op == OP_CONCAT_COPY || layers[L.folded_into].op == OP_NORM);
+}
+
+// the chain that layer li heads (plan_norm_layers): BatchNorm, Scale and ReLU stages with their layers' device vectors
+NormStages shf_net::norm_stages(int li) const {
+  const Layer& L = layers[li];
+  NormStages st;
+  if (L.chain_bn >= 0) {
+    const NormVecs& v = *layers[L.chain_bn].nv;
+    st.norm = 1;
+    st.m = (const float*)v.m.p; st.d = (const float*)v.d.p;
+    st.m64 = (const double*)v.m64.p; st.d64 = (const double*)v.d64.p;
+  }
+  if (L.chain_sc >= 0) {
+    const Layer& S = layers[L.chain_sc];
+    st.scale = 1;
+    st.g = (const float*)S.nv->g.p;
+    if (S.params.size() > 1) {
+      st.bias = 1;
+      st.b = (const float*)S.nv->b.p;
+    }
+  }
+  if (L.chain_relu >= 0) {
+    st.act = 1;
+    st.slope = layers[L.chain_relu].slope;
+  }
+  return st;
+}
+
+NormArgs shf_net::norm_args(int li) const {
+  const Layer& L = layers[li];
+  NormArgs a;
+  a.in = view_of(L.bottoms[0]);
+  a.out = view_of(L.tops[0]);
+  a.out_amax = amax_slot(L.tops[0]);
+  return a;
 }
 
 CombineArgs shf_net::combine_args(int li, bool fused, int member) const {
@@ -223,6 +259,16 @@ void shf_net::add_cost(int li, bool fused, int heads, double& flops, double& byt
     const int n = L.op == OP_ELTWISE ? (int)L.bottoms.size() : 1;
     flops += (n - 1) * out;
     bytes += 4.0 * (n + 1) * out;
+    return;
+  }
+  if (L.op == OP_NORM) {
+    // the channel-affine launch: one read and one write per element, and one operation per stage of the chain (normalise,
+    // scale, activation: 1 .. 3); a chain's members are booked with their head
+    const double out = (double)blobs[L.tops[0]].count();
+    if (L.folded_into < 0) {
+      bytes += 8.0 * out;
+      flops += ((L.chain_bn >= 0) + (L.chain_sc >= 0) + (L.chain_relu >= 0)) * out;
+    }
     return;
   }
   const Blob& ib = blobs[L.bottoms[0]];
@@ -464,6 +510,16 @@ void run_pass(const Pass& p) {
           ProfScope ps(h.prof, p.s, PC_ELTWISE, c.first, c.second);
           CHECK_RC_LAYER(launch_combine_group(ca, p.n, f64 ? 1 : 0, h.fp16_mode() ? flag : nullptr, p.s), L.name);
         }
+        break;
+      }
+      case OP_NORM: {
+        if (L.folded_into >= 0) break;   // a member of an in-place chain: applied in its head's launch
+        // one launch over the lanes of the pass (the stages and their vectors are the net's, shared by the lanes)
+        NormArgs na[kMaxGroup];
+        for (int m = 0; m < p.n; ++m) na[m] = p.u[m].lane->norm_args(li);
+        const auto c = cost(li, 0, p.n, 1);
+        ProfScope ps(h.prof, p.s, PC_NORM, c.first, c.second);
+        CHECK_RC_LAYER(launch_channel_affine_group(na, p.n, n0.norm_stages(li), f64 ? 1 : 0, h.fp16_mode() ? flag : nullptr, p.s), L.name);
         break;
       }
       case OP_TAIL:

@@ -479,6 +479,37 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
       if (L.bottoms[0] == L.tops[0] || L.bottoms[1] == L.tops[0])
         throw std::runtime_error(who + "cannot run in place on '" + blobs[L.tops[0]].name + "'");
       L.op = OP_CROP;
+    } else if (L.type == "BatchNorm" || L.type == "Scale") {
+      // BatchNormLayer::LayerSetUp (batch_norm_layer.cpp:10-50, inference only) / ScaleLayer::LayerSetUp (scale_layer.cpp:12-60)
+      const std::string who = L.type + " '" + L.name + "': ";
+      L.is_bn = L.type == "BatchNorm";
+      if (!L.is_bn && L.bottoms.size() == 2)
+        throw std::runtime_error(who + "the two-bottom form (the scale as a second bottom) is not supported: give the scale as the "
+                                 "layer's parameter blob");
+      if (L.bottoms.size() != 1 || L.tops.size() != 1)
+        throw std::runtime_error(who + "takes exactly one bottom and one top (" + std::to_string(L.bottoms.size()) + " / " +
+                                 std::to_string(L.tops.size()) + " given)");
+      if (L.is_bn) {
+        const PMsg* bp = L.msg->sub("batch_norm_param");
+        if (bp && bp->str("use_global_stats", "true") == "false")
+          throw std::runtime_error(who + "use_global_stats: false asks for batch statistics, which is training: only inference "
+                                   "with the stored statistics is supported");
+        const double eps = bp ? bp->real("eps", 1e-5) : 1e-5;
+        L.eps = (float)eps;
+        if (!std::isfinite(eps) || !std::isfinite(L.eps) || eps < 0)
+          throw std::runtime_error(who + "eps must be a finite, non-negative fp32 number");
+      } else {
+        const PMsg* sp = L.msg->sub("scale_param");
+        const int axis = geti(sp, "axis", 1), num_axes = geti(sp, "num_axes", 1);
+        if ((axis != 1 && axis != -3) || num_axes != 1)
+          throw std::runtime_error(who + "axis " + std::to_string(axis) + " / num_axes " + std::to_string(num_axes) +
+                                   ": only a per-channel scale (axis 1, num_axes 1) is supported");
+        L.bias_term = sp && sp->str("bias_term", "false") == "true";
+      }
+      if (std::count(inputs.begin(), inputs.end(), L.bottoms[0]))
+        throw std::runtime_error(who + "bottom '" + blobs[L.bottoms[0]].name + "' is a net input: the layer reads NHWC activations, put a "
+                                 "convolution in between");
+      L.op = OP_NORM;
     } else if (L.type == "Pooling") {
       const PMsg* pp = L.msg->sub("pooling_param");
       if (pp && pp->str("pool", "MAX") != "MAX") throw std::runtime_error("only MAX pooling is supported");
@@ -542,13 +573,13 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
     int rewriter = -1;
     for (size_t lj = li + 1; lj < layers.size() && rewriter < 0; ++lj) {
       const Layer& Q = layers[lj];
-      if (Q.op == OP_RELU && Q.bottoms[0] == Q.tops[0] && Q.tops[0] == L.tops[0]) rewriter = (int)lj;
+      if ((Q.op == OP_RELU || Q.op == OP_NORM) && Q.bottoms[0] == Q.tops[0] && Q.tops[0] == L.tops[0]) rewriter = (int)lj;
     }
     if (rewriter >= 0) {
       for (int b : L.bottoms)
         if (std::count(inputs.begin(), inputs.end(), b))
           throw std::runtime_error("Concat '" + L.name + "': bottom '" + blobs[b].name + "' is a net input and the top is rewritten "
-                                   "in place by ReLU '" + layers[rewriter].name + "': the copy reads NHWC activations");
+                                   "in place by " + layers[rewriter].type + " '" + layers[rewriter].name + "': the copy reads NHWC activations");
       L.op = OP_CONCAT_COPY;
       continue;
     }
@@ -560,7 +591,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   }
   // ---- what the combine launches read is a plain fp32 NHWC activation (not a blob of a proposal tail)
   for (const Layer& L : layers) {
-    if (L.op != OP_ELTWISE && L.op != OP_CROP && L.op != OP_RELU && L.op != OP_CONCAT_COPY) continue;
+    if (L.op != OP_ELTWISE && L.op != OP_CROP && L.op != OP_RELU && L.op != OP_CONCAT_COPY && L.op != OP_NORM) continue;
     for (int b : L.bottoms)
       if (blobs[b].kind != BK_NHWC)
         throw std::runtime_error(L.type + " '" + L.name + "': bottom '" + blobs[b].name + "' is not an NHWC activation (it belongs to "
@@ -572,13 +603,14 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   //      output, is read through its offsets by that Eltwise on the fused path and never written.
   for (size_t li = 0; li < layers.size(); ++li) {
     Layer& R = layers[li];
-    if (R.op != OP_RELU || R.bottoms[0] != R.tops[0]) continue;
+    if ((R.op != OP_RELU && R.op != OP_NORM) || R.bottoms[0] != R.tops[0]) continue;
     const int x = R.tops[0];
     if (blobs[x].owner >= 0)   // a member of a zero-copy Concat: rewriting it AFTER the Concat would rewrite the Concat's top
       for (size_t lc = 0; lc < li; ++lc)
         if (layers[lc].type == "Concat" && !layers[lc].tops.empty() && layers[lc].tops[0] == blobs[x].owner)
-          throw std::runtime_error("ReLU '" + R.name + "': rewrites '" + blobs[x].name + "' in place after Concat '" + layers[lc].name +
+          throw std::runtime_error(R.type + " '" + R.name + "': rewrites '" + blobs[x].name + "' in place after Concat '" + layers[lc].name +
                                    "' has taken it as a bottom (the Concat's top is a view of its bottoms here)");
+    if (R.op == OP_NORM) continue;   // (their chains and folds: plan_norm_layers)
     int prod = -1;
     bool read_between = false;
     for (int lj = (int)li - 1; lj >= 0 && prod < 0; --lj) {
@@ -625,10 +657,21 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   }
   for (size_t li = 0; li < layers.size(); ++li) {
     Layer& L = layers[li];
-    if (L.type != "Convolution" && L.type != "Deconvolution") continue;
+    const bool norm = L.type == "BatchNorm" || L.type == "Scale";
+    if (L.type != "Convolution" && L.type != "Deconvolution" && !norm) continue;
     const int cin = blobs[L.bottoms[0]].shape[1];
     std::vector<std::vector<int>> shapes;
-    if (L.type == "Convolution") {
+    float fill = 0.f;
+    if (norm) {
+      // BatchNorm: mean (C), variance (C), the moving-average factor (1), zero as Caffe creates them; Scale: gamma (C) from
+      // the default filler, the constant 1, and with bias_term beta (C), zero
+      if (L.is_bn) shapes = {{cin}, {cin}, {1}};
+      else {
+        shapes.push_back({cin});
+        if (L.bias_term) shapes.push_back({cin});
+        fill = 1.f;
+      }
+    } else if (L.type == "Convolution") {
       if (L.group != 1) throw std::runtime_error("Convolution '" + L.name + "': group != 1 unsupported");
       shapes.push_back({L.nout, cin, L.k, L.k});
     } else {
@@ -636,7 +679,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
         throw std::runtime_error("Deconvolution '" + L.name + "': only depthwise (group == channels) is supported");
       shapes.push_back({cin, 1, L.k, L.k});
     }
-    if (L.bias_term) shapes.push_back({L.nout});
+    if (!norm && L.bias_term) shapes.push_back({L.nout});
     auto pspecs = L.msg->all("param");
     for (size_t pi = 0; pi < shapes.size(); ++pi) {
       std::string pname = (pi < pspecs.size() && pspecs[pi]->msg) ? pspecs[pi]->msg->str("name") : "";
@@ -649,7 +692,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
       } else {
         pb = std::make_shared<ParamBlob>();
         pb->shape = shapes[pi];
-        pb->host.assign(pb->count(), 0.f);
+        pb->host.assign(pb->count(), pi == 0 ? fill : 0.f);
         if (!pname.empty()) shared_params[pname] = pb;
       }
       L.params.push_back(pb);
@@ -659,6 +702,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
       // pair, no split-format input or output: each of those plans asks for class 0 or 1)
       L.kclass = conv_kernel_class(cin, L.nout, L.k, L.pad, L.dil, blobs[L.bottoms[0]].kind == BK_INPUT_NCHW, L.stride);
   }
+  plan_norm_layers(fused_by);
   // ---- conv -> MAX 2x2/2 pool pairs that the fused (detect) path runs as one kernel
   for (size_t li = 0; li < layers.size(); ++li) {
     Layer& P = layers[li];
@@ -669,12 +713,19 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
       if (lj == li) continue;
       Layer& Q = layers[lj];
       if (Q.type == "Convolution" && !Q.tops.empty() && Q.tops[0] == x) prod = (int)lj;
-      if (Q.op == OP_SKIP && Q.type == "ReLU") continue;  // the in-place ReLU is part of the conv
+      if (Q.op == OP_SKIP && (Q.type == "ReLU" || Q.norm_conv >= 0)) continue;  // the in-place ReLU (and a folded BatchNorm / Scale) is part of the conv
       for (int bb : Q.bottoms)
         if (bb == x) ++others;
     }
     if (prod < 0 || layers[prod].op != OP_CONV || layers[prod].kclass != 0 || !layers[prod].relu) continue;
     if (blobs[x].owner >= 0 || blobs[P.tops[0]].owner >= 0) continue;
+    // a layer between the two that rewrites x in place with a launch of its own (a BatchNorm / Scale that did not fold, a
+    // ReLU that is not the convolution's epilogue): the pool must read the rewritten values, the epilogue would pool the
+    // convolution's own
+    bool rewritten = false;
+    for (size_t lj = (size_t)prod + 1; lj < li; ++lj)
+      rewritten = rewritten || (layers[lj].op != OP_SKIP && std::count(layers[lj].tops.begin(), layers[lj].tops.end(), x) > 0);
+    if (rewritten) continue;
     layers[prod].fuse_pool = (int)li;
     layers[prod].pool_only = (others == 0);
     P.fused_into = prod;
@@ -688,7 +739,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
     int next = -1, readers = 0;
     for (size_t lj = 0; lj < layers.size(); ++lj) {
       Layer& Q = layers[lj];
-      if (lj == li || (Q.op == OP_SKIP && Q.type == "ReLU")) continue;
+      if (lj == li || (Q.op == OP_SKIP && (Q.type == "ReLU" || Q.norm_conv >= 0))) continue;
       for (int bb : Q.bottoms)
         if (bb == x) { ++readers; next = (int)lj; }
     }
@@ -777,7 +828,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
       bool all_w4 = true;
       for (size_t lj = 0; lj < layers.size(); ++lj) {
         Layer& Q = layers[lj];
-        if (Q.op == OP_SKIP && Q.type == "ReLU") continue;                       // in-place, part of the conv
+        if (Q.op == OP_SKIP && (Q.type == "ReLU" || Q.norm_conv >= 0)) continue;   // in-place, part of the conv
         if (Q.op == OP_POOL && Q.fused_into >= 0 && Q.bottoms[0] == (int)bi) continue;  // folded into the producer
         for (int bb : Q.bottoms)
           if (bb == (int)bi) {
@@ -796,7 +847,8 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
     return;
   }
   if (caffemodel && caffemodel[0]) load_caffemodel(caffemodel);
-  for (size_t li = 0; li < layers.size(); ++li) commit_params((int)li);
+  for (size_t li = 0; li < layers.size(); ++li)
+    if (layers[li].norm_conv < 0) commit_params((int)li);   // (a folded BatchNorm / Scale: its convolution's commit read its blobs)
 }
 
 void shf_net::infer_shapes() {
@@ -855,6 +907,11 @@ void shf_net::infer_shapes() {
         L.crop_origin[ax] = off;
       }
       blobs[L.tops[0]].shape = s;
+    } else if (L.type == "BatchNorm" || L.type == "Scale") {
+      // per channel of a 4-D blob (batch_norm_layer.cpp:52-80; scale_layer.cpp:62-100 with axis 1, num_axes 1)
+      if (bs.size() != 4)
+        throw std::runtime_error(L.type + " '" + L.name + "': bottom '" + blobs[L.bottoms[0]].name + "' is not 4-D");
+      blobs[L.tops[0]].shape = bs;
     } else if (L.type == "ReLU" || L.type == "Softmax" || L.type == "Split") {
       if (L.op == OP_RELU && bs.size() != 4)
         throw std::runtime_error("ReLU '" + L.name + "': bottom '" + blobs[L.bottoms[0]].name + "' is not 4-D");
@@ -974,9 +1031,183 @@ void shf_net::build_tail_weights(TailModule& M) {
   M.gen = *wgen;
 }
 
+// BatchNorm / Scale: which of them are folded into their producing convolution's parameters, and which run the channel-affine
+// kernel (norm.hip), alone or as one launch of an in-place chain.  Runs behind the parameter blobs' creation (a fold needs to
+// know who shares them) and before the passes that pair convolutions with pools and first layers (they read Layer::relu).
+void shf_net::plan_norm_layers(const std::map<int, int>& fused_by) {
+  const int nl = (int)layers.size();
+  // the next layer after `from` that has blob x among its bottoms or tops, or -1
+  auto next_touch = [&](int from, int x) {
+    for (int lj = from + 1; lj < nl; ++lj) {
+      const Layer& Q = layers[lj];
+      if (std::count(Q.bottoms.begin(), Q.bottoms.end(), x) || std::count(Q.tops.begin(), Q.tops.end(), x)) return lj;
+    }
+    return -1;
+  };
+  auto in_place_on = [&](int lj, int x) {
+    const Layer& Q = layers[lj];
+    return Q.bottoms.size() == 1 && Q.tops.size() == 1 && Q.bottoms[0] == x && Q.tops[0] == x;
+  };
+  for (int li = 0; li < nl; ++li) {
+    Layer& L = layers[li];
+    if (L.op == OP_NORM) L.nv = clone_src ? clone_src->layers[li].nv : std::make_shared<NormVecs>();
+  }
+  // ---- folds: an in-place BatchNorm, an in-place Scale, or the two in that order, directly on a Convolution's top.  The
+  //      convolution is no predictor of a proposal tail and shares its parameter blobs with no other layer (their device
+  //      tensors become the effective ones).  A slope-0 in-place ReLU right behind becomes the convolution's epilogue.
+  for (int ci = 0; ci < nl; ++ci) {
+    Layer& C = layers[ci];
+    if (C.op != OP_CONV || C.type != "Convolution" || C.relu || fused_by.count(ci) || C.params.empty()) continue;
+    bool shared = false;
+    for (int lj = 0; lj < nl && !shared; ++lj)
+      if (lj != ci)
+        for (auto& q : layers[lj].params)
+          for (auto& p : C.params) shared = shared || p == q;
+    if (shared) continue;
+    const int x = C.tops[0];
+    int at = ci;
+    for (int stage = 0; stage < 2; ++stage) {   // 0: BatchNorm, 1: Scale
+      const int nx = next_touch(at, x);
+      if (nx < 0 || layers[nx].op != OP_NORM || !in_place_on(nx, x) || layers[nx].is_bn != (stage == 0)) continue;
+      (stage == 0 ? C.fold_bn : C.fold_sc) = nx;
+      layers[nx].norm_conv = ci;
+      layers[nx].op = OP_SKIP;
+      at = nx;
+    }
+    if (at == ci) continue;
+    C.fold_bias = clone_src ? clone_src->layers[ci].fold_bias : std::make_shared<ParamBlob>();
+    if (!clone_src) {
+      C.fold_bias->shape = {C.nout};
+      C.fold_bias->host.assign(C.nout, 0.f);
+    }
+    const int nx = next_touch(at, x);
+    if (nx >= 0 && layers[nx].op == OP_RELU && in_place_on(nx, x) && layers[nx].slope == 0.f && layers[nx].folded_into < 0) {
+      C.relu = 1;
+      layers[nx].op = OP_SKIP;
+    }
+  }
+  // ---- chains of what is left: consecutive in-place BatchNorm -> Scale -> ReLU on the head's top, nothing reading in between
+  for (int li = 0; li < nl; ++li) {
+    Layer& Hd = layers[li];
+    if (Hd.op != OP_NORM || Hd.folded_into >= 0) continue;
+    (Hd.is_bn ? Hd.chain_bn : Hd.chain_sc) = li;
+    const int x = Hd.tops[0];
+    int at = li;
+    for (;;) {
+      const int nx = next_touch(at, x);
+      if (nx < 0 || !in_place_on(nx, x) || layers[nx].folded_into >= 0) break;
+      Layer& Q = layers[nx];
+      if (Q.op == OP_NORM && !Q.is_bn && Hd.chain_sc < 0) {   // (a Scale behind the BatchNorm; never a second one, never a BatchNorm behind a Scale)
+        Hd.chain_sc = nx;
+        Q.folded_into = li;
+        at = nx;
+        continue;
+      }
+      if (Q.op == OP_RELU) {
+        Hd.chain_relu = nx;
+        Q.folded_into = li;
+      }
+      break;
+    }
+  }
+}
+
+// the per-channel vectors of a BatchNorm / Scale layer on the device, from its fp32 blobs.  BatchNorm in Caffe's operation
+// order (batch_norm_layer.cpp:98-105, 117-123): sf = blob2 == 0 ? 0 : 1 / blob2, m = blob0 * sf, d = sqrt(blob1 * sf + eps),
+// every step rounded to fp32; for conv mode "f64" the same steps in binary64.
+void shf_net::derive_norm(int li) {
+  Layer& L = layers[li];
+  if (!L.nv) return;   // (folded into a convolution: its commit reads the blobs themselves)
+  const size_t C = L.params[0]->count();
+  auto up = [&](DevBuf& buf, const void* src, size_t bytes) {
+    buf.ensure(bytes);
+    HIP_THROW(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice));
+  };
+  if (L.is_bn) {
+    const float* mean = L.params[0]->host.data();
+    const float* var = L.params[1]->host.data();
+    const float f = L.params[2]->host[0];
+    const float sf = f == 0.f ? 0.f : 1.f / f;
+    const double sf64 = f == 0.f ? 0.0 : 1.0 / (double)f;
+    std::vector<float> m(C), d(C);
+    std::vector<double> m64(C), d64(C);
+    for (size_t c = 0; c < C; ++c) {
+      m[c] = mean[c] * sf;
+      const float v = var[c] * sf;
+      const float ve = v + L.eps;
+      d[c] = std::sqrt(ve);
+      m64[c] = (double)mean[c] * sf64;
+      d64[c] = std::sqrt((double)var[c] * sf64 + (double)L.eps);
+    }
+    up(L.nv->m, m.data(), C * 4);
+    up(L.nv->d, d.data(), C * 4);
+    up(L.nv->m64, m64.data(), C * 8);
+    up(L.nv->d64, d64.data(), C * 8);
+  } else {
+    up(L.nv->g, L.params[0]->host.data(), C * 4);
+    if (L.params.size() > 1) up(L.nv->b, L.params[1]->host.data(), C * 4);
+  }
+}
+
+// W_eff[o, ...] = fp32(W[o, ...] * s[o]), b_eff[o] = fp32((b[o] - blob0[o] * sf) * s[o] + beta[o]) with
+// s = gamma / sqrt(blob1 * sf + eps): binary64 from the fp32 blobs, one rounding per value (gamma = 1 without a Scale,
+// s = gamma and no mean without a BatchNorm, b = 0 without a bias blob, beta = 0 without bias_term)
+void shf_net::fold_conv_params(int li, std::vector<float>& w_eff, std::vector<float>& b_eff) const {
+  const Layer& L = layers[li];
+  const ParamBlob& w = *L.params[0];
+  const int co = w.shape[0];
+  const size_t K = w.count() / (size_t)co;
+  const Layer* bn = L.fold_bn >= 0 ? &layers[L.fold_bn] : nullptr;
+  const Layer* sc = L.fold_sc >= 0 ? &layers[L.fold_sc] : nullptr;
+  double sf = 0.0;
+  if (bn) {
+    const float f = bn->params[2]->host[0];
+    sf = f == 0.f ? 0.0 : 1.0 / (double)f;
+  }
+  w_eff.resize(w.count());
+  b_eff.resize(co);
+  for (int o = 0; o < co; ++o) {
+    const double gamma = sc ? (double)sc->params[0]->host[o] : 1.0;
+    const double s = bn ? gamma / std::sqrt((double)bn->params[1]->host[o] * sf + (double)bn->eps) : gamma;
+    const double mean = bn ? (double)bn->params[0]->host[o] * sf : 0.0;
+    const double b = L.params.size() > 1 ? (double)L.params[1]->host[o] : 0.0;
+    const double beta = sc && sc->params.size() > 1 ? (double)sc->params[1]->host[o] : 0.0;
+    for (size_t r = 0; r < K; ++r) w_eff[(size_t)o * K + r] = (float)((double)w.host[(size_t)o * K + r] * s);
+    b_eff[o] = (float)((b - mean) * s + beta);
+  }
+}
+
+std::vector<unsigned long long> shf_net::fold_versions(int li) const {
+  const Layer& L = layers[li];
+  std::vector<unsigned long long> v;
+  for (int lj : {li, L.fold_bn, L.fold_sc})
+    if (lj >= 0)
+      for (auto& p : layers[lj].params) v.push_back(p->version);
+  return v;
+}
+
 void shf_net::commit_params(int li) {
   Layer& L = layers[li];
   if (L.params.empty()) return;
+  if (L.type == "BatchNorm" || L.type == "Scale") {
+    // (the vectors are shared by every lane: nothing may be in flight on any stream)
+    HIP_THROW(hipDeviceSynchronize());
+    for (auto& p : L.params) p->dirty = false;
+    if (L.norm_conv >= 0) {   // part of a convolution's parameters: re-fold and re-pack those
+      // ... unless that convolution's last commit already folded these very values: a commit of the convolution, its
+      // BatchNorm and its Scale after one load packs once, not three times
+      if (layers[L.norm_conv].fold_bias->folded_from != fold_versions(L.norm_conv)) commit_params(L.norm_conv);
+      return;
+    }
+    derive_norm(li);
+    ++*wgen;
+    return;
+  }
+  // a convolution with a BatchNorm / Scale folded in: every device tensor below is built from the effective parameters,
+  // the blobs themselves (Net.params) keep Caffe's unfolded values
+  std::vector<float> w_eff, b_eff;
+  const bool folded = L.fold_bias != nullptr;
+  if (folded) fold_conv_params(li, w_eff, b_eff);
   // the dual-tile family's weight pack (16-channel slabs, unscaled low parts): its 3x3 layers, and the 1x1 GEMM kernel's
   auto wants_family_pack = [](const Layer& Q, const ParamBlob& w) {
     return conv_f16x3_family_shape(w.shape[1], w.shape[0], Q.k, Q.pad, Q.dil, false, true);
@@ -991,24 +1222,26 @@ void shf_net::commit_params(int li) {
     }
   for (size_t pi = 0; pi < L.params.size(); ++pi) {
     ParamBlob& p = *L.params[pi];
+    // what the device tensors are built from: the blob, or for a folded convolution its effective weights / bias
+    const float* const src = !folded ? p.host.data() : pi == 0 ? w_eff.data() : b_eff.data();
     p.raw.ensure(p.count() * 4);
-    HIP_THROW(hipMemcpy(p.raw.p, p.host.data(), p.count() * 4, hipMemcpyHostToDevice));
+    HIP_THROW(hipMemcpy(p.raw.p, src, p.count() * 4, hipMemcpyHostToDevice));
     if (pi == 0 && L.type == "Convolution" && L.kclass == 1) {
       // first layer: (Cout, Cin*k*k) -> (Cin*k*k, Cout) so a wave's 16 output channels are one uniform run
       const int co = p.shape[0], K = (int)(p.count() / p.shape[0]);
       std::vector<float> t(p.count());
       for (int o = 0; o < co; ++o)
-        for (int r = 0; r < K; ++r) t[(size_t)r * co + o] = p.host[(size_t)o * K + r];
+        for (int r = 0; r < K; ++r) t[(size_t)r * co + o] = src[(size_t)o * K + r];
       p.first_t.ensure(t.size() * 4);
       HIP_THROW(hipMemcpy(p.first_t.p, t.data(), t.size() * 4, hipMemcpyHostToDevice));
       if (co == 64 && K == 27) {  // the shape the fused producer/consumer kernel computes on the matrix cores
         std::vector<uint16_t> fr(kFirstConvFragHalfs);
-        pack_first_conv_frags(p.host.data(), fr.data());
+        pack_first_conv_frags(src, fr.data());
         p.first_frag.ensure(fr.size() * 2);
         HIP_THROW(hipMemcpy(p.first_frag.p, fr.data(), fr.size() * 2, hipMemcpyHostToDevice));
         p.bf_stale = true;
         if (conv_mode == 4) {
-          pack_first_conv_frags(p.host.data(), fr.data(), true);
+          pack_first_conv_frags(src, fr.data(), true);
           p.first_frag_b.ensure(fr.size() * 2);
           HIP_THROW(hipMemcpy(p.first_frag_b.p, fr.data(), fr.size() * 2, hipMemcpyHostToDevice));
           p.bf_stale = false;
@@ -1018,13 +1251,13 @@ void shf_net::commit_params(int li) {
     if (pi == 0 && L.type == "Convolution" && L.kclass == kConvClassGeneral && !in_tail) {
       // the general-geometry kernel's pack, K over (ky, kx, cin): its one parameter form in every conv mode
       std::vector<float> packed(gen_conv_weight_floats(p.shape[0], p.shape[1], p.shape[2]));
-      pack_conv_weights_gen(p.host.data(), p.shape[0], p.shape[1], p.shape[2], packed.data());
+      pack_conv_weights_gen(src, p.shape[0], p.shape[1], p.shape[2], packed.data());
       p.packed_gen.ensure(packed.size() * 4);
       HIP_THROW(hipMemcpy(p.packed_gen.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
     }
     if (pi == 0 && L.type == "Convolution" && L.kclass == 0 && !in_tail) {
       std::vector<float> packed(p.count());
-      pack_conv_weights(p.host.data(), p.shape[0], p.shape[1], p.shape[2], packed.data());
+      pack_conv_weights(src, p.shape[0], p.shape[1], p.shape[2], packed.data());
       p.packed.ensure(packed.size() * 4);
       HIP_THROW(hipMemcpy(p.packed.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
       // a commit in fp32 mode leaves the split-fp16 packs behind: shf_net_set_conv_mode re-packs them on the way back
@@ -1033,18 +1266,18 @@ void shf_net::commit_params(int li) {
       if (conv_mode == 4 && conv_f16x3_eligible(p.shape[1], p.shape[0], L.k, L.pad, L.dil)) {
         // bf16 mode: hi = bf16(w) bit patterns in the same layouts (no range check: bf16 has fp32's exponent range)
         std::vector<uint16_t> sp(split16_conv_weight_halfs(p.shape[0], p.shape[1], p.shape[2]));
-        pack_conv_weights_split16(p.host.data(), p.shape[0], p.shape[1], p.shape[2], sp.data(), true);
+        pack_conv_weights_split16(src, p.shape[0], p.shape[1], p.shape[2], sp.data(), true);
         p.packed16b.ensure(sp.size() * 2);
         HIP_THROW(hipMemcpy(p.packed16b.p, sp.data(), sp.size() * 2, hipMemcpyHostToDevice));
         if (L.first_src >= 0 && p.shape[0] == 64 && p.shape[1] == 64) {   // the fused first pair's own pack
           std::vector<uint16_t> sr(split16r_conv_weight_halfs(p.shape[0], p.shape[1], p.shape[2]));
-          pack_conv_weights_split16r(p.host.data(), p.shape[0], p.shape[1], p.shape[2], sr.data(), true);
+          pack_conv_weights_split16r(src, p.shape[0], p.shape[1], p.shape[2], sr.data(), true);
           p.packed16rb.ensure(sr.size() * 2);
           HIP_THROW(hipMemcpy(p.packed16rb.p, sr.data(), sr.size() * 2, hipMemcpyHostToDevice));
         }
         if (wants_family_pack(L, p)) {
           std::vector<uint16_t> sh(split16h_conv_weight_halfs(p.shape[0], p.shape[1], p.shape[2]));
-          pack_conv_weights_split16h(p.host.data(), p.shape[0], p.shape[1], p.shape[2], sh.data(), true);
+          pack_conv_weights_split16h(src, p.shape[0], p.shape[1], p.shape[2], sh.data(), true);
           p.packed16hb.ensure(sh.size() * 2);
           HIP_THROW(hipMemcpy(p.packed16hb.p, sh.data(), sh.size() * 2, hipMemcpyHostToDevice));
         }
@@ -1053,30 +1286,37 @@ void shf_net::commit_params(int li) {
       if (conv_mode >= 1 && conv_mode <= 3 && conv_f16x3_eligible(p.shape[1], p.shape[0], L.k, L.pad, L.dil)) {
         // split-fp16 keeps hi = fp16(w): a weight beyond the fp16 range would become inf (the reference is fp32
         // everywhere, caffe/python/caffe/_caffe.cpp:46-48) -- refuse the mode instead of computing garbage
-        for (float w : p.host)
-          if (!(std::fabs(w) <= 65504.f))
+        for (size_t wi = 0; wi < p.count(); ++wi)
+          if (!(std::fabs(src[wi]) <= 65504.f))
             throw std::runtime_error("layer '" + L.name + "': a weight is outside the fp16 range (|w| > 65504 or not "
                                      "finite); the split-fp16 conv mode cannot represent it -- use conv mode fp32");
         std::vector<uint16_t> sp(split16_conv_weight_halfs(p.shape[0], p.shape[1], p.shape[2]));
-        pack_conv_weights_split16(p.host.data(), p.shape[0], p.shape[1], p.shape[2], sp.data());
+        pack_conv_weights_split16(src, p.shape[0], p.shape[1], p.shape[2], sp.data());
         p.packed16.ensure(sp.size() * 2);
         HIP_THROW(hipMemcpy(p.packed16.p, sp.data(), sp.size() * 2, hipMemcpyHostToDevice));
         if (L.first_src >= 0 && p.shape[0] == 64 && p.shape[1] == 64) {   // the fused first pair's own pack
           std::vector<uint16_t> sr(split16r_conv_weight_halfs(p.shape[0], p.shape[1], p.shape[2]));
-          pack_conv_weights_split16r(p.host.data(), p.shape[0], p.shape[1], p.shape[2], sr.data());
+          pack_conv_weights_split16r(src, p.shape[0], p.shape[1], p.shape[2], sr.data());
           p.packed16r.ensure(sr.size() * 2);
           HIP_THROW(hipMemcpy(p.packed16r.p, sr.data(), sr.size() * 2, hipMemcpyHostToDevice));
         }
         p.split_stale = false;
         if (wants_family_pack(L, p)) {
           std::vector<uint16_t> sh(split16h_conv_weight_halfs(p.shape[0], p.shape[1], p.shape[2]));
-          p.wscale_inv = pack_conv_weights_split16h(p.host.data(), p.shape[0], p.shape[1], p.shape[2], sh.data());
+          p.wscale_inv = pack_conv_weights_split16h(src, p.shape[0], p.shape[1], p.shape[2], sh.data());
           p.packed16h.ensure(sh.size() * 2);
           HIP_THROW(hipMemcpy(p.packed16h.p, sh.data(), sh.size() * 2, hipMemcpyHostToDevice));
         }
       }
     }
     p.dirty = false;
+  }
+  if (folded) {   // the bias the launches read: a convolution without a bias blob gets one here
+    ParamBlob& fb = *L.fold_bias;
+    fb.host = b_eff;
+    fb.folded_from = fold_versions(li);
+    fb.raw.ensure(b_eff.size() * 4);
+    HIP_THROW(hipMemcpy(fb.raw.p, b_eff.data(), b_eff.size() * 4, hipMemcpyHostToDevice));
   }
   ++*wgen;
 }
@@ -1096,6 +1336,7 @@ void shf_net::load_caffemodel(const std::string& path) {
                                    "'; shape mismatch.");
         std::copy(sl.blobs[i].data.begin(), sl.blobs[i].data.end(), p.host.begin());
         p.dirty = true;
+        ++p.version;
       }
     }
   }

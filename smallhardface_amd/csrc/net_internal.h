@@ -113,6 +113,10 @@ struct ParamBlob {
   float wscale_inv = 1.f;  // packed16h: the power of two its weights were scaled by, inverted
   bool dirty = true;
   bool split_stale = false;  // committed while the net was in fp32 mode: packed16 / packed16h hold OLDER weights
+  // bumped whenever the host values may have been written (shf_net_param_data, load_caffemodel).  On a folded convolution's
+  // effective bias: the versions of the blobs (its own, the BatchNorm's, the Scale's) its last commit folded
+  unsigned long long version = 0;
+  std::vector<unsigned long long> folded_from;
   size_t count() const {
     size_t c = 1;
     for (int d : shape) c *= (size_t)d;
@@ -159,7 +163,16 @@ void check_blob_dims(const std::vector<int>& shp, const std::string& name);   //
 // OP_ELTWISE / OP_CROP / OP_RELU / OP_CONCAT_COPY: launches of the combine kernel (eltwise.hip).  OP_RELU: a ReLU that is not
 // the in-place, slope-0 one behind a Convolution (that one is Layer::relu of the convolution, OP_SKIP); OP_CONCAT_COPY: a
 // channel Concat that copies, because a later in-place ReLU rewrites its top (every other channel Concat is a zero-copy view)
-enum OpType { OP_SKIP, OP_CONV, OP_POOL, OP_DECONV, OP_TAIL, OP_ELTWISE, OP_CROP, OP_RELU, OP_CONCAT_COPY };
+// OP_NORM: a BatchNorm or Scale layer that runs the channel-affine kernel (norm.hip), alone or as the head or a member of an
+// in-place chain; one that is folded into its producing convolution is OP_SKIP with Layer::norm_conv set
+enum OpType { OP_SKIP, OP_CONV, OP_POOL, OP_DECONV, OP_TAIL, OP_ELTWISE, OP_CROP, OP_RELU, OP_CONCAT_COPY, OP_NORM };
+
+// what a BatchNorm / Scale layer's launch reads: per-channel vectors derived from its blobs at commit time (derive_norm),
+// shared by the lanes of a net like a weight pack
+struct NormVecs {
+  DevBuf m, d, m64, d64;   // BatchNorm: mean * sf and sqrt(var * sf + eps), in fp32 (Caffe's operation order) and in binary64
+  DevBuf g, b;             // Scale: its blobs
+};
 
 struct Layer {
   std::string name, type;
@@ -190,6 +203,16 @@ struct Layer {
   int fold_relu = -1;              // Eltwise / Crop / copying Concat: index of the in-place ReLU applied in its launch
   int folded_into = -1;            // ReLU: the layer whose launch applies it; Crop: the Eltwise that reads through its offsets
                                    // (a ReLU behind a copying Concat is folded on BOTH paths: the two are one launch per member)
+  // BatchNorm / Scale.  Unfolded, consecutive in-place BatchNorm, Scale, ReLU on one blob with no reader in between are ONE
+  // launch on both paths: the first is the chain's head, the others carry folded_into = head.  Folded, they are part of the
+  // convolution's parameters and run no launch.
+  bool is_bn = false;              // BatchNorm (else Scale)
+  float eps = 1e-5f;               // BatchNorm: batch_norm_param.eps
+  std::shared_ptr<NormVecs> nv;
+  int chain_bn = -1, chain_sc = -1, chain_relu = -1;   // on a chain's head: its stages' layers (the head is one of them)
+  int norm_conv = -1;              // BatchNorm / Scale: the convolution it is folded into
+  int fold_bn = -1, fold_sc = -1;  // Convolution: the BatchNorm / Scale folded into its parameters
+  std::shared_ptr<ParamBlob> fold_bias;   // ... and the effective bias its launches read (params keeps Caffe's unfolded blobs)
 };
 
 extern const char* const kProfNames[PC_COUNT];   // net_forward.cpp
@@ -561,6 +584,18 @@ struct shf_net {
   // folds the path allows, and whether the layer runs a launch of its own on that path
   CombineArgs combine_args(int li, bool fused, int member = 0) const;
   bool combine_runs(int li, bool fused) const;
+  // the channel-affine launch of the chain that layer li heads: its stages (the same on every lane) and this lane's views
+  NormStages norm_stages(int li) const;
+  NormArgs norm_args(int li) const;
+  void plan_norm_layers(const std::map<int, int>& fused_by);   // net_graph.cpp: folds into convolutions, in-place chains
+  void derive_norm(int li);                                    // a BatchNorm / Scale layer's device vectors from its blobs
+  // a convolution's effective parameters with its BatchNorm / Scale folded in (binary64, one rounding per value)
+  void fold_conv_params(int li, std::vector<float>& w_eff, std::vector<float>& b_eff) const;
+  std::vector<unsigned long long> fold_versions(int li) const;   // the versions of every blob convolution li folds
+  const float* conv_bias(const Layer& L) const {
+    if (L.fold_bias) return (const float*)L.fold_bias->raw.p;
+    return L.params.size() > 1 ? (const float*)L.params[1]->raw.p : nullptr;
+  }
   void add_cost(int li, bool fused, int heads, double& flops, double& bytes) const;
   void tail_cost(int module, double& flops, double& bytes) const;   // one module's tail on this lane's unit
   // one unit on this lane: its own stream, range flag and profiler

@@ -35,6 +35,7 @@ enum ProfClass {
   PC_CONV_FIRST, PC_CONV_DIRECT, PC_CONV_F64, PC_POOL, PC_DECONV, PC_TAIL, PC_MERGE, PC_LAYOUT, PC_H2D, PC_D2H,
   PC_ELTWISE,   // the combine kernel (eltwise.hip): Eltwise, Crop, free-standing ReLU, a copying Concat
   PC_CONV_GEN,  // the general-geometry convolution (conv_gen.h), its fp32 and its f64 form
+  PC_NORM,      // the channel-affine kernel (norm.hip): BatchNorm, Scale and the ReLU behind them, where they are not folded
   PC_COUNT
 };
 
@@ -156,6 +157,22 @@ struct CombineArgs {
 // ONE launch over n <= 16 members that share the operation and the channel count (the lanes of a grouped pass); f64: SUM
 // and PROD accumulate in binary64 and round once; range_flag (fp16 modes): raised when an output leaves the fp16 range
 int launch_combine_group(const CombineArgs* as, int n, int f64, int* range_flag, hipStream_t s);
+// the channel-affine kernel (norm.hip): out = act(((in - m[c]) / d[c]) * g[c] + b[c]), every stage optional and rounded as the
+// layer it stands for (BatchNorm: one subtraction, one division; Scale: a product, then an add; ReLU as the combine kernel's).
+// The per-channel vectors live on the device, C values each, as the host derived them at commit time.
+struct NormStages {
+  int norm = 0, scale = 0, bias = 0, act = 0;   // BatchNorm; Scale's product; Scale's bias_term; ReLU
+  float slope = 0.f;
+  const float *m = nullptr, *d = nullptr, *g = nullptr, *b = nullptr;
+  const double *m64 = nullptr, *d64 = nullptr;  // conv mode "f64": mean and denominator formed in binary64
+};
+struct NormArgs {
+  View in, out;                   // the same B, H, W, C; each its own pixel pitch and channel offset; out may BE in
+  unsigned* out_amax = nullptr;   // the output blob's activation-exponent slot (fp16 modes) or null
+};
+// ONE launch over n <= 16 members that share the stages and the channel count (the lanes of a grouped pass); f64: the
+// expression in binary64, rounded once, the activation on the rounded value; range_flag as launch_combine_group's
+int launch_channel_affine_group(const NormArgs* as, int n, const NormStages& st, int f64, int* range_flag, hipStream_t s);
 int launch_nhwc_to_nchw(const View& in, float* out_nchw, hipStream_t s);    // blob.data read-back
 int launch_nchw_to_nhwc(const float* in_nchw, const View& out, hipStream_t s);
 // pyramid unit from the raw BGR uint8 image (pre.hip)
