@@ -6,7 +6,8 @@
 hipcc cross-compiles without a GPU.  The box-arithmetic kernels (tail.hip, class_lists.hip, merge.hip,
 eval.hip) and the image resize (pre.hip) are built with -ffp-contract=off so IoU / decode round like numpy and devIoU;
 so is the combine kernel (eltwise.hip): coeff * x and the add of an Eltwise SUM round separately, and the channel-affine
-kernel (norm.hip): BatchNorm's subtraction and division, Scale's product and add each round once.
+kernel (norm.hip): BatchNorm's subtraction and division, Scale's product and add each round once; and the depthwise
+convolution (conv_dw.hip): its fmaf chain, bias add and binary64 form are compiled as written.
 """
 import os
 import subprocess
@@ -22,6 +23,7 @@ ARCH = "gfx950"
 SOURCES = [
     ("conv.hip", []),
     ("conv_f16x3.hip", []),
+    ("conv_dw.hip", ["-ffp-contract=off"]),
     ("misc.hip", []),
     ("eltwise.hip", ["-ffp-contract=off"]),
     ("norm.hip", ["-ffp-contract=off"]),

@@ -28,7 +28,7 @@ const char* const kProfNames[PC_COUNT] = {"conv_mfma_f32_kernel<3, 1, 128, 8, 16
                                            "conv_mfma_f16x3_heads3_kernel<true, 3>",
                                            "conv_first_kernel", "conv_direct_kernel", "conv_mfma_f64_kernel", "maxpool_kernel",
                                            "deconv_depthwise", "detect_tail", "box_merge", "layout", "h2d_copy", "d2h_copy",
-                                           "eltwise_combine", "conv_mfma_gen_kernel", "channel_affine"};
+                                           "eltwise_combine", "conv_mfma_gen_kernel", "channel_affine", "conv_dw_kernel"};
 
 int run_conv_plan(const ConvPlan& pl, hipStream_t s, Prof& prof, double flops, double bytes) {
   if (!pl.err.empty()) {
@@ -44,7 +44,7 @@ int run_conv_plan(const ConvPlan& pl, hipStream_t s, Prof& prof, double flops, d
 }  // namespace shf
 
 static double conv_flops(const Layer& L, const std::vector<int>& in, const std::vector<int>& out) {
-  return 2.0 * out[0] * out[2] * out[3] * (double)L.nout * in[1] * L.k * L.k;
+  return 2.0 * out[0] * out[2] * out[3] * (double)L.nout * (in[1] / std::max(L.group, 1)) * L.k * L.k;
 }
 
 // the proposal stage's arguments for the current shapes (also sizes the workspace: pre_nms_topN is shared with the
@@ -103,6 +103,10 @@ ConvArgs shf_net::conv_args(int li, bool fused, int* flag) const {
   a.wpacked = (const float*)w.packed.p;
   a.wfirst = (const float*)w.first_t.p;
   a.wgen = (const float*)w.packed_gen.p;
+  if (L.kclass == kConvClassDepthwise) {   // (group == bottom channels: the multiplier is what is left of num_output)
+    a.wdw = (const float*)w.packed_dw.p;
+    a.dw_mult = L.nout / L.group;
+  }
   a.stride = L.stride;
   a.wsplit16 = s16 ? (bf ? w.packed16b.p : w.packed16.p) : nullptr;
   a.wsplit16h = s16 ? (bf ? w.packed16hb.p : w.packed16h.p) : nullptr;
@@ -414,6 +418,12 @@ void run_pass(const Pass& p) {
         if (L.first_dst >= 0 && n0.absorbs_first(L.first_dst, fused)) break;   // computed inside the next conv's halo staging
         if (L.heads3_lead >= 0 && heads3_done == L.heads3_lead) break;        // written by the dilation-1 sibling's launch
         for (int m = 0; m < p.n; ++m) a1[m] = p.u[m].lane->conv_args(li, fused, flag);
+        if (L.kclass == kConvClassDepthwise) {   // depthwise: one launch over the lanes, in every mode (f64: its binary64 form)
+          const auto c = cost(li, 0, p.n, 1);
+          ProfScope ps(h.prof, p.s, PC_CONV_DW, c.first, c.second);
+          CHECK_RC_LAYER(launch_conv_dw(a1, p.n, p.s), L.name);
+          break;
+        }
         if (L.kclass == kConvClassGeneral) {   // the general geometry: one launch over the lanes, in every mode (f64: its binary64 form)
           const auto c = cost(li, 0, p.n, 1);
           ProfScope ps(h.prof, p.s, PC_CONV_GEN, c.first, c.second);

@@ -672,8 +672,20 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
         fill = 1.f;
       }
     } else if (L.type == "Convolution") {
-      if (L.group != 1) throw std::runtime_error("Convolution '" + L.name + "': group != 1 unsupported");
-      shapes.push_back({L.nout, cin, L.k, L.k});
+      // group 1, or depthwise: group == bottom channels, num_output a multiple of them (Layer setup checked that group divides
+      // num_output); the blob is (Cout, Cin / group, k, k) as Caffe shapes it
+      if (L.group != 1) {
+        if (L.group != cin)
+          throw std::runtime_error("Convolution '" + L.name + "': group != 1 unsupported unless depthwise (group == bottom channels); got group " +
+                                   std::to_string(L.group) + " of " + std::to_string(cin));
+        if (blobs[L.bottoms[0]].kind == BK_INPUT_NCHW)
+          throw std::runtime_error("Convolution '" + L.name + "': depthwise (group " + std::to_string(L.group) + ") on bottom '" +
+                                   blobs[L.bottoms[0]].name + "', a net input: the layer reads NHWC activations, put a convolution in between");
+        if (fused_by.count((int)li))
+          throw std::runtime_error("Convolution '" + L.name + "': depthwise (group " + std::to_string(L.group) + ") as a predictor of ProposalLayer '" +
+                                   layers[mods[fused_by[(int)li]].layer].name + "': the tail's combined weight matrix takes dense predictors");
+      }
+      shapes.push_back({L.nout, cin / L.group, L.k, L.k});
     } else {
       if (L.group != cin || L.nout != cin)
         throw std::runtime_error("Deconvolution '" + L.name + "': only depthwise (group == channels) is supported");
@@ -700,7 +712,9 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
     if (L.type == "Convolution")
       // (class 3, the general geometry: any stride / pad / kernel outside the "same" family -- no fused pool, no fused first
       // pair, no split-format input or output: each of those plans asks for class 0 or 1)
-      L.kclass = conv_kernel_class(cin, L.nout, L.k, L.pad, L.dil, blobs[L.bottoms[0]].kind == BK_INPUT_NCHW, L.stride);
+      // (class 4, depthwise: likewise none of those plans, whatever its geometry)
+      L.kclass = L.group != 1 ? kConvClassDepthwise
+                              : conv_kernel_class(cin, L.nout, L.k, L.pad, L.dil, blobs[L.bottoms[0]].kind == BK_INPUT_NCHW, L.stride);
   }
   plan_norm_layers(fused_by);
   // ---- conv -> MAX 2x2/2 pool pairs that the fused (detect) path runs as one kernel
@@ -1254,6 +1268,13 @@ void shf_net::commit_params(int li) {
       pack_conv_weights_gen(src, p.shape[0], p.shape[1], p.shape[2], packed.data());
       p.packed_gen.ensure(packed.size() * 4);
       HIP_THROW(hipMemcpy(p.packed_gen.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
+    }
+    if (pi == 0 && L.type == "Convolution" && L.kclass == kConvClassDepthwise) {
+      // the depthwise kernel's tap-major pack: its one parameter form in every conv mode
+      std::vector<float> packed(p.count());
+      pack_conv_weights_dw(src, p.shape[0], p.shape[2], packed.data());
+      p.packed_dw.ensure(packed.size() * 4);
+      HIP_THROW(hipMemcpy(p.packed_dw.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
     }
     if (pi == 0 && L.type == "Convolution" && L.kclass == 0 && !in_tail) {
       std::vector<float> packed(p.count());

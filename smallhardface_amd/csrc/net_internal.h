@@ -108,6 +108,7 @@ struct ParamBlob {
   std::vector<float> host;
   DevBuf raw, packed, packed16, packed16h, packed16r, first_t, first_frag;   // (packed16r: the fused first pair's rotated-row pack)
   DevBuf packed_gen;   // the general-geometry kernel's pack (conv_gen.h): allocated for layers of that class only
+  DevBuf packed_dw;    // the depthwise kernel's tap-major pack (conv_dw.hip): allocated for layers of that class only
   DevBuf packed16b, packed16hb, packed16rb, first_frag_b;   // the same three packs for conv mode "bf16" (built on first use of the mode)
   bool bf_stale = true;                         // ... and whether they hold the current weights
   float wscale_inv = 1.f;  // packed16h: the power of two its weights were scaled by, inverted

@@ -36,6 +36,7 @@ enum ProfClass {
   PC_ELTWISE,   // the combine kernel (eltwise.hip): Eltwise, Crop, free-standing ReLU, a copying Concat
   PC_CONV_GEN,  // the general-geometry convolution (conv_gen.h), its fp32 and its f64 form
   PC_NORM,      // the channel-affine kernel (norm.hip): BatchNorm, Scale and the ReLU behind them, where they are not folded
+  PC_CONV_DW,   // the depthwise convolution (conv_dw.hip), its fp32 and its f64 form
   PC_COUNT
 };
 
@@ -50,6 +51,8 @@ struct ConvArgs {
   const void* wsplit16h = nullptr; // dual-tile 4-wave kernel: [Cin/16][tap][Cout][hi16|lo16], lo UNSCALED, weights x 1/wscale_inv
   float wscale_inv = 1.f;          // ... and the power of two the epilogue multiplies back
   const float* wgen = nullptr;     // general-geometry kernel: [ceil(K/32)][Cout][32], K over (ky, kx, cin) (conv_gen.h)
+  const float* wdw = nullptr;      // depthwise kernel: tap-major [k*k][Cout] (conv_dw.hip)
+  int dw_mult = 0;                 // depthwise layers: the channel multiplier Cout / Cin (>= 1); 0 = not depthwise
   const float* bias = nullptr;     // [Cout] or null
   int k = 3, dil = 1, pad = 1;
   int stride = 1;                  // != 1 only on the general-geometry kernel
@@ -79,13 +82,21 @@ struct ConvArgs {
 };
 // which kernel class a conv will use: 0 = mfma implicit GEMM, 1 = first-layer direct (NCHW in), 2 = generic direct,
 // 3 = general geometry (stride != 1, or neither 3x3 pad == dilation nor 1x1 pad 0: conv_gen.h), from either input layout
+// 4 = depthwise (group == Cin, Cout = m * Cin: conv_dw.hip), decided by the graph from the layer's group, never by
+// conv_kernel_class
 constexpr int kConvClassGeneral = 3;
+constexpr int kConvClassDepthwise = 4;
 int conv_kernel_class(int Cin, int Cout, int k, int pad, int dil, bool in_nchw, int stride = 1);
 // the general-geometry kernel: ONE launch over n <= 16 members that share the layer.  `img` set: the layer reads the NCHW
 // net input itself; f64: binary64 accumulation, one rounding.  Its weight pack (made on commit for its layers only):
 int launch_conv_gen(const ConvArgs* as, int n, hipStream_t s);
 size_t gen_conv_weight_floats(int Cout, int Cin, int k);
 void pack_conv_weights_gen(const float* w, int Cout, int Cin, int k, float* dst);
+// the depthwise kernel: ONE launch over n <= 16 members that share the layer; any square kernel, stride, pad, dilation and
+// channel multiplier; f64: binary64 accumulation, one rounding.  Its weight pack (made on commit for its layers only):
+// (Cout, 1, k, k) -> [k*k][Cout]
+int launch_conv_dw(const ConvArgs* as, int n, hipStream_t s);
+void pack_conv_weights_dw(const float* w, int Cout, int k, float* dst);
 // first layer: input is the NCHW 'data' blob (B,Cin,H,W), Cin <= 8, Cout % 16 == 0
 int launch_conv_first(const float* in_nchw, const ConvArgs& a, hipStream_t s);
 int launch_conv_direct(const ConvArgs& a, hipStream_t s);
