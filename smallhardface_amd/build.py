@@ -7,7 +7,8 @@ hipcc cross-compiles without a GPU.  The box-arithmetic kernels (tail.hip, class
 eval.hip) and the image resize (pre.hip) are built with -ffp-contract=off so IoU / decode round like numpy and devIoU;
 so is the combine kernel (eltwise.hip): coeff * x and the add of an Eltwise SUM round separately, and the channel-affine
 kernel (norm.hip): BatchNorm's subtraction and division, Scale's product and add each round once; and the depthwise
-convolution (conv_dw.hip): its fmaf chain, bias add and binary64 form are compiled as written.
+convolution (conv_dw.hip): its fmaf chain, bias add and binary64 form are compiled as written; and the channel-L2-norm
+kernel (l2norm.hip): Normalize's sum of squares, + eps, square root, division and product each round once.
 """
 import os
 import subprocess
@@ -27,6 +28,7 @@ SOURCES = [
     ("misc.hip", []),
     ("eltwise.hip", ["-ffp-contract=off"]),
     ("norm.hip", ["-ffp-contract=off"]),
+    ("l2norm.hip", ["-ffp-contract=off"]),
     ("tail.hip", ["-ffp-contract=off"]),
     ("class_lists.hip", ["-ffp-contract=off"]),
     ("merge.hip", ["-ffp-contract=off"]),

@@ -35,7 +35,7 @@ def _field(no, wire, payload):
 
 
 def _blob(arr):
-    arr = np.ascontiguousarray(arr, dtype=np.float32)
+    arr = np.asarray(arr, dtype=np.float32, order="C")   # (keeps a blob of 0 axes, a channel_shared Normalize scale, at 0 axes)
     shape = _field(1, 2, b"".join(_varint(d) for d in arr.shape))  # BlobShape.dim (packed int64)
     return _field(7, 2, shape) + _field(5, 2, arr.tobytes())       # BlobProto.shape, .data (packed float)
 

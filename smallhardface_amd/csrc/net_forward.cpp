@@ -28,7 +28,8 @@ const char* const kProfNames[PC_COUNT] = {"conv_mfma_f32_kernel<3, 1, 128, 8, 16
                                            "conv_mfma_f16x3_heads3_kernel<true, 3>",
                                            "conv_first_kernel", "conv_direct_kernel", "conv_mfma_f64_kernel", "maxpool_kernel",
                                            "deconv_depthwise", "detect_tail", "box_merge", "layout", "h2d_copy", "d2h_copy",
-                                           "eltwise_combine", "conv_mfma_gen_kernel", "channel_affine", "conv_dw_kernel"};
+                                           "eltwise_combine", "conv_mfma_gen_kernel", "channel_affine", "conv_dw_kernel",
+                                           "channel_l2norm"};
 
 int run_conv_plan(const ConvPlan& pl, hipStream_t s, Prof& prof, double flops, double bytes) {
   if (!pl.err.empty()) {
@@ -273,6 +274,13 @@ void shf_net::add_cost(int li, bool fused, int heads, double& flops, double& byt
       bytes += 8.0 * out;
       flops += ((L.chain_bn >= 0) + (L.chain_sc >= 0) + (L.chain_relu >= 0)) * out;
     }
+    return;
+  }
+  if (L.op == OP_L2NORM) {
+    // the channel-L2-norm launch: one read and one write per element; a square-and-add, a division and a product
+    const double out = (double)blobs[L.tops[0]].count();
+    bytes += 8.0 * out;
+    flops += 3.0 * out;
     return;
   }
   const Blob& ib = blobs[L.bottoms[0]];
@@ -530,6 +538,16 @@ void run_pass(const Pass& p) {
         const auto c = cost(li, 0, p.n, 1);
         ProfScope ps(h.prof, p.s, PC_NORM, c.first, c.second);
         CHECK_RC_LAYER(launch_channel_affine_group(na, p.n, n0.norm_stages(li), f64 ? 1 : 0, h.fp16_mode() ? flag : nullptr, p.s), L.name);
+        break;
+      }
+      case OP_L2NORM: {
+        // one launch over the lanes of the pass (the scale vector is the net's, shared by the lanes)
+        NormArgs na[kMaxGroup];
+        for (int m = 0; m < p.n; ++m) na[m] = p.u[m].lane->norm_args(li);
+        const auto c = cost(li, 0, p.n, 1);
+        ProfScope ps(h.prof, p.s, PC_L2NORM, c.first, c.second);
+        CHECK_RC_LAYER(launch_channel_l2norm_group(na, p.n, (const float*)L.nv->g.p, L.eps, f64 ? 1 : 0, h.fp16_mode() ? flag : nullptr, p.s),
+                       L.name);
         break;
       }
       case OP_TAIL:

@@ -510,6 +510,29 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
         throw std::runtime_error(who + "bottom '" + blobs[L.bottoms[0]].name + "' is a net input: the layer reads NHWC activations, put a "
                                  "convolution in between");
       L.op = OP_NORM;
+    } else if (L.type == "Normalize") {
+      // NormalizeLayer::LayerSetUp (normalize_layer.cpp:11-63), the per-pixel form only
+      const std::string who = "Normalize '" + L.name + "': ";
+      if (L.bottoms.size() != 1 || L.tops.size() != 1)
+        throw std::runtime_error(who + "takes exactly one bottom and one top (" + std::to_string(L.bottoms.size()) + " / " +
+                                 std::to_string(L.tops.size()) + " given)");
+      const PMsg* np = L.msg->sub("norm_param");
+      if (!np || np->str("across_spatial", "true") != "false")
+        throw std::runtime_error(who + "across_spatial: true (the default of norm_param) normalises over the whole image, which is "
+                                 "not supported: write across_spatial: false for the per-pixel norm over channels");
+      L.l2_shared = np->str("channel_shared", "true") == "true";
+      const double eps = np->real("eps", 1e-10);
+      L.eps = (float)eps;
+      if (!std::isfinite(eps) || !std::isfinite(L.eps) || eps < 0)
+        throw std::runtime_error(who + "eps must be a finite, non-negative fp32 number");
+      // the scale blob before a model is loaded: a constant filler's value; no filler, 1 (normalize_layer.cpp:44-51); any
+      // other filler type is random in Caffe and stays 1 here -- the caffemodel brings the values
+      const PMsg* sf = np->sub("scale_filler");
+      if (sf && sf->str("type", "constant") == "constant") L.l2_fill = (float)sf->real("value", 0.0);
+      if (std::count(inputs.begin(), inputs.end(), L.bottoms[0]))
+        throw std::runtime_error(who + "bottom '" + blobs[L.bottoms[0]].name + "' is a net input: the layer reads NHWC activations, put a "
+                                 "convolution in between");
+      L.op = OP_L2NORM;
     } else if (L.type == "Pooling") {
       const PMsg* pp = L.msg->sub("pooling_param");
       if (pp && pp->str("pool", "MAX") != "MAX") throw std::runtime_error("only MAX pooling is supported");
@@ -573,7 +596,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
     int rewriter = -1;
     for (size_t lj = li + 1; lj < layers.size() && rewriter < 0; ++lj) {
       const Layer& Q = layers[lj];
-      if ((Q.op == OP_RELU || Q.op == OP_NORM) && Q.bottoms[0] == Q.tops[0] && Q.tops[0] == L.tops[0]) rewriter = (int)lj;
+      if ((Q.op == OP_RELU || Q.op == OP_NORM || Q.op == OP_L2NORM) && Q.bottoms[0] == Q.tops[0] && Q.tops[0] == L.tops[0]) rewriter = (int)lj;
     }
     if (rewriter >= 0) {
       for (int b : L.bottoms)
@@ -591,7 +614,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   }
   // ---- what the combine launches read is a plain fp32 NHWC activation (not a blob of a proposal tail)
   for (const Layer& L : layers) {
-    if (L.op != OP_ELTWISE && L.op != OP_CROP && L.op != OP_RELU && L.op != OP_CONCAT_COPY && L.op != OP_NORM) continue;
+    if (L.op != OP_ELTWISE && L.op != OP_CROP && L.op != OP_RELU && L.op != OP_CONCAT_COPY && L.op != OP_NORM && L.op != OP_L2NORM) continue;
     for (int b : L.bottoms)
       if (blobs[b].kind != BK_NHWC)
         throw std::runtime_error(L.type + " '" + L.name + "': bottom '" + blobs[b].name + "' is not an NHWC activation (it belongs to "
@@ -603,7 +626,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   //      output, is read through its offsets by that Eltwise on the fused path and never written.
   for (size_t li = 0; li < layers.size(); ++li) {
     Layer& R = layers[li];
-    if ((R.op != OP_RELU && R.op != OP_NORM) || R.bottoms[0] != R.tops[0]) continue;
+    if ((R.op != OP_RELU && R.op != OP_NORM && R.op != OP_L2NORM) || R.bottoms[0] != R.tops[0]) continue;
     const int x = R.tops[0];
     if (blobs[x].owner >= 0)   // a member of a zero-copy Concat: rewriting it AFTER the Concat would rewrite the Concat's top
       for (size_t lc = 0; lc < li; ++lc)
@@ -611,6 +634,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
           throw std::runtime_error(R.type + " '" + R.name + "': rewrites '" + blobs[x].name + "' in place after Concat '" + layers[lc].name +
                                    "' has taken it as a bottom (the Concat's top is a view of its bottoms here)");
     if (R.op == OP_NORM) continue;   // (their chains and folds: plan_norm_layers)
+    if (R.op == OP_L2NORM) continue;   // (a launch of its own, never folded)
     int prod = -1;
     bool read_between = false;
     for (int lj = (int)li - 1; lj >= 0 && prod < 0; --lj) {
@@ -657,12 +681,17 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   }
   for (size_t li = 0; li < layers.size(); ++li) {
     Layer& L = layers[li];
-    const bool norm = L.type == "BatchNorm" || L.type == "Scale";
+    const bool l2 = L.type == "Normalize";
+    const bool norm = L.type == "BatchNorm" || L.type == "Scale" || l2;
     if (L.type != "Convolution" && L.type != "Deconvolution" && !norm) continue;
     const int cin = blobs[L.bottoms[0]].shape[1];
     std::vector<std::vector<int>> shapes;
     float fill = 0.f;
-    if (norm) {
+    if (l2) {
+      // Normalize: the scale, (C) or with channel_shared a blob of 0 axes and one value (normalize_layer.cpp:36-41), from its filler
+      shapes.push_back(L.l2_shared ? std::vector<int>() : std::vector<int>{cin});
+      fill = L.l2_fill;
+    } else if (norm) {
       // BatchNorm: mean (C), variance (C), the moving-average factor (1), zero as Caffe creates them; Scale: gamma (C) from
       // the default filler, the constant 1, and with bias_term beta (C), zero
       if (L.is_bn) shapes = {{cin}, {cin}, {1}};
@@ -926,6 +955,11 @@ void shf_net::infer_shapes() {
       if (bs.size() != 4)
         throw std::runtime_error(L.type + " '" + L.name + "': bottom '" + blobs[L.bottoms[0]].name + "' is not 4-D");
       blobs[L.tops[0]].shape = bs;
+    } else if (L.type == "Normalize") {
+      // per pixel of a 4-D blob, over its channels (normalize_layer.cpp:64-82)
+      if (bs.size() != 4)
+        throw std::runtime_error("Normalize '" + L.name + "': bottom '" + blobs[L.bottoms[0]].name + "' is not 4-D");
+      blobs[L.tops[0]].shape = bs;
     } else if (L.type == "ReLU" || L.type == "Softmax" || L.type == "Split") {
       if (L.op == OP_RELU && bs.size() != 4)
         throw std::runtime_error("ReLU '" + L.name + "': bottom '" + blobs[L.bottoms[0]].name + "' is not 4-D");
@@ -1064,7 +1098,7 @@ void shf_net::plan_norm_layers(const std::map<int, int>& fused_by) {
   };
   for (int li = 0; li < nl; ++li) {
     Layer& L = layers[li];
-    if (L.op == OP_NORM) L.nv = clone_src ? clone_src->layers[li].nv : std::make_shared<NormVecs>();
+    if (L.op == OP_NORM || L.op == OP_L2NORM) L.nv = clone_src ? clone_src->layers[li].nv : std::make_shared<NormVecs>();
   }
   // ---- folds: an in-place BatchNorm, an in-place Scale, or the two in that order, directly on a Convolution's top.  The
   //      convolution is no predictor of a proposal tail and shares its parameter blobs with no other layer (their device
@@ -1214,6 +1248,19 @@ void shf_net::commit_params(int li) {
       return;
     }
     derive_norm(li);
+    ++*wgen;
+    return;
+  }
+  if (L.type == "Normalize") {
+    // the scale the launch reads: C values, a channel_shared blob's one value broadcast, so that the kernel has one form
+    HIP_THROW(hipDeviceSynchronize());   // (shared by every lane: nothing may be in flight on any stream)
+    ParamBlob& p = *L.params[0];
+    const size_t C = (size_t)blobs[L.bottoms[0]].shape[1];
+    std::vector<float> sc(C);
+    for (size_t c = 0; c < C; ++c) sc[c] = p.host[L.l2_shared ? 0 : c];
+    L.nv->g.ensure(C * 4);
+    HIP_THROW(hipMemcpy(L.nv->g.p, sc.data(), C * 4, hipMemcpyHostToDevice));
+    p.dirty = false;
     ++*wgen;
     return;
   }

@@ -166,13 +166,14 @@ void check_blob_dims(const std::vector<int>& shp, const std::string& name);   //
 // channel Concat that copies, because a later in-place ReLU rewrites its top (every other channel Concat is a zero-copy view)
 // OP_NORM: a BatchNorm or Scale layer that runs the channel-affine kernel (norm.hip), alone or as the head or a member of an
 // in-place chain; one that is folded into its producing convolution is OP_SKIP with Layer::norm_conv set
-enum OpType { OP_SKIP, OP_CONV, OP_POOL, OP_DECONV, OP_TAIL, OP_ELTWISE, OP_CROP, OP_RELU, OP_CONCAT_COPY, OP_NORM };
+// OP_L2NORM: a Normalize layer (across_spatial: false): one launch of the channel-L2-norm kernel (l2norm.hip), never folded
+enum OpType { OP_SKIP, OP_CONV, OP_POOL, OP_DECONV, OP_TAIL, OP_ELTWISE, OP_CROP, OP_RELU, OP_CONCAT_COPY, OP_NORM, OP_L2NORM };
 
 // what a BatchNorm / Scale layer's launch reads: per-channel vectors derived from its blobs at commit time (derive_norm),
 // shared by the lanes of a net like a weight pack
 struct NormVecs {
   DevBuf m, d, m64, d64;   // BatchNorm: mean * sf and sqrt(var * sf + eps), in fp32 (Caffe's operation order) and in binary64
-  DevBuf g, b;             // Scale: its blobs
+  DevBuf g, b;             // Scale: its blobs.  Normalize: g = its scale, C values (a channel_shared one broadcast on commit)
 };
 
 struct Layer {
@@ -208,7 +209,9 @@ struct Layer {
   // launch on both paths: the first is the chain's head, the others carry folded_into = head.  Folded, they are part of the
   // convolution's parameters and run no launch.
   bool is_bn = false;              // BatchNorm (else Scale)
-  float eps = 1e-5f;               // BatchNorm: batch_norm_param.eps
+  float eps = 1e-5f;               // BatchNorm: batch_norm_param.eps; Normalize: norm_param.eps (default 1e-10)
+  bool l2_shared = false;          // Normalize: channel_shared (the blob has 0 axes and one value)
+  float l2_fill = 1.f;             // Normalize: what the blob holds before a model is loaded (a constant scale_filler's value)
   std::shared_ptr<NormVecs> nv;
   int chain_bn = -1, chain_sc = -1, chain_relu = -1;   // on a chain's head: its stages' layers (the head is one of them)
   int norm_conv = -1;              // BatchNorm / Scale: the convolution it is folded into

@@ -37,6 +37,7 @@ enum ProfClass {
   PC_CONV_GEN,  // the general-geometry convolution (conv_gen.h), its fp32 and its f64 form
   PC_NORM,      // the channel-affine kernel (norm.hip): BatchNorm, Scale and the ReLU behind them, where they are not folded
   PC_CONV_DW,   // the depthwise convolution (conv_dw.hip), its fp32 and its f64 form
+  PC_L2NORM,    // the channel-L2-norm kernel (l2norm.hip): Normalize with across_spatial: false
   PC_COUNT
 };
 
@@ -184,6 +185,10 @@ struct NormArgs {
 // ONE launch over n <= 16 members that share the stages and the channel count (the lanes of a grouped pass); f64: the
 // expression in binary64, rounded once, the activation on the rounded value; range_flag as launch_combine_group's
 int launch_channel_affine_group(const NormArgs* as, int n, const NormStages& st, int f64, int* range_flag, hipStream_t s);
+// the channel-L2-norm kernel (l2norm.hip): out[c] = (in[c] / sqrt(sum_c in[c]^2 + eps)) * scale[c] per pixel, `scale` C values
+// on the device.  ONE launch over n <= 16 members that share the layer (the lanes of a grouped pass); f64: the expression in
+// binary64, rounded once; range_flag as launch_combine_group's
+int launch_channel_l2norm_group(const NormArgs* as, int n, const float* scale, float eps, int f64, int* range_flag, hipStream_t s);
 int launch_nhwc_to_nchw(const View& in, float* out_nchw, hipStream_t s);    // blob.data read-back
 int launch_nchw_to_nhwc(const float* in_nchw, const View& out, hipStream_t s);
 // pyramid unit from the raw BGR uint8 image (pre.hip)
