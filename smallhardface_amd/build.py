@@ -8,7 +8,8 @@ eval.hip) and the image resize (pre.hip) are built with -ffp-contract=off so IoU
 so is the combine kernel (eltwise.hip): coeff * x and the add of an Eltwise SUM round separately, and the channel-affine
 kernel (norm.hip): BatchNorm's subtraction and division, Scale's product and add each round once; and the depthwise
 convolution (conv_dw.hip): its fmaf chain, bias add and binary64 form are compiled as written; and the channel-L2-norm
-kernel (l2norm.hip): Normalize's sum of squares, + eps, square root, division and product each round once.
+kernel (l2norm.hip): Normalize's sum of squares, + eps, square root, division and product each round once; and the pooling
+kernel (pool.hip): AVE's sum and its one division.
 """
 import os
 import subprocess
@@ -29,6 +30,7 @@ SOURCES = [
     ("eltwise.hip", ["-ffp-contract=off"]),
     ("norm.hip", ["-ffp-contract=off"]),
     ("l2norm.hip", ["-ffp-contract=off"]),
+    ("pool.hip", ["-ffp-contract=off"]),
     ("tail.hip", ["-ffp-contract=off"]),
     ("class_lists.hip", ["-ffp-contract=off"]),
     ("merge.hip", ["-ffp-contract=off"]),

@@ -29,7 +29,7 @@ const char* const kProfNames[PC_COUNT] = {"conv_mfma_f32_kernel<3, 1, 128, 8, 16
                                            "conv_first_kernel", "conv_direct_kernel", "conv_mfma_f64_kernel", "maxpool_kernel",
                                            "deconv_depthwise", "detect_tail", "box_merge", "layout", "h2d_copy", "d2h_copy",
                                            "eltwise_combine", "conv_mfma_gen_kernel", "channel_affine", "conv_dw_kernel",
-                                           "channel_l2norm"};
+                                           "channel_l2norm", "pool_kernel"};
 
 int run_conv_plan(const ConvPlan& pl, hipStream_t s, Prof& prof, double flops, double bytes) {
   if (!pl.err.empty()) {
@@ -187,6 +187,37 @@ NormArgs shf_net::norm_args(int li) const {
   NormArgs a;
   a.in = view_of(L.bottoms[0]);
   a.out = view_of(L.tops[0]);
+  a.out_amax = amax_slot(L.tops[0]);
+  return a;
+}
+
+// Pooling: what maxpool_kernel keeps -- MAX, square, not global, channel count and views multiples of 4 (its launches and its
+// name in the profile are what they always were); every other layer runs the pooling kernel (pool.hip)
+bool shf_net::pool_legacy(int li) const {
+  const Layer& L = layers[li];
+  // SHF_POOL_LEGACY=0 (measurements): every layer runs the pooling kernel.  Read once.
+  static const bool keep = !(getenv("SHF_POOL_LEGACY") && atoi(getenv("SHF_POOL_LEGACY")) == 0);
+  if (!keep) return false;
+  if (L.pool_method != POOL_MAX || L.global_pool || L.kh != L.kw || L.sh != L.sw || L.ph != L.pw) return false;
+  const View in = view_of(L.bottoms[0]), out = view_of(L.tops[0]);
+  return !(in.C % 4 || in.cstride % 4 || in.coff % 4 || out.cstride % 4 || out.coff % 4);
+}
+
+PoolGeom shf_net::pool_geom(int li) const {
+  const Layer& L = layers[li];
+  PoolGeom q;
+  q.method = L.pool_method;
+  q.kh = L.kh; q.kw = L.kw; q.sh = L.sh; q.sw = L.sw; q.ph = L.ph; q.pw = L.pw;
+  q.global = L.global_pool ? 1 : 0;
+  return q;
+}
+
+PoolArgs shf_net::pool_args(int li) const {
+  const Layer& L = layers[li];
+  PoolArgs a;
+  a.in = view_of(L.bottoms[0]);
+  a.out = view_of(L.tops[0]);
+  a.in_amax = amax_slot(L.bottoms[0]);
   a.out_amax = amax_slot(L.tops[0]);
   return a;
 }
@@ -464,8 +495,18 @@ void run_pass(const Pass& p) {
         CHECK_RC_LAYER(run_conv_plan(plan_conv(a1, p.n), p.s, h.prof, c.first, c.second), L.name);
         break;
       }
-      case OP_POOL:
+      case OP_POOL: {
         if (fused && L.fused_into >= 0) break;  // done by the producing conv's epilogue
+        if (!n0.pool_legacy(li)) {
+          // everything maxpool_kernel does not run (AVE, global, rectangular, channel counts or views off the quad grid): one
+          // launch of the pooling kernel over the lanes of the pass, which raises the tops' activation-exponent slots itself
+          PoolArgs pa[kMaxGroup];
+          for (int m = 0; m < p.n; ++m) pa[m] = p.u[m].lane->pool_args(li);
+          const auto c = cost(li, 0, p.n, 1);
+          ProfScope ps(h.prof, p.s, PC_POOLGEN, c.first, c.second);
+          CHECK_RC_LAYER(launch_pool_group(pa, p.n, n0.pool_geom(li), f64 ? 1 : 0, p.s), L.name);
+          break;
+        }
         for (int m = 0; m < p.n; ++m) {
           const shf_net& ln = *p.u[m].lane;
           const auto c = cost(li, m, m + 1, 1);
@@ -475,6 +516,7 @@ void run_pass(const Pass& p) {
             CHECK_RC(launch_amax_raise(ln.amax_slot(L.tops[0]), ln.amax_slot(L.bottoms[0]), p.s));
         }
         break;
+      }
       case OP_DECONV: {
         View in[kMaxGroup], out[kMaxGroup];
         unsigned* slot[kMaxGroup];

@@ -534,14 +534,55 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
                                  "convolution in between");
       L.op = OP_L2NORM;
     } else if (L.type == "Pooling") {
+      // PoolingLayer::LayerSetUp (pooling_layer.cpp:14-77): Caffe CHECKs these and aborts, here the graph is refused
+      const std::string who = "Pooling '" + L.name + "': ";
       const PMsg* pp = L.msg->sub("pooling_param");
-      if (pp && pp->str("pool", "MAX") != "MAX") throw std::runtime_error("only MAX pooling is supported");
-      L.k = geti(pp, "kernel_size", 2);
-      L.stride = geti(pp, "stride", 1);
-      L.pad = geti(pp, "pad", 0);
-      // PoolingLayer::LayerSetUp (pooling_layer.cpp:20-77): kernel > 0, stride > 0, pad < kernel
-      if (L.k < 1 || L.k > 64 || L.stride < 1 || L.stride > 64 || L.pad < 0 || L.pad >= L.k)
-        throw std::runtime_error("layer '" + L.name + "': pooling needs kernel_size 1 .. 64, stride 1 .. 64 and 0 <= pad < kernel_size");
+      auto has = [&](const char* f) { return pp && pp->get(f) != nullptr; };
+      if (L.tops.size() == 2)
+        throw std::runtime_error(who + "the second top '" + blobs[L.tops[1]].name + "' (MAX pooling's mask) is not supported: give one top");
+      if (L.bottoms.size() != 1 || L.tops.size() != 1)
+        throw std::runtime_error(who + "takes exactly one bottom and one top (" + std::to_string(L.bottoms.size()) + " / " +
+                                 std::to_string(L.tops.size()) + " given)");
+      const std::string method = pp ? pp->str("pool", "MAX") : "MAX";
+      if (method == "MAX" || method == "0") L.pool_method = POOL_MAX;
+      else if (method == "AVE" || method == "1") L.pool_method = POOL_AVE;
+      else throw std::runtime_error(who + "pool: " + method + ": only MAX and AVE pooling are supported");
+      L.global_pool = pp && pp->str("global_pooling", "false") == "true";
+      const bool k_sq = has("kernel_size"), k_hw = has("kernel_h") || has("kernel_w");
+      if (L.global_pool) {
+        // the window is the bottom's H x W (set at every reshape): no kernel field, pad 0, stride 1
+        if (k_sq || k_hw) throw std::runtime_error(who + "with global_pooling the kernel is the bottom's size: give no kernel_size / kernel_h / kernel_w");
+        if (geti(pp, "pad", 0) != 0 || geti(pp, "pad_h", 0) != 0 || geti(pp, "pad_w", 0) != 0 || geti(pp, "stride", 1) != 1 ||
+            geti(pp, "stride_h", 1) != 1 || geti(pp, "stride_w", 1) != 1)
+          throw std::runtime_error(who + "with global_pooling pad must be 0 and stride 1");
+        L.kh = L.kw = L.k = 1;
+        L.sh = L.sw = L.stride = 1;
+        L.ph = L.pw = L.pad = 0;
+      } else {
+        if (k_sq && k_hw) throw std::runtime_error(who + "both kernel_size and kernel_h / kernel_w given: the filter size is one or the other");
+        if (!k_sq && !(has("kernel_h") && has("kernel_w")))
+          throw std::runtime_error(who + "no filter size: give kernel_size, or kernel_h and kernel_w");
+        if ((has("pad_h") || has("pad_w")) && has("pad")) throw std::runtime_error(who + "both pad and pad_h / pad_w given: the pad is one or the other");
+        if ((has("stride_h") || has("stride_w")) && has("stride"))
+          throw std::runtime_error(who + "both stride and stride_h / stride_w given: the stride is one or the other");
+        L.kh = k_sq ? geti(pp, "kernel_size", 1) : geti(pp, "kernel_h", 0);
+        L.kw = k_sq ? geti(pp, "kernel_size", 1) : geti(pp, "kernel_w", 0);
+        const bool p_hw = has("pad_h") || has("pad_w"), s_hw = has("stride_h") || has("stride_w");
+        L.ph = p_hw ? geti(pp, "pad_h", 0) : geti(pp, "pad", 0);
+        L.pw = p_hw ? geti(pp, "pad_w", 0) : geti(pp, "pad", 0);
+        L.sh = s_hw ? geti(pp, "stride_h", 1) : geti(pp, "stride", 1);
+        L.sw = s_hw ? geti(pp, "stride_w", 1) : geti(pp, "stride", 1);
+        if (L.kh < 1 || L.kh > 64 || L.kw < 1 || L.kw > 64 || L.sh < 1 || L.sh > 64 || L.sw < 1 || L.sw > 64 || L.ph < 0 || L.pw < 0)
+          throw std::runtime_error(who + "needs a kernel of 1 .. 64, a stride of 1 .. 64 and a pad >= 0 per axis");
+        if (L.ph >= L.kh || L.pw >= L.kw)
+          throw std::runtime_error(who + "pad " + std::to_string(L.ph) + " x " + std::to_string(L.pw) + " must be smaller than the kernel " +
+                                   std::to_string(L.kh) + " x " + std::to_string(L.kw) + " (pad < kernel per axis)");
+        L.k = L.kh; L.stride = L.sh; L.pad = L.ph;   // (the square case: what the convolution's fold and maxpool_kernel read)
+      }
+      if (L.bottoms[0] == L.tops[0]) throw std::runtime_error(who + "cannot run in place on '" + blobs[L.tops[0]].name + "'");
+      if (std::count(inputs.begin(), inputs.end(), L.bottoms[0]))
+        throw std::runtime_error(who + "bottom '" + blobs[L.bottoms[0]].name + "' is a net input: the layer reads NHWC activations, put a "
+                                 "convolution in between");
       L.op = OP_POOL;
     } else if (L.type == "Python") {
       const PMsg* py = L.msg->sub("python_param");
@@ -614,7 +655,9 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   }
   // ---- what the combine launches read is a plain fp32 NHWC activation (not a blob of a proposal tail)
   for (const Layer& L : layers) {
-    if (L.op != OP_ELTWISE && L.op != OP_CROP && L.op != OP_RELU && L.op != OP_CONCAT_COPY && L.op != OP_NORM && L.op != OP_L2NORM) continue;
+    if (L.op != OP_ELTWISE && L.op != OP_CROP && L.op != OP_RELU && L.op != OP_CONCAT_COPY && L.op != OP_NORM && L.op != OP_L2NORM &&
+        L.op != OP_POOL)
+      continue;
     for (int b : L.bottoms)
       if (blobs[b].kind != BK_NHWC)
         throw std::runtime_error(L.type + " '" + L.name + "': bottom '" + blobs[b].name + "' is not an NHWC activation (it belongs to "
@@ -750,6 +793,8 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   for (size_t li = 0; li < layers.size(); ++li) {
     Layer& P = layers[li];
     if (P.op != OP_POOL || P.k != 2 || P.stride != 2 || P.pad != 0) continue;
+    // ... MAX, square, not global: the epilogue takes a maximum over 2 x 2 (an AVE 2x2/2 must not be folded into it)
+    if (P.pool_method != POOL_MAX || P.global_pool || P.kh != P.kw || P.sh != P.sw || P.ph != P.pw) continue;
     const int x = P.bottoms[0];
     int prod = -1, others = 0;
     for (size_t lj = 0; lj < layers.size(); ++lj) {
@@ -965,12 +1010,23 @@ void shf_net::infer_shapes() {
         throw std::runtime_error("ReLU '" + L.name + "': bottom '" + blobs[L.bottoms[0]].name + "' is not 4-D");
       for (int t : L.tops) blobs[t].shape = bs;
     } else if (L.type == "Pooling") {
-      int ho = (int)std::ceil((bs[2] + 2 * L.pad - L.k) / (double)L.stride) + 1;
-      int wo = (int)std::ceil((bs[3] + 2 * L.pad - L.k) / (double)L.stride) + 1;
-      if (L.pad) {
-        if ((ho - 1) * L.stride >= bs[2] + L.pad) --ho;
-        if ((wo - 1) * L.stride >= bs[3] + L.pad) --wo;
+      // PoolingLayer::Reshape (pooling_layer.cpp:79-123): ceil sizing per axis; with a pad on either axis the last window of
+      // BOTH axes must start inside the image or its padding, else it is dropped.  Global: the window is the bottom's H x W
+      if (bs.size() != 4)
+        throw std::runtime_error("Pooling '" + L.name + "': bottom '" + blobs[L.bottoms[0]].name + "' is not 4-D");
+      if (L.global_pool) {
+        L.kh = bs[2];
+        L.kw = bs[3];
       }
+      int ho = (int)std::ceil((bs[2] + 2 * L.ph - L.kh) / (double)L.sh) + 1;
+      int wo = (int)std::ceil((bs[3] + 2 * L.pw - L.kw) / (double)L.sw) + 1;
+      if (L.ph || L.pw) {
+        if ((ho - 1) * L.sh >= bs[2] + L.ph) --ho;
+        if ((wo - 1) * L.sw >= bs[3] + L.pw) --wo;
+      }
+      if (ho < 1 || wo < 1)
+        throw std::runtime_error("Pooling '" + L.name + "': kernel " + std::to_string(L.kh) + " x " + std::to_string(L.kw) + " exceeds the padded "
+                                 "input of bottom '" + blobs[L.bottoms[0]].name + "'");
       blobs[L.tops[0]].shape = {bs[0], bs[1], ho, wo};
     } else if (L.type == "Concat") {
       const int axis = geti(L.msg->sub("concat_param"), "axis", 1);

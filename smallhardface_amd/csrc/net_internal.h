@@ -167,6 +167,8 @@ void check_blob_dims(const std::vector<int>& shp, const std::string& name);   //
 // OP_NORM: a BatchNorm or Scale layer that runs the channel-affine kernel (norm.hip), alone or as the head or a member of an
 // in-place chain; one that is folded into its producing convolution is OP_SKIP with Layer::norm_conv set
 // OP_L2NORM: a Normalize layer (across_spatial: false): one launch of the channel-L2-norm kernel (l2norm.hip), never folded
+// OP_POOL: a Pooling layer: maxpool_kernel (misc.hip) for MAX, square, quad-aligned layers, a 2x2/2 one possibly folded into
+// its producing convolution on the fused path; the pooling kernel (pool.hip) for everything else
 enum OpType { OP_SKIP, OP_CONV, OP_POOL, OP_DECONV, OP_TAIL, OP_ELTWISE, OP_CROP, OP_RELU, OP_CONCAT_COPY, OP_NORM, OP_L2NORM };
 
 // what a BatchNorm / Scale layer's launch reads: per-channel vectors derived from its blobs at commit time (derive_norm),
@@ -185,6 +187,11 @@ struct Layer {
   // conv / deconv / pool hyper-parameters
   int k = 1, pad = 0, stride = 1, dil = 1, group = 1, nout = 0, relu = 0, bias_term = 1;
   int kclass = 0;
+  // Pooling (PoolingLayer::LayerSetUp): the method and the window per axis; k / stride / pad above keep the square case's
+  // values (a rectangular or global layer: those of the h axis).  global_pool: the window is the bottom's H x W at every reshape
+  int pool_method = POOL_MAX;
+  int kh = 2, kw = 2, sh = 1, sw = 1, ph = 0, pw = 0;
+  bool global_pool = false;
   int fuse_pool = -1;      // conv: index of the 2x2/2 MAX pool folded into its epilogue (fused path only)
   bool pool_only = false;  // conv: its un-pooled top has no other reader
   int fused_into = -1;     // pool: index of the conv that produces it in the fused path
@@ -591,6 +598,10 @@ struct shf_net {
   // the channel-affine launch of the chain that layer li heads: its stages (the same on every lane) and this lane's views
   NormStages norm_stages(int li) const;
   NormArgs norm_args(int li) const;
+  // a Pooling layer: whether maxpool_kernel keeps it, else the pooling kernel's geometry and this lane's views and slots
+  bool pool_legacy(int li) const;
+  PoolGeom pool_geom(int li) const;
+  PoolArgs pool_args(int li) const;
   void plan_norm_layers(const std::map<int, int>& fused_by);   // net_graph.cpp: folds into convolutions, in-place chains
   void derive_norm(int li);                                    // a BatchNorm / Scale layer's device vectors from its blobs
   // a convolution's effective parameters with its BatchNorm / Scale folded in (binary64, one rounding per value)

@@ -38,6 +38,7 @@ enum ProfClass {
   PC_NORM,      // the channel-affine kernel (norm.hip): BatchNorm, Scale and the ReLU behind them, where they are not folded
   PC_CONV_DW,   // the depthwise convolution (conv_dw.hip), its fp32 and its f64 form
   PC_L2NORM,    // the channel-L2-norm kernel (l2norm.hip): Normalize with across_spatial: false
+  PC_POOLGEN,   // the pooling kernel (pool.hip): AVE, global, rectangular and any-channel-count Pooling (PC_POOL: maxpool_kernel)
   PC_COUNT
 };
 
@@ -189,6 +190,23 @@ int launch_channel_affine_group(const NormArgs* as, int n, const NormStages& st,
 // on the device.  ONE launch over n <= 16 members that share the layer (the lanes of a grouped pass); f64: the expression in
 // binary64, rounded once; range_flag as launch_combine_group's
 int launch_channel_l2norm_group(const NormArgs* as, int n, const float* scale, float eps, int f64, int* range_flag, hipStream_t s);
+// the pooling kernel (pool.hip): Caffe's MAX / AVE windows (pooling_layer.cpp:144-215) of any rectangular geometry, or the
+// whole map (`global`: the kernel is each member's own H x W, pad 0, stride 1, the output (B, C, 1, 1)).  It raises each
+// member's out_amax from its in_amax itself (every output is bounded by max |input|).  ONE launch over n <= 16 members that
+// share the layer (the lanes of a grouped pass); f64: the AVE sum and division in binary64, rounded once.
+enum PoolMethod { POOL_MAX, POOL_AVE };
+struct PoolGeom {
+  int method = POOL_MAX;
+  int kh = 2, kw = 2, sh = 1, sw = 1, ph = 0, pw = 0;
+  int global = 0;
+};
+struct PoolArgs {
+  View in, out;
+  const unsigned* in_amax = nullptr;   // the blobs' activation-exponent slots (fp16 modes) or null
+  unsigned* out_amax = nullptr;
+};
+int launch_pool_group(const PoolArgs* as, int n, const PoolGeom& q, int f64, hipStream_t s);
+int pool_global_threshold();   // pixels up to which a global layer runs the windowed form (above: the tree form)
 int launch_nhwc_to_nchw(const View& in, float* out_nchw, hipStream_t s);    // blob.data read-back
 int launch_nchw_to_nhwc(const float* in_nchw, const View& out, hipStream_t s);
 // pyramid unit from the raw BGR uint8 image (pre.hip)
