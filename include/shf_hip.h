@@ -161,6 +161,10 @@ long long shf_net_range_fallbacks(shf_net* net);
  * semantics, caffe/src/caffe/blob.cpp:22-50: capacity only ever grows; syncedmem.cpp:15-50 is where Caffe allocates).  A
  * stream of images whose shapes were all seen before must leave both counts unchanged.  Measurement only. */
 void shf_alloc_counts(long long* device_allocs, long long* pinned_host_allocs);
+/* The byte (0..255) that the environment's SHF_POISON_ALLOC made this process fill fresh device allocations with, or -1
+ * when the knob is unset.  Parsed once, at first use (strtol base 0: "0xff", "127").  Tests only
+ * (tests/test_gpu_buffer_history.py asserts it against its environment, so that the knob cannot be lost unnoticed). */
+int shf_debug_poison_byte(void);
 /* _get_image_blob (lib/utils/test_utils.py:29-46) + im_list_to_blob (lib/utils/blob.py:16-32) for a whole scale list, for
  * callers that keep HOST blobs (lib/test.py:109-178 detect() -> forward_net): `im_bgr_host` uint8 HxWx3 is uploaded once,
  * level i = mean subtraction + cv2.resize(fx = fy = scales[i], INTER_LINEAR) restated (csrc/pre.hip: the host mirror's

@@ -33,7 +33,10 @@ static DevBuf* g_box_in = nullptr;
 namespace {
 struct CallBuf {
   void* p = nullptr;
-  void alloc(size_t bytes) { HIP_THROW(hipMalloc(&p, bytes ? bytes : 1)); }
+  void alloc(size_t bytes) {
+    HIP_THROW(hipMalloc(&p, bytes ? bytes : 1));
+    poison_fresh(p, bytes ? bytes : 1);
+  }
   template <typename T> T* as() const { return (T*)p; }
   ~CallBuf() { if (p) (void)hipFree(p); }
   CallBuf() = default;
@@ -356,6 +359,8 @@ void shf_alloc_counts(long long* device_allocs, long long* pinned_host_allocs) {
   if (device_allocs) *device_allocs = g_dev_allocs.load();
   if (pinned_host_allocs) *pinned_host_allocs = g_host_allocs.load();
 }
+
+int shf_debug_poison_byte(void) { return poison_byte(); }
 
 static void box_ctx_init();
 

@@ -49,6 +49,21 @@ inline void fill_now(void* p, int byte, size_t n) {
   HIP_THROW(hipStreamSynchronize(nullptr));
 }
 
+// SHF_POISON_ALLOC=<byte> (tests/test_gpu_buffer_history.py): fresh device allocations start filled with that byte (0xff:
+// NaNs) instead of whatever the allocator hands out -- a kernel whose result depends on memory it never wrote shows up as a
+// changed result.  Read once per process; -1 when the knob is unset (shf_debug_poison_byte).
+inline int poison_byte() {
+  static const int byte = [] {
+    const char* s = getenv("SHF_POISON_ALLOC");
+    return s ? (int)(strtol(s, nullptr, 0) & 0xff) : -1;
+  }();
+  return byte;
+}
+// ... applied to a fresh allocation of n bytes (DevBuf::ensure, and the evaluators' per-call buffers in net_api.cpp)
+inline void poison_fresh(void* p, size_t n) {
+  if (poison_byte() >= 0) fill_now(p, poison_byte(), n);
+}
+
 // (re)allocations made by the grow-only buffers of this process: a new level shape re-plans sizes and pointers and only
 // allocates where a buffer has to grow (shf_alloc_counts; bench.py's mixed-shape leg reports them after its first pass)
 extern std::atomic<long long> g_dev_allocs, g_host_allocs;   // net_api.cpp
@@ -65,10 +80,7 @@ struct DevBuf {
     want = (want + 255) & ~(size_t)255;
     HIP_THROW(hipMalloc(&p, want));
     cap = want;
-    // SHF_POISON_ALLOC=<byte> (tests): fresh device buffers start filled with that byte (0xff: NaNs) instead of whatever the
-    // allocator hands out -- a kernel whose result depends on memory it never wrote shows up as a changed detection
-    static const char* poison = getenv("SHF_POISON_ALLOC");
-    if (poison) fill_now(p, (int)strtol(poison, nullptr, 0), want);
+    poison_fresh(p, want);
   }
   ~DevBuf() {
     if (p) (void)hipFree(p);
