@@ -454,6 +454,8 @@ class OracleNet(object):
 
     def __init__(self, net_msg, params=None, proposal_cfg=None):
         from collections import OrderedDict
+        from smallhardface_amd.prototxt import normalize_graph
+        net_msg = normalize_graph(net_msg)    # (what the runtime's graph reader honours is honoured here, what it refuses is refused)
         self.msg = net_msg
         self.layers = net_msg.getall("layer")
         self.blobs = OrderedDict()

@@ -15,6 +15,8 @@
 //   * buffers are grow-only and shape changes re-plan nothing but pointers/sizes.
 #include "net_internal.h"
 
+#include <cerrno>
+
 namespace shf {
 
 // generate_anchors.py:11-86 in double precision
@@ -106,6 +108,109 @@ static int geti(const PMsg* m, const char* n, int d) {
   return v > 2147483647L ? 2147483647 : (v < -2147483647L ? -2147483647 : (int)v);
 }
 
+// ---- scalars that must parse completely as their field's type.  strtol / strtod stop at the first character they cannot use
+// and atoi gives 0 for none: `kernel_size: 3.7` would be 3 and `pad: x` 0 without a word, where protobuf's text format fails
+// the whole file.  Every scalar of the messages the graph reads is checked once, before anything reads it.
+namespace {
+struct TypedField { const char* msg; const char* field; char kind; };   // kind: i(nteger), f(loat), b(ool)
+const TypedField kTypedFields[] = {
+    {"convolution_param", "num_output", 'i'}, {"convolution_param", "bias_term", 'b'}, {"convolution_param", "pad", 'i'},
+    {"convolution_param", "kernel_size", 'i'}, {"convolution_param", "stride", 'i'}, {"convolution_param", "dilation", 'i'},
+    {"convolution_param", "pad_h", 'i'}, {"convolution_param", "pad_w", 'i'}, {"convolution_param", "kernel_h", 'i'},
+    {"convolution_param", "kernel_w", 'i'}, {"convolution_param", "stride_h", 'i'}, {"convolution_param", "stride_w", 'i'},
+    {"convolution_param", "group", 'i'}, {"convolution_param", "axis", 'i'}, {"convolution_param", "force_nd_im2col", 'b'},
+    {"pooling_param", "pad", 'i'}, {"pooling_param", "pad_h", 'i'}, {"pooling_param", "pad_w", 'i'},
+    {"pooling_param", "kernel_size", 'i'}, {"pooling_param", "kernel_h", 'i'}, {"pooling_param", "kernel_w", 'i'},
+    {"pooling_param", "stride", 'i'}, {"pooling_param", "stride_h", 'i'}, {"pooling_param", "stride_w", 'i'},
+    {"pooling_param", "global_pooling", 'b'}, {"relu_param", "negative_slope", 'f'}, {"eltwise_param", "coeff", 'f'},
+    {"eltwise_param", "stable_prod_grad", 'b'}, {"crop_param", "axis", 'i'}, {"crop_param", "offset", 'i'},
+    {"batch_norm_param", "use_global_stats", 'b'}, {"batch_norm_param", "moving_average_fraction", 'f'},
+    {"batch_norm_param", "eps", 'f'}, {"scale_param", "axis", 'i'}, {"scale_param", "num_axes", 'i'},
+    {"scale_param", "bias_term", 'b'}, {"norm_param", "across_spatial", 'b'}, {"norm_param", "channel_shared", 'b'},
+    {"norm_param", "eps", 'f'}, {"concat_param", "axis", 'i'}, {"concat_param", "concat_dim", 'i'},
+    {"softmax_param", "axis", 'i'}, {"reshape_param", "axis", 'i'}, {"reshape_param", "num_axes", 'i'},
+    {"python_param", "share_in_parallel", 'b'}, {"shape", "dim", 'i'}, {"input_shape", "dim", 'i'},
+    {"scale_filler", "value", 'f'},
+};
+
+bool bool_text(const std::string& s, bool& v) {   // the spellings protobuf's text format takes for a bool
+  if (s == "true" || s == "True" || s == "t" || s == "1") { v = true; return true; }
+  if (s == "false" || s == "False" || s == "f" || s == "0") { v = false; return true; }
+  return false;
+}
+
+void check_scalar(const std::string& who, const std::string& path, const PField& f, char kind) {
+  const char* b = f.scalar.c_str();
+  char* e = nullptr;
+  bool ok = !f.quoted && !f.msg && *b;
+  const char* what = kind == 'i' ? "an integer" : kind == 'f' ? "a number" : "a bool (true / false)";
+  if (ok && kind == 'i') {          // (decimal only: a hexadecimal or octal literal is refused, not misread)
+    errno = 0;
+    std::strtoll(b, &e, 10);
+    ok = e != b && *e == 0 && errno == 0;
+  } else if (ok && kind == 'f') {   // (text format lets a float end in 'f')
+    std::strtod(b, &e);
+    ok = e != b && (*e == 0 || ((*e == 'f' || *e == 'F') && e[1] == 0));
+  } else if (ok) {
+    bool v;
+    ok = bool_text(f.scalar, v);
+  }
+  if (!ok) throw std::runtime_error(who + path + ": '" + f.scalar + "' is not " + what);
+}
+
+// every typed scalar directly inside message `m` (named `mname` by its parent), and inside its sub-messages
+void check_typed(const std::string& who, const std::string& mname, const PMsg* m, int depth = 0) {
+  for (const PField& f : m->fields) {
+    if (f.msg) {
+      if (depth < 3) check_typed(who, f.name, f.msg.get(), depth + 1);
+      continue;
+    }
+    for (const TypedField& t : kTypedFields)
+      if (mname == t.msg && f.name == t.field) check_scalar(who, mname + "." + f.name, f, t.kind);
+  }
+}
+
+bool getb(const PMsg* m, const char* n, bool d) {
+  const PField* f = m ? m->get(n) : nullptr;
+  bool v = d;
+  if (f && !bool_text(f->scalar, v)) throw std::runtime_error(std::string(n) + ": '" + f->scalar + "' is not a bool");
+  return v;
+}
+
+// One spatial hyper-parameter of a Convolution / Deconvolution by BaseConvolutionLayer::LayerSetUp's rules
+// (base_conv_layer.cpp:36-117): the repeated field holds one value for both axes or one per axis, or the *_h / *_w pair
+// stands in its place -- never both.  Only square geometry has kernels here: equal axes mean that square, unequal ones are
+// refused by name.
+int conv_spatial(const std::string& who, const PMsg* cp, const char* rep, const char* fh, const char* fw, int dflt, bool required) {
+  auto val = [](const PField* f) {
+    const long v = std::strtol(f->scalar.c_str(), nullptr, 10);
+    return v > 2147483647L ? 2147483647 : (v < -2147483647L ? -2147483647 : (int)v);
+  };
+  const auto vals = cp->all(rep);
+  const PField *h = fh ? cp->get(fh) : nullptr, *w = fw ? cp->get(fw) : nullptr;   // (dilation has no *_h / *_w form)
+  const std::string hw = fh ? std::string(fh) + " / " + fw : std::string();
+  if (h || w) {
+    if (!vals.empty())
+      throw std::runtime_error(who + "both " + rep + " and " + hw + " given: it is one or the other");
+    if (!h || !w) throw std::runtime_error(who + (h ? fh : fw) + " without " + (h ? fw : fh) + ": give both");
+    if (val(h) != val(w))
+      throw std::runtime_error(who + "rectangular " + hw + " (" + std::to_string(val(h)) + " x " + std::to_string(val(w)) +
+                               ") not supported: both axes must be equal");
+    return val(h);
+  }
+  if (vals.empty()) {
+    if (required) throw std::runtime_error(who + "no filter size: give " + rep + ", or " + fh + " and " + fw);
+    return dflt;
+  }
+  if (vals.size() > 2)
+    throw std::runtime_error(who + rep + " given " + std::to_string(vals.size()) + " times: give it once, or once per spatial axis (2)");
+  if (vals.size() == 2 && val(vals[0]) != val(vals[1]))
+    throw std::runtime_error(who + "rectangular " + rep + " (" + std::to_string(val(vals[0])) + " x " + std::to_string(val(vals[1])) +
+                             ") not supported: both axes must be equal");
+  return val(vals[0]);
+}
+}  // namespace
+
 // Blob::Reshape (blob.cpp:23-51): at most 32 axes, every dim >= 0, count <= INT_MAX
 void shf::check_blob_dims(const std::vector<int>& shp, const std::string& name) {
   if (shp.size() > 32) throw std::runtime_error("blob '" + name + "': more than 32 axes");
@@ -144,7 +249,7 @@ void shf_net::build_module(int mj, const std::map<int, int>& producer, std::map<
   if (pit == producer.end()) throw std::runtime_error("tail: dangling softmax input");
   if (layers[pit->second].type == "Concat") {
     const int l_cc = pit->second;
-    if (geti(layers[l_cc].msg->sub("concat_param"), "axis", 1) != 2)
+    if (layers[l_cc].concat_axis != 2)
       throw std::runtime_error("tail: class-score concat must be on axis 2");
     fused_layers.insert(l_cc);
     for (int b : layers[l_cc].bottoms) M.cls_layers.push_back(prod(b, "Convolution"));
@@ -159,7 +264,7 @@ void shf_net::build_module(int mj, const std::map<int, int>& producer, std::map<
   auto bit = producer.find(M.box_blob);
   if (bit == producer.end()) throw std::runtime_error("tail: dangling bbox input");
   if (layers[bit->second].type == "Concat") {
-    if (geti(layers[bit->second].msg->sub("concat_param"), "axis", 1) != 1)
+    if (layers[bit->second].concat_axis != 1)
       throw std::runtime_error("tail: bbox concat must be on axis 1");
     fused_layers.insert(bit->second);
     for (int b : layers[bit->second].bottoms) M.box_layers.push_back(prod(b, "Convolution"));
@@ -175,7 +280,17 @@ void shf_net::build_module(int mj, const std::map<int, int>& producer, std::map<
     Layer& c = layers[M.cls_layers[i]];
     Layer& b = layers[M.box_layers[i]];
     if (c.k != 1 || b.k != 1 || c.bottoms[0] != b.bottoms[0])
-      throw std::runtime_error("tail: cls/bbox predictors must be 1x1 convs on the same head blob");
+      throw std::runtime_error("ProposalLayer '" + T.name + "': predictors '" + c.name + "' / '" + b.name + "' (kernel_size " +
+                               std::to_string(c.k) + " / " + std::to_string(b.k) + "): cls/bbox predictors must be 1x1 convs on the same head blob");
+    // the tail's logits kernel is a matrix product per pixel: a predictor's pad or stride has no place in it, while the
+    // blob shapes would still be computed with them
+    for (const Layer* p : {&c, &b}) {
+      const char* field = p->pad != 0 ? "pad" : p->stride != 1 ? "stride" : p->dil != 1 ? "dilation" : nullptr;
+      if (field)
+        throw std::runtime_error("ProposalLayer '" + T.name + "': predictor '" + p->name + "' has " + field + " " +
+                                 std::to_string(p->pad != 0 ? p->pad : p->stride != 1 ? p->stride : p->dil) +
+                                 ": the fused predictors must be 1x1 convolutions with pad 0, stride 1 and dilation 1");
+    }
     M.feat_blobs.push_back(c.bottoms[0]);
     fused_layers.insert(M.cls_layers[i]);
     fused_layers.insert(M.box_layers[i]);
@@ -302,6 +417,13 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   CHECK_RC(conv_init_attributes());
 
   // ---- inputs: legacy `input:` + input_shape / input_dim (upgrade_proto.cpp:966-1000)
+  // legacy V1 `layers { ... }` entries (caffe.proto NetParameter.layers; Caffe upgrades them, upgrade_proto.cpp): not read
+  // here, so a net that has any would silently lose them
+  if (root->get("layers"))
+    throw std::runtime_error("net: legacy V1 'layers' entries are not supported: write the net with 'layer' (LayerParameter)");
+  for (auto s : root->all("input_shape"))
+    if (s->msg) check_typed("net: ", "input_shape", s->msg.get());
+  for (auto d : root->all("input_dim")) check_scalar("net: ", "input_dim", *d, 'i');
   auto in_names = root->all("input");
   auto in_shapes = root->all("input_shape");
   auto in_dims = root->all("input_dim");
@@ -324,6 +446,21 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
     L.msg = lm;
     L.name = lm->str("name");
     L.type = lm->str("type");
+    {
+      // Net::FilterNet (net.cpp:259-285) drops a layer whose include / exclude rules or phase do not meet the net's state;
+      // nothing here filters, so a TRAIN-only layer would run: refused by name.  Inline `blobs` (Layer's constructor copies
+      // them into the layer's parameters, layer.hpp:46-55) are not read either: the values come from a caffemodel
+      const std::string who = "layer '" + L.name + "': ";
+      for (const char* f : {"include", "exclude"})
+        if (lm->get(f))
+          throw std::runtime_error(who + f + " rules are not supported: write the TEST-phase net without them");
+      const std::string phase = lm->str("phase", "TEST");
+      if (phase != "TEST" && phase != "1")
+        throw std::runtime_error(who + "phase " + phase + ": only TEST-phase layers are supported");
+      if (lm->get("blobs"))
+        throw std::runtime_error(who + "inline blobs are not read: give the parameters in a caffemodel or through Net.params");
+      check_typed(who, "layer", lm);
+    }
     if (L.type == "Input") {
       auto tops = lm->all("top");
       const PMsg* ip = lm->sub("input_param");
@@ -383,12 +520,22 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
       const PMsg* cp = L.msg->sub("convolution_param");
       if (!cp) throw std::runtime_error("layer '" + L.name + "': missing convolution_param");
       L.nout = geti(cp, "num_output", 0);
-      L.k = geti(cp, "kernel_size", 1);
-      L.pad = geti(cp, "pad", 0);
-      L.stride = geti(cp, "stride", 1);
-      L.dil = geti(cp, "dilation", 1);
+      const std::string who = "layer '" + L.name + "': ";
+      L.k = conv_spatial(who, cp, "kernel_size", "kernel_h", "kernel_w", 0, true);
+      L.pad = conv_spatial(who, cp, "pad", "pad_h", "pad_w", 0, false);
+      L.stride = conv_spatial(who, cp, "stride", "stride_h", "stride_w", 1, false);
+      L.dil = conv_spatial(who, cp, "dilation", nullptr, nullptr, 1, false);
       L.group = geti(cp, "group", 1);
-      L.bias_term = cp->str("bias_term", "true") != "false";
+      L.bias_term = getb(cp, "bias_term", true);
+      // the channel axis is 1 and the spatial axes are the two behind it (base_conv_layer.cpp:24-33); another axis is an N-D
+      // or a 1-D convolution, and force_nd_im2col only matters to those
+      const int axis = geti(cp, "axis", 1);
+      if (axis != 1 && axis != -3)
+        throw std::runtime_error(who + "axis " + std::to_string(axis) + ": only 2-D convolution over the last two axes (axis 1) is supported");
+      if (getb(cp, "force_nd_im2col", false)) throw std::runtime_error(who + "force_nd_im2col: true is not supported");
+      // DeconvolutionLayer::compute_output_shape (deconv_layer.cpp:8-24) uses the dilated extent; the kernel here does not
+      if (L.type == "Deconvolution" && L.dil != 1 && L.dil >= 1 && L.dil <= 64)
+        throw std::runtime_error(who + "dilation " + std::to_string(L.dil) + ": a Deconvolution's dilation must be 1");
       // BaseConvolutionLayer::LayerSetUp's CHECKs (base_conv_layer.cpp:21-120): Caffe aborts on these, here the graph is refused
       // with the layer's name -- a hostile prototxt must not reach a division by a zero stride or a 2^31-channel allocation
       if (L.nout < 1 || L.nout > (1 << 20)) throw std::runtime_error("layer '" + L.name + "': num_output must be in 1 .. 2^20");
@@ -491,7 +638,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
                                  std::to_string(L.tops.size()) + " given)");
       if (L.is_bn) {
         const PMsg* bp = L.msg->sub("batch_norm_param");
-        if (bp && bp->str("use_global_stats", "true") == "false")
+        if (!getb(bp, "use_global_stats", true))
           throw std::runtime_error(who + "use_global_stats: false asks for batch statistics, which is training: only inference "
                                    "with the stored statistics is supported");
         const double eps = bp ? bp->real("eps", 1e-5) : 1e-5;
@@ -504,7 +651,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
         if ((axis != 1 && axis != -3) || num_axes != 1)
           throw std::runtime_error(who + "axis " + std::to_string(axis) + " / num_axes " + std::to_string(num_axes) +
                                    ": only a per-channel scale (axis 1, num_axes 1) is supported");
-        L.bias_term = sp && sp->str("bias_term", "false") == "true";
+        L.bias_term = getb(sp, "bias_term", false);
       }
       if (std::count(inputs.begin(), inputs.end(), L.bottoms[0]))
         throw std::runtime_error(who + "bottom '" + blobs[L.bottoms[0]].name + "' is a net input: the layer reads NHWC activations, put a "
@@ -517,10 +664,10 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
         throw std::runtime_error(who + "takes exactly one bottom and one top (" + std::to_string(L.bottoms.size()) + " / " +
                                  std::to_string(L.tops.size()) + " given)");
       const PMsg* np = L.msg->sub("norm_param");
-      if (!np || np->str("across_spatial", "true") != "false")
+      if (!np || getb(np, "across_spatial", true))
         throw std::runtime_error(who + "across_spatial: true (the default of norm_param) normalises over the whole image, which is "
                                  "not supported: write across_spatial: false for the per-pixel norm over channels");
-      L.l2_shared = np->str("channel_shared", "true") == "true";
+      L.l2_shared = getb(np, "channel_shared", true);
       const double eps = np->real("eps", 1e-10);
       L.eps = (float)eps;
       if (!std::isfinite(eps) || !std::isfinite(L.eps) || eps < 0)
@@ -547,7 +694,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
       if (method == "MAX" || method == "0") L.pool_method = POOL_MAX;
       else if (method == "AVE" || method == "1") L.pool_method = POOL_AVE;
       else throw std::runtime_error(who + "pool: " + method + ": only MAX and AVE pooling are supported");
-      L.global_pool = pp && pp->str("global_pooling", "false") == "true";
+      L.global_pool = getb(pp, "global_pooling", false);
       const bool k_sq = has("kernel_size"), k_hw = has("kernel_h") || has("kernel_w");
       if (L.global_pool) {
         // the window is the bottom's H x W (set at every reshape): no kernel field, pad 0, stride 1
@@ -592,8 +739,36 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
       tail_layer = (int)li;
       mods.emplace_back();
       mods.back().layer = (int)li;
-    } else if (L.type == "Concat" || L.type == "Softmax" || L.type == "Reshape" || L.type == "Split" ||
-               L.type == "Input") {
+    } else if (L.type == "Concat") {
+      // ConcatLayer::LayerSetUp / Reshape (concat_layer.cpp:10-30): `concat_dim` is the legacy spelling of `axis` (never
+      // negative), giving both is an error; a negative axis counts from the end of the 4-D blob
+      const std::string who = "Concat '" + L.name + "': ";
+      const PMsg* cc = L.msg->sub("concat_param");
+      const bool has_dim = cc && cc->get("concat_dim"), has_axis = cc && cc->get("axis");
+      if (has_dim && has_axis) throw std::runtime_error(who + "both axis and concat_dim given: it is one or the other");
+      int axis = has_dim ? geti(cc, "concat_dim", 1) : geti(cc, "axis", 1);
+      if (has_dim && axis < 0) throw std::runtime_error(who + "concat_dim " + std::to_string(axis) + " must not be negative");
+      if (axis < 0) axis += 4;
+      if (axis < 0 || axis > 3)
+        throw std::runtime_error(who + (has_dim ? "concat_dim " : "axis ") + std::to_string(geti(cc, has_dim ? "concat_dim" : "axis", 1)) +
+                                 " is outside a 4-D blob");
+      if (L.bottoms.empty() || L.tops.size() != 1) throw std::runtime_error(who + "takes at least one bottom and exactly one top");
+      L.concat_axis = axis;
+      L.op = OP_SKIP;
+    } else if (L.type == "Softmax" || L.type == "Reshape" || L.type == "Split" || L.type == "Input") {
+      // (the proposal tail computes the Softmax over the class planes that its Reshapes lay out: axis 1 of the 4-D score
+      // blob, and a Reshape of the whole shape -- softmax_layer.cpp:12-16, reshape_layer.cpp:10-60)
+      if (L.type == "Softmax") {
+        const int axis = geti(L.msg->sub("softmax_param"), "axis", 1);
+        if (axis != 1 && axis != -3)
+          throw std::runtime_error("Softmax '" + L.name + "': axis " + std::to_string(axis) + ": only the softmax over axis 1 is supported");
+      }
+      if (L.type == "Reshape") {
+        const PMsg* rp = L.msg->sub("reshape_param");
+        if (geti(rp, "axis", 0) != 0 || geti(rp, "num_axes", -1) != -1)
+          throw std::runtime_error("Reshape '" + L.name + "': axis " + std::to_string(geti(rp, "axis", 0)) + " / num_axes " +
+                                   std::to_string(geti(rp, "num_axes", -1)) + ": only a reshape of the whole blob (axis 0, num_axes -1) is supported");
+      }
       L.op = OP_SKIP;
     } else {
       throw std::runtime_error("Unsupported layer type '" + L.type + "' (layer '" + L.name + "')");
@@ -629,8 +804,8 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   for (size_t li = 0; li < layers.size(); ++li) {
     Layer& L = layers[li];
     if (L.type != "Concat" || fused_by.count((int)li)) continue;
-    if (geti(L.msg->sub("concat_param"), "axis", 1) != 1)
-      throw std::runtime_error("Concat '" + L.name + "': only channel concat is supported outside the tail");
+    if (L.concat_axis != 1)
+      throw std::runtime_error("Concat '" + L.name + "': axis " + std::to_string(L.concat_axis) + ": only channel concat (axis 1) is supported outside the tail");
     // Caffe's Concat copies: its bottoms keep their values when a later in-place ReLU rewrites the top.  As views they would
     // be rewritten with it, so such a Concat copies here too (one combine launch per member, the ReLU applied on the way
     // when it comes directly behind) and its members keep their own buffers.
@@ -927,6 +1102,14 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
       B.split_fused = readers > 0 && all_w4;
     }
   }
+  // ---- Softmax, Reshape and Split have no launch of their own: inside a tail the tail computes them, outside one their top
+  //      would be a buffer that nothing writes.  (Checked last: what another layer refuses about the graph is said first.)
+  for (size_t li = 0; li < layers.size(); ++li) {
+    const Layer& L = layers[li];
+    if ((L.type == "Softmax" || L.type == "Reshape" || L.type == "Split") && !fused_by.count((int)li))
+      throw std::runtime_error(L.type + " '" + L.name + "': the layer type exists only inside a proposal tail (between the predictors "
+                               "and a ProposalLayer); this one feeds none");
+  }
   alloc_buffers();
   amax_slots.ensure(std::max<size_t>(blobs.size(), 1) * 4);
   fill_now(amax_slots.p, 0, std::max<size_t>(blobs.size(), 1) * 4);
@@ -1029,7 +1212,7 @@ void shf_net::infer_shapes() {
                                  "input of bottom '" + blobs[L.bottoms[0]].name + "'");
       blobs[L.tops[0]].shape = {bs[0], bs[1], ho, wo};
     } else if (L.type == "Concat") {
-      const int axis = geti(L.msg->sub("concat_param"), "axis", 1);
+      const int axis = L.concat_axis;
       std::vector<int> s = bs;
       int sum = 0;
       int off = 0;

@@ -217,6 +217,7 @@ struct Layer {
   int eop = COMBINE_COPY;          // Eltwise: its operation
   std::vector<float> coeff;        // Eltwise SUM: one per bottom (all 1 when the prototxt gives none)
   float slope = 0.f;               // ReLU: negative_slope
+  int concat_axis = 1;             // Concat: the canonical axis (concat_param.axis, or its legacy spelling concat_dim)
   int crop_axis = 2;               // Crop: first cropped axis, and the origin per blob axis (set by shape inference)
   std::vector<int> crop_offsets;   //   as the prototxt gives them: none, one, or one per cropped axis
   int crop_origin[4] = {0, 0, 0, 0};

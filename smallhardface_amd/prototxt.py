@@ -422,3 +422,154 @@ def write_test_prototxt(path, different_dilation=True, dim_red=True):
     with open(path, "w") as f:
         f.write(dumps(pb))
     return path
+
+
+# --------------------------------------------------------------------------
+# what the graph reader honours and refuses (csrc/net_graph.cpp), for the Python readers of the same text
+# --------------------------------------------------------------------------
+_TYPED = {
+    "convolution_param": dict(num_output="i", bias_term="b", pad="i", kernel_size="i", stride="i", dilation="i", pad_h="i", pad_w="i",
+                              kernel_h="i", kernel_w="i", stride_h="i", stride_w="i", group="i", axis="i", force_nd_im2col="b"),
+    "pooling_param": dict(pad="i", pad_h="i", pad_w="i", kernel_size="i", kernel_h="i", kernel_w="i", stride="i", stride_h="i",
+                          stride_w="i", global_pooling="b"),
+    "relu_param": dict(negative_slope="f"), "eltwise_param": dict(coeff="f", stable_prod_grad="b"),
+    "crop_param": dict(axis="i", offset="i"),
+    "batch_norm_param": dict(use_global_stats="b", moving_average_fraction="f", eps="f"),
+    "scale_param": dict(axis="i", num_axes="i", bias_term="b"),
+    "norm_param": dict(across_spatial="b", channel_shared="b", eps="f"),
+    "concat_param": dict(axis="i", concat_dim="i"), "softmax_param": dict(axis="i"),
+    "reshape_param": dict(axis="i", num_axes="i"), "python_param": dict(share_in_parallel="b"),
+    "shape": dict(dim="i"), "input_shape": dict(dim="i"), "scale_filler": dict(value="f"),
+}
+_WHAT = {"i": "an integer", "f": "a number", "b": "a bool (true / false)"}
+_BOOLS = {"true": True, "True": True, "t": True, "1": True, "false": False, "False": False, "f": False, "0": False}
+
+
+def _check_typed(who, mname, msg, depth=0):
+    for k, v in msg.fields:
+        if isinstance(v, Msg):
+            if depth < 3:
+                _check_typed(who, k, v, depth + 1)
+            continue
+        kind = _TYPED.get(mname, {}).get(k)
+        if kind is None:
+            continue
+        bare = not isinstance(v, str) or isinstance(v, Enum)          # (a quoted string is no number)
+        if kind == "i":
+            ok = bare and isinstance(v, int) and not isinstance(v, bool)
+        elif kind == "f":
+            ok = bare and (isinstance(v, (int, float)) or re.match(r"^[-+]?(\d+\.?\d*|\.\d+)([eE][-+]?\d+)?[fF]$|^[-+]?(inf|nan)", str(v)) is not None)
+        else:
+            ok = bare and str(v) in _BOOLS
+        if not ok:
+            raise ValueError("%s%s.%s: '%s' is not %s" % (who, mname, k, v, _WHAT[kind]))
+
+
+def as_bool(msg, name, default):
+    """A bool field by the spellings protobuf's text format takes."""
+    v = msg.get(name) if msg is not None else None
+    if v is None:
+        return default
+    if str(v) not in _BOOLS:
+        raise ValueError("%s: '%s' is not a bool" % (name, v))
+    return _BOOLS[str(v)]
+
+
+def _conv_spatial(who, cp, rep, fh, fw, default, required):
+    """BaseConvolutionLayer::LayerSetUp's rules (base_conv_layer.cpp:36-117) for one spatial hyper-parameter, square only."""
+    vals = [int(v) for v in cp.getall(rep)]
+    h, w = (cp.get(fh), cp.get(fw)) if fh else (None, None)
+    if h is not None or w is not None:
+        hw = "%s / %s" % (fh, fw)
+        if vals:
+            raise ValueError("%sboth %s and %s given: it is one or the other" % (who, rep, hw))
+        if h is None or w is None:
+            raise ValueError("%s%s without %s: give both" % ((who,) + ((fh, fw) if h is not None else (fw, fh))))
+        if int(h) != int(w):
+            raise ValueError("%srectangular %s (%d x %d) not supported: both axes must be equal" % (who, hw, int(h), int(w)))
+        return int(h)
+    if not vals:
+        if required:
+            raise ValueError("%sno filter size: give %s, or %s and %s" % (who, rep, fh, fw))
+        return default
+    if len(vals) > 2:
+        raise ValueError("%s%s given %d times: give it once, or once per spatial axis (2)" % (who, rep, len(vals)))
+    if len(vals) == 2 and vals[0] != vals[1]:
+        raise ValueError("%srectangular %s (%d x %d) not supported: both axes must be equal" % (who, rep, vals[0], vals[1]))
+    return vals[0]
+
+
+def normalize_graph(net_msg):
+    """A copy of the net in which every field the Python readers take with ``_ints(msg, name, default)`` holds the value the
+    graph reader of the runtime resolves (csrc/net_graph.cpp), and a ValueError in that reader's words for what it refuses:
+    a Convolution / Deconvolution ends up with one ``kernel_size``, ``pad``, ``stride`` and ``dilation`` (from the repeated
+    fields or the ``*_h`` / ``*_w`` pairs, equal axes only), a Concat with ``axis`` (from ``concat_dim``, negative axes made
+    canonical), every bool with ``true`` / ``false``.  ``weights.py`` and the oracle nets read through it, so a field the
+    runtime honours is honoured by them and one it refuses is refused by them."""
+    if net_msg.has("layers"):
+        raise ValueError("net: legacy V1 'layers' entries are not supported: write the net with 'layer' (LayerParameter)")
+    for s in net_msg.getall("input_shape"):
+        _check_typed("net: ", "input_shape", s)
+    out = net_msg.copy()
+    for L in out.getall("layer"):
+        who = "layer '%s': " % L.get("name", "")
+        for f in ("include", "exclude"):
+            if L.has(f):
+                raise ValueError("%s%s rules are not supported: write the TEST-phase net without them" % (who, f))
+        if str(L.get("phase", "TEST")) not in ("TEST", "1"):
+            raise ValueError("%sphase %s: only TEST-phase layers are supported" % (who, L.get("phase")))
+        if L.has("blobs"):
+            raise ValueError("%sinline blobs are not read: give the parameters in a caffemodel or through Net.params" % who)
+        _check_typed(who, "layer", L)
+        for sub, names in (("convolution_param", ("bias_term",)), ("scale_param", ("bias_term",)),
+                           ("pooling_param", ("global_pooling",)), ("norm_param", ("across_spatial", "channel_shared")),
+                           ("batch_norm_param", ("use_global_stats",))):
+            m = L.get(sub)
+            for n in names:
+                if m is not None and m.has(n):
+                    m.set(n, Enum("true" if as_bool(m, n, None) else "false"))
+        t = str(L.get("type"))
+        if t in ("Convolution", "Deconvolution") and L.get("convolution_param") is not None:
+            cp = L.get("convolution_param")
+            k = _conv_spatial(who, cp, "kernel_size", "kernel_h", "kernel_w", 0, True)
+            pad = _conv_spatial(who, cp, "pad", "pad_h", "pad_w", 0, False)
+            stride = _conv_spatial(who, cp, "stride", "stride_h", "stride_w", 1, False)
+            dil = _conv_spatial(who, cp, "dilation", None, None, 1, False)
+            axis = int(cp.get("axis", 1))
+            if axis not in (1, -3):
+                raise ValueError("%saxis %d: only 2-D convolution over the last two axes (axis 1) is supported" % (who, axis))
+            if as_bool(cp, "force_nd_im2col", False):
+                raise ValueError("%sforce_nd_im2col: true is not supported" % who)
+            if t == "Deconvolution" and dil != 1:
+                raise ValueError("%sdilation %d: a Deconvolution's dilation must be 1" % (who, dil))
+            for n in ("kernel_size", "pad", "stride", "dilation", "kernel_h", "kernel_w", "pad_h", "pad_w", "stride_h", "stride_w"):
+                cp.clear(n)
+            for n, v in (("kernel_size", k), ("pad", pad), ("stride", stride), ("dilation", dil)):
+                cp.add(n, v)
+        elif t == "Concat":
+            who = "Concat '%s': " % L.get("name", "")
+            cc = L.get("concat_param")
+            has_dim, has_axis = cc is not None and cc.has("concat_dim"), cc is not None and cc.has("axis")
+            if has_dim and has_axis:
+                raise ValueError("%sboth axis and concat_dim given: it is one or the other" % who)
+            axis = int(cc.get("concat_dim")) if has_dim else int(cc.get("axis")) if has_axis else 1
+            if has_dim and axis < 0:
+                raise ValueError("%sconcat_dim %d must not be negative" % (who, axis))
+            if not 0 <= (axis + 4 if axis < 0 else axis) <= 3:
+                raise ValueError("%s%s %d is outside a 4-D blob" % (who, "concat_dim" if has_dim else "axis", axis))
+            if cc is None:
+                cc = L.add("concat_param", Msg())
+            cc.clear("concat_dim")
+            cc.clear("axis")
+            cc.add("axis", axis + 4 if axis < 0 else axis)
+        elif t == "Softmax":
+            axis = int(L.get("softmax_param").get("axis", 1)) if L.get("softmax_param") is not None else 1
+            if axis not in (1, -3):
+                raise ValueError("Softmax '%s': axis %d: only the softmax over axis 1 is supported" % (L.get("name", ""), axis))
+        elif t == "Reshape":
+            rp = L.get("reshape_param")
+            ax, na = (int(rp.get("axis", 0)), int(rp.get("num_axes", -1))) if rp is not None else (0, -1)
+            if ax != 0 or na != -1:
+                raise ValueError("Reshape '%s': axis %d / num_axes %d: only a reshape of the whole blob (axis 0, num_axes -1) is "
+                                 "supported" % (L.get("name", ""), ax, na))
+    return out

@@ -34,6 +34,8 @@ def synth_params(net_msg, seed=1234, cls_bias=4.0):
     naming the same ``param {name:}`` share one tensor.  Returns
     {layer_name: [w, b]} with Caffe blob shapes.  Used by BOTH the oracle net and
     the HIP net (through Net.params) so they hold identical values."""
+    from .prototxt import normalize_graph
+    net_msg = normalize_graph(net_msg)        # (the geometry as the runtime's graph reader resolves it, or its refusal)
     rng = np.random.default_rng(seed)
     shapes = infer_channels(net_msg)
     params = {}
@@ -77,6 +79,8 @@ def synth_params(net_msg, seed=1234, cls_bias=4.0):
 
 def infer_channels(net_msg, in_ch=3):
     """Channel count of every blob (enough shape inference to size weights)."""
+    from .prototxt import normalize_graph
+    net_msg = normalize_graph(net_msg)
     ch = {"data": in_ch, "im_info": 1}
     for n, shp in zip(net_msg.getall("input"), net_msg.getall("input_shape")):
         dims = shp.getall("dim")
