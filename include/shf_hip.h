@@ -436,6 +436,14 @@ int shf_calib_matrix_pipe(int bf16, int zero_eighths, int constant_operands, int
  * runs the slim three-blocks-per-CU form of the 4-wave kernel.  Returns the number of launches, -1 with a message. */
 int shf_debug_conv_plan(int cin, int cout, int h, int w, int in_split, int pooled, long long* lds_bytes, long long* grid_blocks,
                         int* slim);
+/* Diagnostics (tests only): the same for a grouped pass over n units (b[i], h[i], w[i]), n <= 16 (b NULL: one image each), planned for `cus` compute
+ * units (0: SHF_CONV_CUS, or the device's count).  first_pair != 0: the plan of conv1_2 fused with conv1_1 (cin = cout =
+ * 64) instead of a dual-tile family layer.  launches[8 * i ..] of launch i (at most two): grid, dynamic LDS bytes, tile
+ * rows, pixel tiles per block, tile_base (the first pixel tile of the launch), ntile_blocks (as the kernel receives it),
+ * slim form (0 / 1), persistent first pair (0 / 1); *pc_tab: the persistent pair keeps its per-block tile table (0 / 1).
+ * Nothing is launched; no GPU is needed.  Returns the number of launches, -1 with a message. */
+int shf_debug_conv_plan_group(int n, const int* b, const int* h, const int* w, int cin, int cout, int in_split, int pooled, int first_pair,
+                              int cus, long long* launches, int* pc_tab);
 /* stream synchronise (end of a timed region) */
 int shf_net_sync(shf_net* net);
 

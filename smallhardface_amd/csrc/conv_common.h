@@ -764,7 +764,7 @@ int launch_conv_plan(const ConvPlan& pl, int i, hipStream_t s);
 long long conv_fill(ConvPlan& pl, const ConvArgs* as, int n, int nct, int th, int tw, bool scalar_loads = false);
 // the kernel tables' LDS opt-in (160 KiB)
 int conv_set_lds_attributes(const ConvKernel* t, int n);
-ConvPlan plan_conv_f16x3(const ConvArgs* as, int n);   // (conv_f16x3.hip: the split-fp16 modes)
+ConvPlan plan_conv_f16x3(const ConvArgs* as, int n, int plan_cus = 0);   // (conv_f16x3.hip: the split-fp16 modes)
 int conv_f16x3_init_attributes();
 
 }  // namespace shf

@@ -155,7 +155,10 @@ const ConvKnobs& conv_knobs() {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 4)
       cus = 256;
-    q.cus = cus;
+    // SHF_CONV_CUS >= 1: the planner cuts the work as for a device (or a partition) of that many CUs -- launches only,
+    // never a result; the clamp above is for the device's own count
+    const int plan_cus = env_int("SHF_CONV_CUS", 0);
+    q.cus = plan_cus >= 1 ? plan_cus : cus;
     return q;
   }();
   return k;
@@ -227,10 +230,9 @@ static bool w4_short_k(const ConvArgs* as) { return as[0].in.C <= 128; }
 // two-per-CU form (A/B, identity tests).
 static bool w4_slim(const ConvArgs* as) { return conv_knobs().w4_slim != 0 && w4_short_k(as) && as[0].in.C >= 64; }
 
-static int w4_pick_mt(const ConvArgs* as, int n, int nct) {
+static int w4_pick_mt(const ConvArgs* as, int n, int nct, int cus) {
   if (conv_knobs().w4_mt == 2 || conv_knobs().w4_mt == 4) return conv_knobs().w4_mt;
   if (w4_short_k(as)) return 2;
-  const int cus = conv_knobs().cus;
   long long t4 = 0, t2 = 0;
   for (int i = 0; i < n; ++i) {
     const long long tx = (as[i].in.W + f16x3::TW - 1) / f16x3::TW, B = as[i].in.B;
@@ -345,9 +347,11 @@ static void f16x3_timing_report(const ConvPlan& pl, hipStream_t s) {
 // The split-fp16 modes: the fused first pair (producer / consumer kernel, or the 8-wave kernel's FUSE1 form), the dual-tile
 // family (1x1: the GEMM kernel; dilated heads: single 16-row tiles; dilation 1: two-tile / single-tile blocks, 16 or 8 rows),
 // and the 8-wave kernel for what the others cannot take (Cout 64, other 1x1s, unaligned views, inputs of 4 GiB or more).
-ConvPlan plan_conv_f16x3(const ConvArgs* as, int n) {
+// `plan_cus` >= 1 (the plan probes only): plan for that many CUs instead of conv_knobs().cus.
+ConvPlan plan_conv_f16x3(const ConvArgs* as, int n, int plan_cus) {
   using namespace f16x3;
   const ConvKnobs& kn = conv_knobs();
+  const int cus = plan_cus >= 1 ? plan_cus : kn.cus;
   const ConvArgs& a = as[0];
   ConvPlan pl;
   if (a.img && (a.in.C != 64 || !a.w1t)) { pl.err = "conv f16x3: fused first layer needs 64 channels + transposed weights"; return pl; }
@@ -357,7 +361,7 @@ ConvPlan plan_conv_f16x3(const ConvArgs* as, int n) {
   const bool dual = family && a.k == 3 && a.dil == 1;
   const int BN = family ? (a.k == 1 ? 256 : 128) : (a.img || a.out.C % 128 || (a.k == 3 && a.dil != 1)) ? 64 : 128;
   const int nct = a.out.C / BN;
-  const int mt = dual ? w4_pick_mt(as, n, nct) : 4;
+  const int mt = dual ? w4_pick_mt(as, n, nct, cus) : 4;
   const long long tiles = conv_fill(pl, as, n, nct, family && a.k == 1 ? 0 : 4 * mt, family && a.k == 1 ? 256 : TW);
   if (tiles < 0) return pl;
   ConvK& p = pl.k;
@@ -394,7 +398,7 @@ ConvPlan plan_conv_f16x3(const ConvArgs* as, int n) {
       return pl;
     }
     // one block per CU walks the tiles (tile = block, block + grid, ...)
-    const long long grid = std::min<long long>(tiles, kn.cus);
+    const long long grid = std::min<long long>(tiles, cus);
     // the per-block tile table: fits (PC_TABN = 300 tiles per block) and packs (image < 256, tile row / column < 1024)?
     bool ok = kn.pc_tab != 0 && (tiles + grid - 1) / grid <= PcLds::PC_TABN;
     for (int i = 0; i < n; ++i)
@@ -412,7 +416,7 @@ ConvPlan plan_conv_f16x3(const ConvArgs* as, int n) {
     // dual-tile family (conv_mfma_f16x3_w4d_kernel<.., MT, NTILE, ..>): every variant forms an output with the same
     // operations in the same order, so the choice below -- two tiles per block where that fills whole rounds of one
     // block per CU, single tiles for the rest -- never changes a result.
-    const long long per_round = kn.cus / nct > 0 ? kn.cus / nct : 1;   // pixel tiles (single) or pairs (dual) per round
+    const long long per_round = cus / nct > 0 ? cus / nct : 1;   // pixel tiles (single) or pairs (dual) per round
     const long long pairs = (tiles + 1) / 2;
     const double c1 = mt == 4 ? 1.0 : 0.56, c2 = mt == 4 ? 1.82 : 1.02;   // block cost: one / two tiles (w4_pick_mt's unit)
     const long long full2 = pairs / per_round;                  // whole rounds of dual blocks
@@ -464,6 +468,52 @@ int conv_f16x3_plan_probe(int Cin, int Cout, int H, int W, int in_split, int poo
     grid[i] = (long long)pl.l[i].grid.x;
     slim[i] = pl.l[i].kern >= kK.w4d_slim && pl.l[i].kern < kK.w4d_slim + 7 ? 1 : 0;
   }
+  return pl.nl;
+}
+
+// diagnostics (shf_debug_conv_plan_group): the launches of a grouped pass over n (b[i], h[i], w[i]) units (b null: 1) -- the dual-tile
+// family's cover, or with first_pair the plan of conv1_2 fused with conv1_1 (64 -> 64) -- planned for `cus` CUs (0: the
+// knob's or the device's).  out[8 * launch ..]: grid, LDS bytes, tile rows, tiles per block, tile_base, ntile_blocks, slim,
+// persistent; *pc_tab: ConvK::pc_tab.  Nothing is launched and no device memory is touched.
+int conv_f16x3_plan_probe_group(int n, const int* B, const int* H, const int* W, int Cin, int Cout, int in_split, int pooled, int first_pair,
+                                int cus, long long* out, int* pc_tab) {
+  alignas(16) static float dummy[4];
+  if (n < 1 || n > MAX_GROUP) { set_error("conv plan probe: 1..16 members"); return -1; }
+  ConvArgs as[MAX_GROUP];
+  for (int i = 0; i < n; ++i) {
+    ConvArgs& a = as[i];
+    const int b = B ? B[i] : 1;
+    a.in = View{dummy, b, H[i], W[i], Cin, Cin, 0};
+    a.out = View{dummy, b, H[i], W[i], Cout, Cout, 0};
+    if (pooled) a.pool = View{dummy, b, (H[i] + 1) / 2, (W[i] + 1) / 2, Cout, Cout, 0};
+    a.wsplit16 = dummy;
+    a.in_split = in_split ? 1 : 0;
+    if (first_pair) {
+      a.img = dummy; a.w1t = dummy; a.w1f = dummy; a.b1 = dummy; a.wsplit16r = dummy;
+    } else {
+      a.wsplit16h = dummy;
+    }
+  }
+  const ConvPlan pl = plan_conv_f16x3(as, n, cus);
+  if (pl.nl == 0) { set_error(pl.err.empty() ? "conv f16x3: no plan" : pl.err); return -1; }
+  for (int i = 0; i < pl.nl; ++i) {
+    const ConvLaunch& L = pl.l[i];
+    const ConvKernel* k = L.kern;
+    const bool slim = k >= kK.w4d_slim && k < kK.w4d_slim + 7, pc = k >= &kK.pc[0][0] && k < &kK.pc[0][0] + 8;
+    const bool w4 = k >= &kK.w4d[0][0][0] && k < &kK.w4d[0][0][0] + 28;
+    int rows = 16, ntile = 1;   // (the first pair and the 8-wave kernel: 16-row tiles, one at a time)
+    if (slim) rows = 8;
+    if (w4) {
+      const int idx = (int)(k - &kK.w4d[0][0][0]) / 7;   // [MT 4, 2][NTILE 2, 1]
+      rows = idx / 2 ? 8 : 16;
+      ntile = idx % 2 ? 1 : 2;
+    }
+    long long* o = out + 8 * i;
+    o[0] = (long long)L.grid.x; o[1] = (long long)L.lds; o[2] = rows; o[3] = ntile; o[4] = L.tile_base; o[5] = L.ntile_blocks;
+    o[6] = slim ? 1 : 0;
+    o[7] = pc && k >= &kK.pc[1][0] ? 1 : 0;
+  }
+  *pc_tab = pl.k.pc_tab;
   return pl.nl;
 }
 

@@ -927,6 +927,18 @@ int shf_debug_conv_plan(int cin, int cout, int h, int w, int in_split, int poole
   return nl;
   API_END(-1)
 }
+int shf_debug_conv_plan_group(int n, const int* b, const int* h, const int* w, int cin, int cout, int in_split, int pooled, int first_pair,
+                              int cus, long long* launches, int* pc_tab) {
+  API_BEGIN
+  if (!h || !w || !launches || !pc_tab || n < 1 || cin < 1 || cout < 1 || cus < 0) throw std::runtime_error("debug_conv_plan_group: bad arguments");
+  for (int i = 0; i < n; ++i)
+    if (h[i] < 1 || w[i] < 1 || (b && b[i] < 1)) throw std::runtime_error("debug_conv_plan_group: bad arguments");
+  if (first_pair && (cin != 64 || cout != 64)) throw std::runtime_error("debug_conv_plan_group: the first pair is 64 -> 64");
+  const int nl = conv_f16x3_plan_probe_group(n, b, h, w, cin, cout, in_split, pooled, first_pair, cus, launches, pc_tab);
+  if (nl < 0) return -1;
+  return nl;
+  API_END(-1)
+}
 int shf_net_sync(shf_net* net) {
   API_BEGIN
   HIP_THROW(hipStreamSynchronize(net->stream));

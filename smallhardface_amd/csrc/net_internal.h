@@ -385,6 +385,8 @@ int conv_out(int n, int k, int pad, int stride, int dil);
 namespace shf {
 int calib_matrix_pipe(int bf16, int zero_eighths, int constant, int iters, int reps, double* tflops);   // calib.hip
 int conv_f16x3_plan_probe(int Cin, int Cout, int H, int W, int in_split, int pooled, long long* lds, long long* grid, int* slim);   // conv_f16x3.hip
+int conv_f16x3_plan_probe_group(int n, const int* B, const int* H, const int* W, int Cin, int Cout, int in_split, int pooled, int first_pair,
+                                int cus, long long* out, int* pc_tab);   // conv_f16x3.hip
 }
 using namespace shf;
 

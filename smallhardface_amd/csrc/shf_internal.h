@@ -117,7 +117,10 @@ struct ConvKnobs {
   bool pc;          // SHF_F16X3_PC (default on): the fused first pair on the producer / consumer kernel
   bool pc_persist;  // SHF_F16X3_PC_PERSIST (default on): the fused first pair as one block per CU walking the tiles
   bool split_act;   // SHF_F16X3_SPLIT_ACT (default on): blobs read only by the dual-tile family are stored split (net_graph.cpp)
-  int cus;
+  int cus;          // the CU count the PLANNER cuts work by (16- or 8-row tiles, the dual-tile cover, the persistent first pair's
+                    // grid): the device's (256 where it cannot be read or is under 4), or SHF_CONV_CUS where that is >= 1 -- a
+                    // partition's count, or a small one under which the tests' maps reach every branch.  It changes how a layer
+                    // is cut into launches, never a result; nothing but plan_conv_f16x3 reads it (calib.hip asks the device)
 };
 const ConvKnobs& conv_knobs();
 bool conv_f16x3_eligible(int Cin, int Cout, int k, int pad, int dil);

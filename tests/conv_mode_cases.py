@@ -22,6 +22,7 @@ import numpy as np
 from oracle import conv_modes as CM
 from oracle import oracle as O
 from smallhardface_amd import prototxt as P
+from tests import conv_plan_cases as PL
 from tests import helpers as H
 from tests.test_gpu_fused_forms import conv as conv_txt, pool as pool_txt
 
@@ -307,9 +308,13 @@ def model(case, grid, h, w, mode, inputs=None, wrong=None, wrong_layer=None, pro
 
 
 # ------------------------------------------------------------------------------------------------------------
-# which kernel form must run (the planner on 256 compute units: maps this small are one round of single 8-row tiles)
+# which kernel form must run.  Without a "plan" entry in `knobs`: the planner on 256 compute units, where maps this small are
+# one round of single 8-row tiles ("mt" / "nt": a form forced by knob).  knobs["plan"] = dict(cus=, units=[(h, w), ..] of the
+# net's input, env={the planner's knobs as environment variables}): tile rows and cover of every dilation-1 family layer come
+# from the planner's restatement (tests/conv_plan_cases.py) for that CU count -- a hybrid cover is one launch of the two-tile
+# class AND one of the single-tile class.
 # ------------------------------------------------------------------------------------------------------------
-def _conv_class(L, mode, split_in, knobs=None):
+def _conv_class(L, mode, split_in, knobs=None, units=None):
     cin, cout, k, dil = L["cin"], L["nout"], L["k"], L["dil"]
     bf = mode == "bf16"
     if mode == "fp32" or not CM.eligible(cin, cout, k, dil):
@@ -321,6 +326,10 @@ def _conv_class(L, mode, split_in, knobs=None):
             return K1
         if dil != 1:
             return W4(True, dil=dil)
+        pl = (knobs or {}).get("plan")
+        if pl:
+            p = PL.plan(units, cin, cout, pl["cus"], knobs=PL.knobs_of(pl.get("env", {})))
+            return [W4(split_in and not bf, p["mt"], q["ntile"]) for q in p["launches"]]
         mt, nt = (knobs or {}).get("mt", 2), (knobs or {}).get("nt", 1)
         return W4(split_in and not bf, mt, nt)
     bn = 64 if (cout % 128 or (k == 3 and dil != 1)) else 128
@@ -335,7 +344,10 @@ def expected_classes(case, mode, knobs=None):
     add = lambda c: out.__setitem__(c, out.get(c, 0) + 1)
     split_blob = {}
     heads_done = False
+    sizes = {"data": [tuple(u) for u in (knobs or {}).get("plan", {}).get("units", [])]}      # blob -> the units' map sizes
     for L in graph:
+        if L.get("bottom") in sizes:
+            sizes[L["name"]] = [((h + 1) // 2, (w + 1) // 2) for h, w in sizes[L["bottom"]]] if L["op"] == "pool" else sizes[L["bottom"]]
         if L["op"] == "pool":
             prod = [M for M in graph if M["name"] == L["bottom"]][0]
             if not (fused and prod["op"] == "conv" and CM.eligible(prod["cin"], prod["nout"], prod["k"], prod["dil"])):
@@ -362,5 +374,7 @@ def expected_classes(case, mode, knobs=None):
         # split-format input: every reader of the bottom blob is a family-shaped convolution of an fp16 mode on the fused path
         rd = [M for M in graph if M.get("bottom") == L["bottom"] and M["op"] == "conv"]
         split_in = fused and mode != "bf16" and all(CM.family_shape(M["cin"], M["nout"], M["k"], False) for M in rd)
-        add(_conv_class(L, mode, split_in, knobs))
+        cls = _conv_class(L, mode, split_in, knobs, sizes.get(L["bottom"]))
+        for c in (cls if isinstance(cls, list) else [cls]):
+            add(c)
     return out

@@ -24,6 +24,7 @@ import pytest
 
 from oracle import conv_modes as CM
 from tests import conv_mode_cases as K
+from tests import conv_plan_cases as PL
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -91,9 +92,18 @@ def run_case(name, h, w, grids):
     return arrays, meta
 
 
+def plan_knobs(h, w, env=None, knobs=None):
+    """`knobs` for K.expected_classes with the cover of the dilation-1 family layers from the planner's restatement, for
+    the CU count this process's library plans by (256 on the full card, where nothing changes) under the knobs of `env`."""
+    from smallhardface_amd import _lib
+    return dict(knobs or {}, plan=dict(cus=PL.device_cus(_lib.load()), units=[(h, w)], env=dict(env or {})))
+
+
 def check_case(name, h, w, grids, arrays, meta, knobs=None):
     case = K.case_of(name)
     assert meta["range_fallbacks"] == 0
+    if "plan" not in (knobs or {}):
+        knobs = plan_knobs(h, w, knobs=knobs)
     for grid in grids:
         params = K.grid_params(case, grid)
         for mode in K.modes_of(grid, case["fused"]):
@@ -189,7 +199,7 @@ def test_knob_selected_form_bits_in_every_mode(forms, form, name, h, w):
     arrays, meta = forms[form]
     tag = "%s-%dx%d" % (name, h, w)
     mine = {k[len(tag) + 1:]: v for k, v in arrays.items() if k.startswith(tag + "/")}
-    check_case(name, h, w, FUSED_GRIDS, mine, meta[tag], FORMS[form][1])
+    check_case(name, h, w, FUSED_GRIDS, mine, meta[tag], plan_knobs(h, w, FORMS[form][0], FORMS[form][1]))
     if "pair" not in form:
         assert meta["slim"] == 0      # (none of the four family forms is the slim one, whose class the two-per-CU form shares)
 
@@ -227,12 +237,14 @@ def test_set_layer_products_on_the_per_layer_path():
     assert gnet.range_fallbacks == 0
 
 
-def _read_group(head, members, onet, datas, infos):
+def _read_group(head, members, onet, datas, infos, case=None):
+    """One grouped pass per 32 channels of the case's probed blob (a single-blob tail; default: the 128 channels of "slim")."""
+    channels = 128 if case is None else [L for L in case["graph"] if L["name"] == case["probe"]][0]["nout"]
     outs = [None] * len(members)
     for m, d, i in zip(members, datas, infos):
         m.blobs['data'].reshape(*d.shape)
         m.blobs['im_info'].reshape(*i.shape)
-    for c0 in range(0, 128, 32):
+    for c0 in range(0, channels, 32):
         H.readout_set_predictors(head, onet, c0)
         head.forward_group(members, [dict(data=d, im_info=i) for d, i in zip(datas, infos)])
         for k, m in enumerate(members):

@@ -783,14 +783,16 @@ for u in units:
     gnet.detect_add_level(*u, thresh=0.05)
 buf = torch.empty((400000, 5), dtype=torch.float32, device="cuda")
 n = gnet.detect_export(buf.data_ptr(), 400000)
-np.savez(sys.argv[1], voted=voted, raw=buf[:n].cpu().numpy())
+np.savez(sys.argv[1], voted=voted, raw=buf[:n].cpu().numpy(), sizes=np.array([(u[1], u[2]) for u in units]))
 ''')
     outs = {}
     for name, env in (("default", {}), ("no_split_act", {"SHF_F16X3_SPLIT_ACT": "0"}), ("no_w4", {"SHF_F16X3_W4": "0"}),
                       ("single_tile", {"SHF_F16X3_W4D_NTILE": "1"}), ("dual_tile", {"SHF_F16X3_W4D_NTILE": "2"}),
                       ("rows8", {"SHF_F16X3_W4_MT": "2"}), ("rows16", {"SHF_F16X3_W4_MT": "4"}), ("no_pc", {"SHF_F16X3_PC": "0"}),
                       ("pc_no_tile_table", {"SHF_F16X3_PC_TAB": "0"}), ("three_head_launches", {"SHF_F16X3_HEADS3": "0"}),
-                      ("pc_block_per_tile", {"SHF_F16X3_PC_PERSIST": "0"})):
+                      ("pc_block_per_tile", {"SHF_F16X3_PC_PERSIST": "0"}),
+                      # the planner cutting the same work for 1, 3 and 32 compute units: other tile rows, covers and walks
+                      ("cus1", {"SHF_CONV_CUS": "1"}), ("cus3", {"SHF_CONV_CUS": "3"}), ("cus32", {"SHF_CONV_CUS": "32"})):
         out = str(tmp_path / (name + ".npz"))
         e = dict(os.environ, PYTHONPATH=root, **env)
         r = subprocess.run([sys.executable, str(script), out, conv_mode], env=e, cwd=root, capture_output=True, text=True,
@@ -799,9 +801,20 @@ np.savez(sys.argv[1], voted=voted, raw=buf[:n].cpu().numpy())
         outs[name] = np.load(out)
     assert len(outs["default"]["voted"]) > 0 and len(outs["default"]["raw"]) > len(outs["default"]["voted"])
     # same arithmetic, different data path: bit-identical, merged and un-merged
-    for name in ("no_split_act", "single_tile", "dual_tile", "rows8", "rows16", "pc_block_per_tile", "pc_no_tile_table", "three_head_launches"):
+    for name in ("no_split_act", "single_tile", "dual_tile", "rows8", "rows16", "pc_block_per_tile", "pc_no_tile_table", "three_head_launches",
+                 "cus1", "cus3", "cus32"):
         for key in ("voted", "raw"):
             assert outs[name][key].shape == outs["default"][key].shape and np.array_equal(outs[name][key], outs["default"][key]), (name, key)
+    # at cus1 the first pair of the grouped pass is ONE block walking every tile of every unit: with its per-block tile table,
+    # or -- past 300 tiles, by the planner's own decision -- decoding tile by tile.  Which of the two ran, from the probe:
+    from smallhardface_amd import _lib
+    from tests import conv_plan_cases as PL
+    sizes = [tuple(int(v) for v in u) for u in outs["cus1"]["sizes"]]
+    pair = PL.probe(_lib.load(), sizes, 64, 64, cus=1, first_pair=True)
+    tiles = sum(PL.member_tiles(sizes, 16))
+    assert pair["launches"][0]["grid"] == 1 and pair["launches"][0]["ntile_blocks"] == tiles
+    assert pair["pc_tab"] == (1 if tiles <= PL.PC_TABN and PL.knobs_of(os.environ)["pc_tab"] else 0), (tiles, pair)
+    print("cus1: the first pair's one block walks %d tiles of %d units %s its tile table" % (tiles, len(sizes), "with" if pair["pc_tab"] else "WITHOUT"))
     # other kernels for the same layers: fp32-class agreement of the rows that go into the merge (a row may cross the
     # > 0.05 cut on one side only)
     for name in ("no_w4", "no_pc"):
