@@ -9,7 +9,8 @@ so is the combine kernel (eltwise.hip): coeff * x and the add of an Eltwise SUM 
 kernel (norm.hip): BatchNorm's subtraction and division, Scale's product and add each round once; and the depthwise
 convolution (conv_dw.hip): its fmaf chain, bias add and binary64 form are compiled as written; and the channel-L2-norm
 kernel (l2norm.hip): Normalize's sum of squares, + eps, square root, division and product each round once; and the pooling
-kernel (pool.hip): AVE's sum and its one division.
+kernel (pool.hip): AVE's sum and its one division; and the neuron kernel (neuron.hip): every product and add of PReLU,
+Sigmoid, ELU, BNLL, Power, Exp and Log rounds once, in Caffe's order, around the library's expf / logf / tanhf / powf.
 """
 import os
 import subprocess
@@ -31,6 +32,7 @@ SOURCES = [
     ("norm.hip", ["-ffp-contract=off"]),
     ("l2norm.hip", ["-ffp-contract=off"]),
     ("pool.hip", ["-ffp-contract=off"]),
+    ("neuron.hip", ["-ffp-contract=off"]),
     ("tail.hip", ["-ffp-contract=off"]),
     ("class_lists.hip", ["-ffp-contract=off"]),
     ("merge.hip", ["-ffp-contract=off"]),

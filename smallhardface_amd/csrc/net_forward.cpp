@@ -29,7 +29,7 @@ const char* const kProfNames[PC_COUNT] = {"conv_mfma_f32_kernel<3, 1, 128, 8, 16
                                            "conv_first_kernel", "conv_direct_kernel", "conv_mfma_f64_kernel", "maxpool_kernel",
                                            "deconv_depthwise", "detect_tail", "box_merge", "layout", "h2d_copy", "d2h_copy",
                                            "eltwise_combine", "conv_mfma_gen_kernel", "channel_affine", "conv_dw_kernel",
-                                           "channel_l2norm", "pool_kernel"};
+                                           "channel_l2norm", "pool_kernel", "neuron"};
 
 int run_conv_plan(const ConvPlan& pl, hipStream_t s, Prof& prof, double flops, double bytes) {
   if (!pl.err.empty()) {
@@ -314,6 +314,16 @@ void shf_net::add_cost(int li, bool fused, int heads, double& flops, double& byt
     flops += 3.0 * out;
     return;
   }
+  if (L.op == OP_NEURON) {
+    // the neuron launch: one read and one write per element (the constant form writes only, booked alike); operations per
+    // element, a library call counted as one: PReLU 2 (product, add), Sigmoid 4, TanH 1, ELU 3, AbsVal 1, Threshold 1, BNLL
+    // 4, Power 2 without pow and 3 with it, the constant 0, Exp 3, Log 4
+    static const double kOps[NEURON_FORMS] = {2, 4, 1, 3, 1, 1, 4, 2, 3, 0, 3, 4};
+    const double out = (double)blobs[L.tops[0]].count();
+    bytes += 8.0 * out;
+    flops += kOps[L.neuron_form] * out;
+    return;
+  }
   const Blob& ib = blobs[L.bottoms[0]];
   const Blob& ob = blobs[L.tops[0]];
   bytes += 4.0 * (ib.count() + heads * (double)ob.count());
@@ -590,6 +600,18 @@ void run_pass(const Pass& p) {
         ProfScope ps(h.prof, p.s, PC_L2NORM, c.first, c.second);
         CHECK_RC_LAYER(launch_channel_l2norm_group(na, p.n, (const float*)L.nv->g.p, L.eps, f64 ? 1 : 0, h.fp16_mode() ? flag : nullptr, p.s),
                        L.name);
+        break;
+      }
+      case OP_NEURON: {
+        // one launch over the lanes of the pass (PReLU's slope vector is the net's, shared by the lanes)
+        NormArgs na[kMaxGroup];
+        for (int m = 0; m < p.n; ++m) na[m] = p.u[m].lane->norm_args(li);
+        NeuronSpec sp;
+        sp.form = L.neuron_form; sp.a = L.neuron_a; sp.b = L.neuron_b; sp.c = L.neuron_c;
+        sp.slope = L.neuron_form == NEURON_PRELU ? (const float*)L.nv->g.p : nullptr;
+        const auto c = cost(li, 0, p.n, 1);
+        ProfScope ps(h.prof, p.s, PC_NEURON, c.first, c.second);
+        CHECK_RC_LAYER(launch_neuron_group(na, p.n, sp, f64 ? 1 : 0, h.fp16_mode() ? flag : nullptr, p.s), L.name);
         break;
       }
       case OP_TAIL:

@@ -131,7 +131,18 @@ const TypedField kTypedFields[] = {
     {"softmax_param", "axis", 'i'}, {"reshape_param", "axis", 'i'}, {"reshape_param", "num_axes", 'i'},
     {"python_param", "share_in_parallel", 'b'}, {"shape", "dim", 'i'}, {"input_shape", "dim", 'i'},
     {"scale_filler", "value", 'f'},
+    {"prelu_param", "channel_shared", 'b'}, {"elu_param", "alpha", 'f'}, {"threshold_param", "threshold", 'f'},
+    {"power_param", "power", 'f'}, {"power_param", "scale", 'f'}, {"power_param", "shift", 'f'},
+    {"exp_param", "base", 'f'}, {"exp_param", "scale", 'f'}, {"exp_param", "shift", 'f'},
+    {"log_param", "base", 'f'}, {"log_param", "scale", 'f'}, {"log_param", "shift", 'f'},
 };
+
+// the layer types that run the neuron kernel (neuron.hip)
+bool neuron_type(const std::string& t) {
+  for (const char* n : {"PReLU", "Sigmoid", "TanH", "ELU", "AbsVal", "Threshold", "BNLL", "Power", "Exp", "Log"})
+    if (t == n) return true;
+  return false;
+}
 
 bool bool_text(const std::string& s, bool& v) {   // the spellings protobuf's text format takes for a bool
   if (s == "true" || s == "True" || s == "t" || s == "1") { v = true; return true; }
@@ -680,6 +691,90 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
         throw std::runtime_error(who + "bottom '" + blobs[L.bottoms[0]].name + "' is a net input: the layer reads NHWC activations, put a "
                                  "convolution in between");
       L.op = OP_L2NORM;
+    } else if (neuron_type(L.type)) {
+      // NeuronLayer::Reshape (neuron_layer.cpp:7-11: one bottom, one top of its shape, in place or not) and each type's
+      // LayerSetUp; what Caffe CHECKs there and aborts on is a refusal here
+      const std::string who = L.type + " '" + L.name + "': ";
+      if (L.bottoms.size() != 1 || L.tops.size() != 1)
+        throw std::runtime_error(who + "takes exactly one bottom and one top (" + std::to_string(L.bottoms.size()) + " / " +
+                                 std::to_string(L.tops.size()) + " given)");
+      // a float field of the layer's message, as the fp32 number Caffe holds
+      auto field = [&](const PMsg* m, const char* f, double dflt) {
+        const double v = m ? m->real(f, dflt) : dflt;
+        const float r = (float)v;
+        if (!std::isfinite(v) || !std::isfinite(r)) throw std::runtime_error(who + f + " is not a finite fp32 number");
+        return r;
+      };
+      // Exp / Log (exp_layer.cpp:12-22, log_layer.cpp:12-27): log(base) in binary64 from the fp32 base; -1 stands for e
+      auto log_of_base = [&](float base) {
+        if (base != -1.f && !(base > 0.f))
+          throw std::runtime_error(who + "base must be -1 (for e) or strictly positive");
+        const double lb = base == -1.f ? 1.0 : std::log((double)base);
+        if (lb == 0.0 || std::isnan(lb) || std::isinf(lb))
+          throw std::runtime_error(who + "base: log(base) is 0, NaN or inf, no base of an exponential or a logarithm");
+        return lb;
+      };
+      if (L.type == "PReLU") {
+        // PReLULayer::LayerSetUp (prelu_layer.cpp:12-45): the slope blob from its filler -- a constant filler's value, no filler
+        // 0.25; any other filler type is random in Caffe and stays 0.25 here, the caffemodel brings the values
+        const PMsg* pp = L.msg->sub("prelu_param");
+        L.prelu_shared = getb(pp, "channel_shared", false);
+        const PMsg* fl = pp ? pp->sub("filler") : nullptr;
+        if (fl && fl->str("type", "constant") == "constant") {
+          if (const PField* v = fl->get("value")) check_scalar(who, "prelu_param.filler.value", *v, 'f');
+          L.prelu_fill = (float)fl->real("value", 0.0);
+        }
+        L.neuron_form = NEURON_PRELU;
+      } else if (L.type == "Sigmoid") {
+        L.neuron_form = NEURON_SIGMOID;
+      } else if (L.type == "TanH") {
+        L.neuron_form = NEURON_TANH;
+      } else if (L.type == "ELU") {
+        L.neuron_form = NEURON_ELU;
+        L.neuron_a = field(L.msg->sub("elu_param"), "alpha", 1.0);
+      } else if (L.type == "AbsVal") {
+        L.neuron_form = NEURON_ABSVAL;
+      } else if (L.type == "Threshold") {
+        L.neuron_form = NEURON_THRESHOLD;
+        L.neuron_a = field(L.msg->sub("threshold_param"), "threshold", 0.0);
+      } else if (L.type == "BNLL") {
+        L.neuron_form = NEURON_BNLL;
+      } else if (L.type == "Power") {
+        // PowerLayer::LayerSetUp / Forward_cpu (power_layer.cpp:9-29): diff_scale_ = power * scale in fp32; where it is 0 the
+        // top is a constant, formed here in binary64 and rounded once
+        const PMsg* pp = L.msg->sub("power_param");
+        const float power = field(pp, "power", 1.0), scale = field(pp, "scale", 1.0), shift = field(pp, "shift", 0.0);
+        const float diff_scale = power * scale;
+        if (diff_scale == 0.f) {
+          L.neuron_form = NEURON_CONST;
+          L.neuron_a = power == 0.f ? 1.f : (float)std::pow((double)shift, (double)power);
+        } else {
+          L.neuron_form = power != 1.f ? NEURON_POWER_POW : NEURON_POWER_LIN;
+          L.neuron_a = power; L.neuron_b = scale; L.neuron_c = shift;
+        }
+      } else if (L.type == "Exp") {
+        // ExpLayer::LayerSetUp (exp_layer.cpp:12-27): inner = log(base) * scale, outer = base ^ shift (1 for shift 0), in
+        // binary64 from the fp32 fields, rounded once (Caffe: in fp32 from float library calls -- an ulp apart at most)
+        const PMsg* ep = L.msg->sub("exp_param");
+        const float base = field(ep, "base", -1.0), scale = field(ep, "scale", 1.0), shift = field(ep, "shift", 0.0);
+        const double lb = log_of_base(base);
+        L.neuron_form = NEURON_EXP;
+        L.neuron_a = (float)(lb * (double)scale);
+        L.neuron_b = shift == 0.f ? 1.f : (float)(base != -1.f ? std::pow((double)base, (double)shift) : std::exp((double)shift));
+      } else {
+        // LogLayer::LayerSetUp (log_layer.cpp:12-30): base_scale = 1 / log(base), likewise
+        const PMsg* lp = L.msg->sub("log_param");
+        const float base = field(lp, "base", -1.0), scale = field(lp, "scale", 1.0), shift = field(lp, "shift", 0.0);
+        const double bs = 1.0 / log_of_base(base);
+        if (std::isnan(bs) || std::isinf(bs) || !std::isfinite((float)bs))
+          throw std::runtime_error(who + "base: 1 / log(base) is NaN or inf");
+        L.neuron_form = NEURON_LOG;
+        L.neuron_a = scale; L.neuron_b = shift; L.neuron_c = (float)bs;
+      }
+      if (std::count(inputs.begin(), inputs.end(), L.bottoms[0]))
+        throw std::runtime_error(who + "bottom '" + blobs[L.bottoms[0]].name + "' is a net input: the layer reads NHWC activations, put a "
+                                 "convolution in between");
+      L.op = OP_NEURON;
     } else if (L.type == "Pooling") {
       // PoolingLayer::LayerSetUp (pooling_layer.cpp:14-77): Caffe CHECKs these and aborts, here the graph is refused
       const std::string who = "Pooling '" + L.name + "': ";
@@ -812,7 +907,8 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
     int rewriter = -1;
     for (size_t lj = li + 1; lj < layers.size() && rewriter < 0; ++lj) {
       const Layer& Q = layers[lj];
-      if ((Q.op == OP_RELU || Q.op == OP_NORM || Q.op == OP_L2NORM) && Q.bottoms[0] == Q.tops[0] && Q.tops[0] == L.tops[0]) rewriter = (int)lj;
+      if ((Q.op == OP_RELU || Q.op == OP_NORM || Q.op == OP_L2NORM || Q.op == OP_NEURON) && Q.bottoms[0] == Q.tops[0] && Q.tops[0] == L.tops[0])
+        rewriter = (int)lj;
     }
     if (rewriter >= 0) {
       for (int b : L.bottoms)
@@ -831,7 +927,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   // ---- what the combine launches read is a plain fp32 NHWC activation (not a blob of a proposal tail)
   for (const Layer& L : layers) {
     if (L.op != OP_ELTWISE && L.op != OP_CROP && L.op != OP_RELU && L.op != OP_CONCAT_COPY && L.op != OP_NORM && L.op != OP_L2NORM &&
-        L.op != OP_POOL)
+        L.op != OP_POOL && L.op != OP_NEURON)
       continue;
     for (int b : L.bottoms)
       if (blobs[b].kind != BK_NHWC)
@@ -844,7 +940,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   //      output, is read through its offsets by that Eltwise on the fused path and never written.
   for (size_t li = 0; li < layers.size(); ++li) {
     Layer& R = layers[li];
-    if ((R.op != OP_RELU && R.op != OP_NORM && R.op != OP_L2NORM) || R.bottoms[0] != R.tops[0]) continue;
+    if ((R.op != OP_RELU && R.op != OP_NORM && R.op != OP_L2NORM && R.op != OP_NEURON) || R.bottoms[0] != R.tops[0]) continue;
     const int x = R.tops[0];
     if (blobs[x].owner >= 0)   // a member of a zero-copy Concat: rewriting it AFTER the Concat would rewrite the Concat's top
       for (size_t lc = 0; lc < li; ++lc)
@@ -852,7 +948,7 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
           throw std::runtime_error(R.type + " '" + R.name + "': rewrites '" + blobs[x].name + "' in place after Concat '" + layers[lc].name +
                                    "' has taken it as a bottom (the Concat's top is a view of its bottoms here)");
     if (R.op == OP_NORM) continue;   // (their chains and folds: plan_norm_layers)
-    if (R.op == OP_L2NORM) continue;   // (a launch of its own, never folded)
+    if (R.op == OP_L2NORM || R.op == OP_NEURON) continue;   // (a launch of its own, never folded)
     int prod = -1;
     bool read_between = false;
     for (int lj = (int)li - 1; lj >= 0 && prod < 0; --lj) {
@@ -899,8 +995,8 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
   }
   for (size_t li = 0; li < layers.size(); ++li) {
     Layer& L = layers[li];
-    const bool l2 = L.type == "Normalize";
-    const bool norm = L.type == "BatchNorm" || L.type == "Scale" || l2;
+    const bool l2 = L.type == "Normalize", prelu = L.type == "PReLU";
+    const bool norm = L.type == "BatchNorm" || L.type == "Scale" || l2 || prelu;
     if (L.type != "Convolution" && L.type != "Deconvolution" && !norm) continue;
     const int cin = blobs[L.bottoms[0]].shape[1];
     std::vector<std::vector<int>> shapes;
@@ -909,6 +1005,10 @@ void shf_net::build(const std::string& text, const char* caffemodel) {
       // Normalize: the scale, (C) or with channel_shared a blob of 0 axes and one value (normalize_layer.cpp:36-41), from its filler
       shapes.push_back(L.l2_shared ? std::vector<int>() : std::vector<int>{cin});
       fill = L.l2_fill;
+    } else if (prelu) {
+      // PReLU: the slopes, (C) or with channel_shared a blob of 0 axes and one value (prelu_layer.cpp:22-37), from its filler
+      shapes.push_back(L.prelu_shared ? std::vector<int>() : std::vector<int>{cin});
+      fill = L.prelu_fill;
     } else if (norm) {
       // BatchNorm: mean (C), variance (C), the moving-average factor (1), zero as Caffe creates them; Scale: gamma (C) from
       // the default filler, the constant 1, and with bias_term beta (C), zero
@@ -1188,6 +1288,11 @@ void shf_net::infer_shapes() {
       if (bs.size() != 4)
         throw std::runtime_error("Normalize '" + L.name + "': bottom '" + blobs[L.bottoms[0]].name + "' is not 4-D");
       blobs[L.tops[0]].shape = bs;
+    } else if (L.op == OP_NEURON) {
+      // elementwise on a 4-D blob (neuron_layer.cpp:7-11: the top takes the bottom's shape)
+      if (bs.size() != 4)
+        throw std::runtime_error(L.type + " '" + L.name + "': bottom '" + blobs[L.bottoms[0]].name + "' is not 4-D");
+      blobs[L.tops[0]].shape = bs;
     } else if (L.type == "ReLU" || L.type == "Softmax" || L.type == "Split") {
       if (L.op == OP_RELU && bs.size() != 4)
         throw std::runtime_error("ReLU '" + L.name + "': bottom '" + blobs[L.bottoms[0]].name + "' is not 4-D");
@@ -1337,7 +1442,7 @@ void shf_net::plan_norm_layers(const std::map<int, int>& fused_by) {
   };
   for (int li = 0; li < nl; ++li) {
     Layer& L = layers[li];
-    if (L.op == OP_NORM || L.op == OP_L2NORM) L.nv = clone_src ? clone_src->layers[li].nv : std::make_shared<NormVecs>();
+    if (L.op == OP_NORM || L.op == OP_L2NORM || L.op == OP_NEURON) L.nv = clone_src ? clone_src->layers[li].nv : std::make_shared<NormVecs>();
   }
   // ---- folds: an in-place BatchNorm, an in-place Scale, or the two in that order, directly on a Convolution's top.  The
   //      convolution is no predictor of a proposal tail and shares its parameter blobs with no other layer (their device
@@ -1490,13 +1595,15 @@ void shf_net::commit_params(int li) {
     ++*wgen;
     return;
   }
-  if (L.type == "Normalize") {
-    // the scale the launch reads: C values, a channel_shared blob's one value broadcast, so that the kernel has one form
+  if (L.type == "Normalize" || L.type == "PReLU") {
+    // the scale (PReLU: the slopes) the launch reads: C values, a channel_shared blob's one value broadcast, so that the
+    // kernel has one form
     HIP_THROW(hipDeviceSynchronize());   // (shared by every lane: nothing may be in flight on any stream)
     ParamBlob& p = *L.params[0];
     const size_t C = (size_t)blobs[L.bottoms[0]].shape[1];
+    const bool shared = L.type == "PReLU" ? L.prelu_shared : L.l2_shared;
     std::vector<float> sc(C);
-    for (size_t c = 0; c < C; ++c) sc[c] = p.host[L.l2_shared ? 0 : c];
+    for (size_t c = 0; c < C; ++c) sc[c] = p.host[shared ? 0 : c];
     L.nv->g.ensure(C * 4);
     HIP_THROW(hipMemcpy(L.nv->g.p, sc.data(), C * 4, hipMemcpyHostToDevice));
     p.dirty = false;

@@ -181,13 +181,16 @@ void check_blob_dims(const std::vector<int>& shp, const std::string& name);   //
 // OP_L2NORM: a Normalize layer (across_spatial: false): one launch of the channel-L2-norm kernel (l2norm.hip), never folded
 // OP_POOL: a Pooling layer: maxpool_kernel (misc.hip) for MAX, square, quad-aligned layers, a 2x2/2 one possibly folded into
 // its producing convolution on the fused path; the pooling kernel (pool.hip) for everything else
-enum OpType { OP_SKIP, OP_CONV, OP_POOL, OP_DECONV, OP_TAIL, OP_ELTWISE, OP_CROP, OP_RELU, OP_CONCAT_COPY, OP_NORM, OP_L2NORM };
+// OP_NEURON: a PReLU, Sigmoid, TanH, ELU, AbsVal, Threshold, BNLL, Power, Exp or Log layer: one launch of the neuron kernel
+// (neuron.hip), never folded; in place it is a rewriter like OP_L2NORM
+enum OpType { OP_SKIP, OP_CONV, OP_POOL, OP_DECONV, OP_TAIL, OP_ELTWISE, OP_CROP, OP_RELU, OP_CONCAT_COPY, OP_NORM, OP_L2NORM, OP_NEURON };
 
 // what a BatchNorm / Scale layer's launch reads: per-channel vectors derived from its blobs at commit time (derive_norm),
 // shared by the lanes of a net like a weight pack
 struct NormVecs {
   DevBuf m, d, m64, d64;   // BatchNorm: mean * sf and sqrt(var * sf + eps), in fp32 (Caffe's operation order) and in binary64
   DevBuf g, b;             // Scale: its blobs.  Normalize: g = its scale, C values (a channel_shared one broadcast on commit)
+                           // PReLU: g = its slopes, likewise
 };
 
 struct Layer {
@@ -232,6 +235,12 @@ struct Layer {
   float eps = 1e-5f;               // BatchNorm: batch_norm_param.eps; Normalize: norm_param.eps (default 1e-10)
   bool l2_shared = false;          // Normalize: channel_shared (the blob has 0 axes and one value)
   float l2_fill = 1.f;             // Normalize: what the blob holds before a model is loaded (a constant scale_filler's value)
+  // the neuron layers (neuron.hip): the kernel form and its constants as NeuronSpec names them; Exp's and Log's derived ones
+  // (inner, outer, 1 / log(base)) are formed in binary64 at construction and rounded once
+  int neuron_form = 0;
+  float neuron_a = 0.f, neuron_b = 0.f, neuron_c = 0.f;
+  bool prelu_shared = false;       // PReLU: channel_shared (the blob has 0 axes and one value)
+  float prelu_fill = 0.25f;        // PReLU: what the blob holds before a model is loaded (a constant filler's value; none: 0.25)
   std::shared_ptr<NormVecs> nv;
   int chain_bn = -1, chain_sc = -1, chain_relu = -1;   // on a chain's head: its stages' layers (the head is one of them)
   int norm_conv = -1;              // BatchNorm / Scale: the convolution it is folded into

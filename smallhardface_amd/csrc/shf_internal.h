@@ -39,6 +39,7 @@ enum ProfClass {
   PC_CONV_DW,   // the depthwise convolution (conv_dw.hip), its fp32 and its f64 form
   PC_L2NORM,    // the channel-L2-norm kernel (l2norm.hip): Normalize with across_spatial: false
   PC_POOLGEN,   // the pooling kernel (pool.hip): AVE, global, rectangular and any-channel-count Pooling (PC_POOL: maxpool_kernel)
+  PC_NEURON,    // the neuron kernel (neuron.hip): PReLU, Sigmoid, TanH, ELU, AbsVal, Threshold, BNLL, Power, Exp, Log
   PC_COUNT
 };
 
@@ -193,6 +194,31 @@ int launch_channel_affine_group(const NormArgs* as, int n, const NormStages& st,
 // on the device.  ONE launch over n <= 16 members that share the layer (the lanes of a grouped pass); f64: the expression in
 // binary64, rounded once; range_flag as launch_combine_group's
 int launch_channel_l2norm_group(const NormArgs* as, int n, const float* scale, float eps, int f64, int* range_flag, hipStream_t s);
+// the neuron kernel (neuron.hip): out = f(in) per element, f one of Caffe's activation layers other than ReLU.  A form is one
+// instantiation of the kernel; Power is three of them (without pow, with it, and the constant of power * scale == 0).
+enum NeuronForm {
+  NEURON_PRELU,       // max(x, 0) + slope[c] * min(x, 0)
+  NEURON_SIGMOID,     // 0.5 * tanh(0.5 * x) + 0.5
+  NEURON_TANH,        // tanh(x)
+  NEURON_ELU,         // max(x, 0) + a * (exp(min(x, 0)) - 1)                  a = alpha
+  NEURON_ABSVAL,      // fabs(x)
+  NEURON_THRESHOLD,   // x > a ? 1 : 0                                         a = threshold
+  NEURON_BNLL,        // x > 0 ? x + log(1 + exp(-x)) : log(1 + exp(x))
+  NEURON_POWER_LIN,   // shift + scale * x (each step only if it changes x)     b = scale, c = shift
+  NEURON_POWER_POW,   // pow(shift + scale * x, power)                         a = power, b = scale, c = shift
+  NEURON_CONST,       // a (the input is not read)
+  NEURON_EXP,         // b * exp(a * x)                                        a = inner scale, b = outer scale
+  NEURON_LOG,         // c * log(b + a * x)                                    a = scale, b = shift, c = 1 / log(base)
+  NEURON_FORMS
+};
+struct NeuronSpec {
+  int form = NEURON_ABSVAL;
+  float a = 0.f, b = 0.f, c = 0.f;
+  const float* slope = nullptr;   // NEURON_PRELU: C values on the device
+};
+// ONE launch over n <= 16 members that share the layer (the lanes of a grouped pass); f64: the expression with the binary64
+// functions on the widened input, rounded once; range_flag as launch_combine_group's
+int launch_neuron_group(const NormArgs* as, int n, const NeuronSpec& sp, int f64, int* range_flag, hipStream_t s);
 // the pooling kernel (pool.hip): Caffe's MAX / AVE windows (pooling_layer.cpp:144-215) of any rectangular geometry, or the
 // whole map (`global`: the kernel is each member's own H x W, pad 0, stride 1, the output (B, C, 1, 1)).  It raises each
 // member's out_amax from its in_amax itself (every output is bounded by max |input|).  ONE launch over n <= 16 members that
